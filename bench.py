@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py — frames/s of the MI355X forward rasterizer on BASELINE.json's metric workload.
 
-  python bench.py [--gpus N --steps K --warmup W]          (N > 1: launched by torch.distributed.run)
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]     (N > 1: launched by torch.distributed.run)
+
+A plain run sets up, warms up, times the K steps, writes the last step's frame to DIR/frame.npy (float32, [H, W, 3]) when
+--dump-outputs is given, and prints the result line.  Everything else described below — the single-stream latency, per-stage
+times and roofline, PSNR against the CPU oracle, the CPU baseline and the extra legs — runs only with --full.
 
 A step = one complete 1920x1080 frame of the synthetic stand-in for MipNeRF-360 'bicycle' — the scene BASELINE.json's
 metric is quoted on (mip360_like(6_131_954, seed 361), ring camera 0) — in the reference's own
@@ -16,7 +20,7 @@ HIP stream with its own workspace (renderer.FramesInFlight); every frame is comp
 single-stream render (tests/test_gpu_parity.py); `single_stream` carries the same loop with ONE frame per launch sequence and one in
 flight (the per-frame latency), and the per-stage times / roofline are measured that way too.
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  With --full, besides the contract fields it carries
   roofline      HBM roofline of the dominant kernel (blend): algorithmic bytes 40*E + 12*P + 8*tiles per launch / its
                 measured average duration (HIP events on the launch stream) vs 8 TB/s, plus the figures of the pipes
                 that actually limit it (VALU issue, LDS) from the committed rocprofv3 counters
@@ -87,20 +91,31 @@ def parse():
                     help="single: every step renders --camera; all: steps cycle over the whole camera set (configs[3])")
     ap.add_argument("--input_dir", default="", help="real data: MipNeRF-360 scene dir with sparse/0/{images,cameras}.bin")
     ap.add_argument("--trained_model_path", default="", help="real data: INRIA model dir (point_cloud/iteration_30000/point_cloud.ply)")
-    ap.add_argument("--legs", default="configs2,early_out,camera_set,shards8,file_order,garden,box4k", help="extra legs at N=1 (comma list; '' = none)")
+    ap.add_argument("--legs", default="configs2,early_out,camera_set,shards8,file_order,garden,box4k", help="extra legs at N=1 with --full (comma list; '' = none)")
     ap.add_argument("--scene-order", default="morton", choices=["morton", "file"],
                     help="how the loader lays the gaussians' arrays out in HBM: along a Morton curve of their means (renderer.GaussianScene "
                          "spatial_order=True: the same frame up to the mutual order of gaussians at exactly equal depth, which the reference "
                          "leaves undefined) or in file order; the `file_order` leg reports the other one")
     ap.add_argument("--frames-in-flight", type=int, default=None,
                     help="independent batches of frames in flight per GPU, each on its own HIP stream and workspace (1 = one stream; the "
-                         "single-stream figure is reported beside the headline either way)")
+                         "single-stream figure is reported beside the headline with --full either way)")
     ap.add_argument("--views-per-launch", type=int, default=None,
                     help="frames per launch sequence of libgsr (gsr_render_batch; 1 = every frame its own ~22 dispatches, rounds 1-4)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-psnr", action="store_true")
     ap.add_argument("--cpu-budget-s", type=float, default=15.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure and check everything else: single-stream latency, per-stage times and "
+                         "roofline, PSNR vs the CPU oracle, the CPU baseline and the --legs (off: the headline alone)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame the last timed step computed to DIR/frame.npy (float32, [H, W, 3])")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, frame):
+    """The last timed step's frame as a caller receives it, widened to float32 (a bf16 store converts exactly)."""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frame.npy"), frame.float().cpu().numpy())
 
 
 def build_real_workload(args):
@@ -368,7 +383,7 @@ def main():
     cam = cams[0]
     ncam = len(cams)
     order_warm_ms = None
-    if spatial and scene.n:  # what the ordering costs once everything it uses is loaded: the permutation + one gather of the arrays
+    if args.full and spatial and scene.n:  # what the ordering costs once everything it uses is loaded: the permutation + one gather of the arrays
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         perm = renderer.scene_order(scene.t["means"])
@@ -482,9 +497,14 @@ def main():
     for k in range(S):
         if fif.rasterizers[k]._ws is not None:
             fif.stats(k)  # raises if ANY of the slot's frames exceeded max_pairs or the depth-sort bound
+    if args.dump_outputs and rank == 0:
+        last = frame
+        if last.dim() == 4:  # N > 1 with K > 1: the gathered batch; the last batch of the timed loop may hold fewer than K frames
+            last = last[(args.steps - 1) % K]
+        dump_outputs(args.dump_outputs, last)
     # the same loop with ONE frame per launch sequence and ONE in flight (one stream, one workspace): the per-frame latency figure
     single = None
-    if S > 1 or K > 1:
+    if args.full and (S > 1 or K > 1):
         one = renderer.FramesInFlight(scene, slots=1, max_pairs=need)
         one.set_sort_passes(R.sort_passes)
         st1 = {"f": 0, "b": 0}
@@ -542,8 +562,8 @@ def main():
             result["single_stream"] = single
 
     # ---- rank 0: per-stage timing + roofline of ITS shard (the whole frame at N=1), outside the timed region; at N=1 also
-    # ---- PSNR vs the oracle, the extra legs and the CPU baseline -------------------------------------------------------
-    if rank == 0:
+    # ---- PSNR vs the oracle, the extra legs and the CPU baseline; all of it only with --full ------------------------------
+    if args.full and rank == 0:
         if world == 1:
             frame = R.enqueue(cam, opts, out=strip_view)  # the frame checked against the oracle below is camera 0's (single-view path)
         full_opts = renderer.make_options(early_out_T=args.early_out_T, blend_impl=args.blend_impl, depth_sort_passes=R.sort_passes, colour_stage=args.colour_stage,
@@ -555,7 +575,7 @@ def main():
         if world > 1:
             result["roofline"]["note"] = "rank 0's shard (interleaved tile rows); " + result["roofline"]["note"]
 
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         legs = [x for x in args.legs.split(",") if x] if not real else []
         leg_imgs = {}
         steps_leg, warm_leg = args.steps, min(args.warmup, 5) + 1

@@ -309,7 +309,7 @@ def _run_bench_multi(backend, ranks, extra=(), timeout=900):
     port = 31500 + (os.getpid() % 2000)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(REPO, "bench.py"), "--gpus", str(ranks), "--steps", "6", "--warmup", "2",
-           "--gaussians", "400000", "--legs", "", "--no-psnr", "--no-cpu-baseline", *extra]
+           "--gaussians", "400000", "--full", "--legs", "", "--no-psnr", "--no-cpu-baseline", *extra]
     return subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=timeout)
 
 
@@ -337,6 +337,38 @@ def test_bench_py_with_two_ranks_over_gloo(G):
     read after the timed loop) must run to ONE well-formed JSON line.  The first 8-GPU lease must not be spent on a traceback."""
     r = _check_bench_line(_run_bench_multi("gloo", 2), 2)
     print(f"\nbench.py --gpus 2 over gloo (ranks share the GPU): {r['value']:.0f} frames/s, {r['ms_per_step']:.3f} ms per frame")
+
+
+def test_bench_py_plain_run_is_lean_and_dumps_the_last_frame(G, tmp_path):
+    """`bench.py --gpus 1` without --full: the headline alone (no single-stream leg, roofline, oracle, CPU baseline or other legs),
+    exactly --steps timed frames, and --dump-outputs writes the last timed frame: camera 0 of the same seeded scene, bit-identical
+    to a single-view render of it."""
+    import json
+
+    import bench
+
+    steps, n = 7, 400_000
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+           "--gaussians", str(n), "--dump-outputs", str(tmp_path)]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["n_gpus"] == 1 and r["steps"] == steps and r["warmup"] == 2 and r["config"]["gaussians"] == n
+    assert r["unit"] == "frames/s" and r["higher_is_better"] is True and r["dtype"] == "f32" and r["metric"].startswith("frames/sec @1080p")
+    assert r["value"] > 0 and abs(r["value"] * r["ms_per_step"] - 1e3) < 1e-3 * 1e3
+    assert not {"single_stream", "roofline", "stage_ms", "psnr_vs_oracle_db", "cpu_baseline", "early_out", "configs2", "camera_set",
+                "shards8", "file_order", "garden", "box4k"} & set(r)
+    img = np.load(tmp_path / "frame.npy")
+    assert img.dtype == np.float32 and img.shape == (1080, 1920, 3) and img.max() > 0.05
+
+    gen, _, seed, W, H, _ = bench.WORKLOADS["bicycle"]
+    packed = G.utils.pack_gaussians(getattr(G.synthetic, gen)(n, seed))
+    scene = G.renderer.GaussianScene.from_packed(packed, device="cuda:0", spatial_order=True)
+    cam, _ = _ring_camera(G, W, H, 0)
+    ref = G.renderer.Rasterizer(scene).render(cam, G.renderer.make_options()).cpu().numpy()
+    assert np.array_equal(img, ref)
 
 
 @pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs >= 2 GPUs for RCCL")
