@@ -222,6 +222,10 @@ int gsr_camera_setup(const double qvec[4], const double tvec[3], double fx_full,
 /* Bytes of scratch one frame needs for n gaussians, a width x height target and room for max_pairs
  * pairs.  max_pairs is the caller's bound on D = the (gaussian, 32x32 cell) pairs of a frame (frames wider than 4096 px:
  * (gaussian, 16x16 tile) pairs); GsrStats.n_pairs_bbox reports what a frame needed; exceeding it is reported, never UB. */
+/* The limits it and every render entry point apply (GSR_ERR_BAD_ARG past them): n in [0, GSR_MAX_GAUSSIANS], width and height in
+ * [1, GSR_MAX_FRAME_SIDE] (tile rects are ushort4: 65535 tiles per side), max_pairs in [0, GSR_MAX_PAIRS]. */
+#define GSR_MAX_GAUSSIANS 0x7FFFFFFFll
+#define GSR_MAX_FRAME_SIDE (65535 * GSR_TILE)
 int gsr_workspace_bytes(int64_t n, int32_t width, int32_t height, int64_t max_pairs, size_t *bytes /* [host] */);
 
 /* Stage 1 — per-gaussian preprocessing, fused: rasterize.py:354-420 (means, cov3D, opacity, SH colour,

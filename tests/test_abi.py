@@ -64,6 +64,29 @@ def test_workspace_query_and_error_codes():
     assert (o.reference_compat, o.early_out_T, o.tile_row_begin, o.tile_row_step, o.output_layout) == (1, 0.0, 0, 1, 0)
 
 
+def test_workspace_query_applies_the_render_entry_points_size_limits():
+    """gsr_workspace_bytes refuses what check_frame (api.hip) refuses: a frame side past 65535 tiles (tile rects are ushort4),
+    n past 2^31 - 1, max_pairs past GSR_MAX_PAIRS — and the limits stated in include/gsr.h are the ones _lib.py carries."""
+    from gsr_amd import _lib
+
+    text = open(os.path.join(REPO, "include", "gsr.h")).read()
+    assert re.search(r"#define GSR_MAX_FRAME_SIDE \(65535 \* GSR_TILE\)", text) and "#define GSR_TILE 16 " in text
+    assert re.search(r"#define GSR_MAX_GAUSSIANS 0x7FFFFFFFll", text) and re.search(r"#define GSR_MAX_PAIRS 0xFFFFE000ll", text)
+    side, n_max, p_max = _lib.GSR_MAX_FRAME_SIDE, _lib.GSR_MAX_GAUSSIANS, _lib.GSR_MAX_PAIRS
+    assert (side, n_max) == (1_048_560, 0x7FFFFFFF)
+    # the largest frame is accepted in either orientation, and sized by its 65535 tiles
+    wide, tall = _lib.workspace_bytes(1000, side, 16, 10_000), _lib.workspace_bytes(1000, 16, side, 10_000)
+    assert wide > _lib.workspace_bytes(1000, side - 16, 16, 10_000) and tall > 8 * 65535 and wide % 256 == 0 and tall % 256 == 0
+    assert _lib.workspace_bytes(n_max, 16, 16, 0) > 0 and _lib.workspace_bytes(0, 16, 16, p_max) > 0
+    refused = {"width": (10, side + 1, 16, 100), "height": (10, 16, side + 1, 100), "both": (10, side + 1, side + 1, 100),
+               "n": (n_max + 1, 16, 16, 100), "max_pairs": (10, 16, 16, p_max + 1), "int32 width": (10, 0x7FFFFFFF, 16, 100)}
+    for name, args in refused.items():
+        with pytest.raises(_lib.GsrError) as e:
+            _lib.workspace_bytes(*args)
+        assert e.value.code == _lib.GSR_ERR_BAD_ARG, name
+        assert b"range" in _lib.lib.gsr_last_error() or b"frame size" in _lib.lib.gsr_last_error(), name
+
+
 def test_gpu_entry_points_reject_bad_arguments_without_touching_a_gpu():
     from gsr_amd import _lib
 

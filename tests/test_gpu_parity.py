@@ -896,6 +896,11 @@ def test_c_abi_rejects_bad_arguments(G):
         "negative draw_limit": dict(opts=bad_opts(draw_limit=-1)), "negative n": dict(scene=bad_scene(n=-1)),
         "null means": dict(scene=bad_scene(means=None)), "misaligned sh": dict(scene=bad_scene(sh=sc.sh + 4)),
         "bad sh degree": dict(scene=bad_scene(sh_degree=4)), "bad sh dtype": dict(scene=bad_scene(sh_dtype=9)),
+        # the size limits of include/gsr.h, the same gsr_workspace_bytes applies (tests/test_abi.py)
+        "width past the limit": dict(camera=bad_cam(width=_lib.GSR_MAX_FRAME_SIDE + 1)),
+        "height past the limit": dict(camera=bad_cam(height=_lib.GSR_MAX_FRAME_SIDE + 1)),
+        "n past 2^31 - 1": dict(scene=bad_scene(n=_lib.GSR_MAX_GAUSSIANS + 1)),
+        "max_pairs past GSR_MAX_PAIRS": dict(max_pairs=_lib.GSR_MAX_PAIRS + 1),
     }
     for name, kw in cases.items():
         rc = call(**kw)
@@ -906,6 +911,8 @@ def test_c_abi_rejects_bad_arguments(G):
     assert call() == 0 and torch.equal(out, ref)   # and the library is still usable
     with pytest.raises(_lib.GsrError):
         _lib.workspace_bytes(10, 0, 10, 10)
+    with pytest.raises(_lib.GsrError):
+        _lib.workspace_bytes(10, _lib.GSR_MAX_FRAME_SIDE + 1, 10, 10)
 
 
 def test_depth_sort_plans_its_passes_from_the_key_range(G):

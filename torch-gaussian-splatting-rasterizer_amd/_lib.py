@@ -23,6 +23,8 @@ GSR_ERR_PAIR_OVERFLOW = -3
 GSR_ERR_HIP = -4
 GSR_ERR_SORT_PASSES = -5
 GSR_MAX_PAIRS = 0xFFFFE000  # include/gsr.h
+GSR_MAX_GAUSSIANS = 0x7FFFFFFF
+GSR_MAX_FRAME_SIDE = 65535 * 16
 GSR_MAX_BATCH_VIEWS = 8
 GSR_BOUNDS_BLOCK = 64
 

@@ -71,16 +71,26 @@ size_t carve_workspace(void *base, int64_t n, int width, int height, int64_t max
     return off;
 }
 
+// The size limits of include/gsr.h, shared by gsr_workspace_bytes and every render entry point: a workspace can only be sized for
+// a frame that can be rendered.
+static int check_sizes(int64_t n, int32_t width, int32_t height, int64_t max_pairs)
+{
+    if (n < 0 || n > GSR_MAX_GAUSSIANS) { set_error("n = %lld out of range [0, %lld]", (long long)n, (long long)GSR_MAX_GAUSSIANS); return GSR_ERR_BAD_ARG; }
+    // tile rects are ushort4 with an exclusive upper bound: at most 65535 tiles per side
+    if (width <= 0 || height <= 0 || width > GSR_MAX_FRAME_SIDE || height > GSR_MAX_FRAME_SIDE) {
+        set_error("bad frame size %dx%d (1 .. %d px per side)", width, height, GSR_MAX_FRAME_SIDE); return GSR_ERR_BAD_ARG;
+    }
+    // the sort kernels index pairs with 32-bit arithmetic, one 4096-pair tile past the last pair at most
+    if (max_pairs < 0 || max_pairs > GSR_MAX_PAIRS) { set_error("max_pairs = %lld out of range [0, %lld]", (long long)max_pairs, (long long)GSR_MAX_PAIRS); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
 static int check_frame(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                        size_t workspace_bytes, Workspace *ws)
 {
     if (!cam || !opts || !workspace) { set_error("null camera/options/workspace"); return GSR_ERR_BAD_ARG; }
-    if (n < 0 || n > 0x7FFFFFFF) { set_error("n = %lld out of range", (long long)n); return GSR_ERR_BAD_ARG; }
-    if (cam->width <= 0 || cam->height <= 0 || cam->width > 65535 * GSR_TILE || cam->height > 65535 * GSR_TILE) {
-        set_error("bad frame size %dx%d", cam->width, cam->height); return GSR_ERR_BAD_ARG;
-    }
-    // the sort kernels index pairs with 32-bit arithmetic, one 4096-pair tile past the last pair at most
-    if (max_pairs < 0 || max_pairs > GSR_MAX_PAIRS) { set_error("max_pairs = %lld out of range [0, %lld]", (long long)max_pairs, (long long)GSR_MAX_PAIRS); return GSR_ERR_BAD_ARG; }
+    const int rc = check_sizes(n, cam->width, cam->height, max_pairs);
+    if (rc) return rc;
     if (opts->tile_row_step < 0 || opts->tile_row_begin < 0 || opts->tile_row_begin >= std::max(opts->tile_row_step, 1)) {
         set_error("bad tile-row shard %d/%d", opts->tile_row_begin, opts->tile_row_step); return GSR_ERR_BAD_ARG;
     }
@@ -203,7 +213,9 @@ int gsr_camera_setup(const double qvec[4], const double tvec[3], double fx_full,
 
 int gsr_workspace_bytes(int64_t n, int32_t width, int32_t height, int64_t max_pairs, size_t *bytes)
 {
-    if (!bytes || n < 0 || width <= 0 || height <= 0 || max_pairs < 0) { set_error("bad argument"); return GSR_ERR_BAD_ARG; }
+    if (!bytes) { set_error("null bytes"); return GSR_ERR_BAD_ARG; }
+    const int rc = check_sizes(n, width, height, max_pairs);
+    if (rc) return rc;
     Workspace ws;
     *bytes = carve_workspace(nullptr, n, width, height, max_pairs, &ws);
     return GSR_OK;
