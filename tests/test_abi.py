@@ -130,3 +130,29 @@ def test_the_library_reads_no_environment_and_keeps_no_function_statics():
             text = re.sub(r"//.*", "", open(os.path.join(pkg, f)).read())
             assert "getenv" not in text, f
             assert not re.search(r"\bstatic\s+(const\s+)?(int|bool|float|unsigned|uint32_t)\s+\w+\s*=\s*\[", text), f
+
+
+def test_a_library_of_another_abi_version_is_refused(tmp_path):
+    """_lib._load() compares gsr_version() with GSR_VERSION (include/gsr.h) before it declares any entry point: a libgsr.so
+    built at another ABI (0.5.0: other parameter lists) must fail the import, not be called with shifted arguments."""
+    import subprocess
+    import sys
+
+    from gsr_amd import _lib
+
+    text = open(os.path.join(REPO, "include", "gsr.h")).read()
+    assert re.search(r"#define GSR_VERSION (\d+)", text).group(1) == str(_lib.GSR_VERSION)
+    src, stub = tmp_path / "stub.c", tmp_path / "libgsr_stub.so"
+    src.write_text("int gsr_version(void) { return 500; }\n")
+    subprocess.run(["gcc", "-shared", "-fPIC", "-o", str(stub), str(src)], check=True)
+    code = ("import gsr_amd\n"                                   # the package alone does not load the library
+            "try:\n"
+            "    from gsr_amd import _lib\n"
+            "except ImportError as e:\n"
+            "    print(e)\n"
+            "else:\n"
+            "    raise SystemExit('the 0.5.0 library was loaded')\n")
+    r = subprocess.run([sys.executable, "-c", code], cwd=REPO, env=dict(os.environ, GSR_LIB_PATH=str(stub)),
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "version 500" in r.stdout and "version 600" in r.stdout, r.stdout

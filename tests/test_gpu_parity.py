@@ -416,6 +416,56 @@ def test_pair_overflow_is_reported_and_recovered(G):
     assert small.max_pairs > 4096 and torch.equal(again, good)
 
 
+def test_a_reported_overflow_is_not_reported_again(G):
+    """Each slice of a workspace keeps its own overflow record.  A batch overflows in slice 2 and stats() reports it; a single
+    frame (slice 0), then a batch that fits (slices 0-2, chained behind the single frame) must read clean — slice 2's record was
+    reported already — and render the single-view frames bit for bit."""
+    from gsr_amd import _lib
+
+    cols, cam, _ = _medium(G, n=60_000)
+    W, H = cam.width, cam.height
+    fx = G.synthetic.pinhole_focal(W)
+    far = [G.renderer.make_camera(p.qvec, np.asarray(p.tvec) * 6.0, 2 * fx, 2 * fx, 2 * W, 2 * H, W, H)   # the scene small in the frame
+           for p in G.synthetic.ring_cameras(25)[::12]]
+    scene = G.renderer.GaussianScene.from_columns(cols)
+    ref = G.renderer.Rasterizer(scene)
+    singles, needs = [], []
+    for c in far + [cam]:
+        singles.append(ref.render(c))
+        needs.append(ref.last_stats["n_pairs_bbox"])
+    assert max(needs[:3]) < needs[3], needs                     # few pairs in the far views, many in `cam`
+    R = G.renderer.Rasterizer(scene, max_pairs=(max(needs[:3]) + needs[3]) // 2, views=3)
+    R.enqueue_batch([far[0], far[1], cam])                      # slice 2 overflows
+    with pytest.raises(_lib.GsrPairOverflow):
+        R.stats()
+    assert [st["overflow"] for st in R.last_slice_stats] == [0, 0, 1]
+    R.enqueue(far[2])                                           # slice 0
+    batch = R.enqueue_batch([far[1], far[2], far[0]])           # slices 0-2, chained behind the single frame
+    assert R.stats()["overflow"] == 0 and len(R.last_slice_stats) == 3
+    assert torch.equal(batch, torch.stack([singles[1], singles[2], singles[0]]))
+
+
+def test_stats_after_an_empty_shard_checks_the_frames_before_it(G):
+    """A shard that owns no tile row runs no kernel and its counters are zeros, but the frames enqueued before it are still
+    unchecked: stats() must read them and raise their overflow."""
+    from gsr_amd import _lib
+
+    cols, cam, _ = _medium(G, n=30_000, W=200, H=40)             # three tile rows: of 8 ranks, rank 5 owns none
+    scene = G.renderer.GaussianScene.from_columns(cols)
+    empty = G.renderer.make_options(tile_row_begin=5, tile_row_step=8, output_layout=2)
+    R = G.renderer.Rasterizer(scene, max_pairs=64)
+    R.enqueue(cam)                                               # overflows, unchecked
+    assert R.enqueue(cam, empty).numel() == 0
+    with pytest.raises(_lib.GsrPairOverflow):
+        R.stats()
+    assert R.last_stats["n_pairs_bbox"] > 64
+    assert not any(R.stats().values())                           # the empty shard's own counters
+    ok = G.renderer.Rasterizer(scene)                            # behind frames that fit: zeros, in every slice read
+    ok.enqueue(cam)
+    ok.enqueue(cam, empty)
+    assert not any(ok.stats().values()) and ok.last_slice_stats == [ok.last_stats]
+
+
 def test_saturation_early_out_is_exact(G):
     """The T == 0.0f rule (saturation_rule = 1; also what runs whenever the final T is requested): early_out_T = 0 stops a wave
     when all its pixels have T == 0.0f; a negative threshold never stops.  An opaque wall in front of a long list makes the
@@ -562,7 +612,7 @@ def test_launch_order_hint_changes_no_bit(G):
     R.render(small)
     assert torch.equal(R.render(cam), ref)                      # another frame size in between: the workspace is carved anew
     R._workspace(cam.width, cam.height).fill_(255)
-    R._chained = False
+    assert R.unchecked.slices == 0                              # no frame to chain onto: the next one clears the 0xFF control block
     assert torch.equal(R.render(cam), ref)                      # garbage where the hint lives
     assert all(R.last_stats[k] == st[k] for k in st if k != "colour_evals")
 

@@ -16,6 +16,7 @@ import torch  # noqa: F401
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GSR_LIB_PATH") or os.path.join(_HERE, "csrc", "libgsr.so")  # the override is for A/B tooling only
 
+GSR_VERSION = 600  # include/gsr.h: the ABI the declarations below are written for
 GSR_OK = 0
 GSR_ERR_BAD_ARG = -1
 GSR_ERR_WORKSPACE = -2
@@ -135,9 +136,11 @@ def _load() -> C.CDLL:
             "or make -C torch-gaussian-splatting-rasterizer_amd/csrc).  There is no CPU fallback."
         )
     L = C.CDLL(LIB_PATH)
+    L.gsr_version.restype = C.c_int
+    if L.gsr_version() != GSR_VERSION:  # another ABI: its entry points would be called with shifted arguments
+        raise ImportError(f"{LIB_PATH} is libgsr version {L.gsr_version()}, these bindings need version {GSR_VERSION}: rebuild it")
     vp, i64, i32, sz = C.c_void_p, C.c_int64, C.c_int32, C.c_size_t
     dp = C.POINTER(C.c_double)
-    L.gsr_version.restype = C.c_int
     L.gsr_last_error.restype = C.c_char_p
     L.gsr_default_options.argtypes = [C.POINTER(GsrOptions)]
     L.gsr_default_options.restype = None

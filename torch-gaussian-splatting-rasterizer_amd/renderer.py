@@ -112,7 +112,7 @@ class GaussianScene:
 
     def __init__(self, arrays: Mapping[str, torch.Tensor], sh_degree: int = 3, sh_half: bool = False):
         self.t: Dict[str, torch.Tensor] = {}
-        self.bounds: Optional[torch.Tensor] = None   # GsrScene.block_bounds (build_bounds): [ceil(n / 256), 8] or None
+        self.bounds: Optional[torch.Tensor] = None   # GsrScene.block_bounds (build_bounds): [ceil(n / GSR_BOUNDS_BLOCK), 8] or None
         self.order_t: Optional[torch.Tensor] = None  # device, int64: scene index -> file index (None: file order)
         self._order_np: Optional[np.ndarray] = None
         self.order_ms = 0.0                          # what building the order and gathering the arrays cost at upload
@@ -169,9 +169,10 @@ class GaussianScene:
         return dead
 
     def build_bounds(self) -> "GaussianScene":
-        """Camera-independent block bounds of the arrays AS THEY LIE NOW (gsr_scene_bounds: per 256 consecutive gaussians the box of
-        their means and their largest log-scale, 32 B per block): the preprocess then skips, unread, every block none of whose gaussians
-        can be drawn in a view — bit-identical frames.  Pays off in spatial order (~40 % of a view's blocks); harmless in file order."""
+        """Camera-independent block bounds of the arrays AS THEY LIE NOW (gsr_scene_bounds: per GSR_BOUNDS_BLOCK = 64 consecutive
+        gaussians the box of their means and their largest log-scale, 32 B per block): the preprocess then skips, unread, every block none
+        of whose gaussians can be drawn in a view — bit-identical frames.  Pays off in spatial order (31 % of the bench frame's blocks,
+        DESIGN.md §5.0); harmless in file order."""
         if self.n == 0:
             return self
         with torch.cuda.device(self.device):
@@ -260,6 +261,71 @@ def shard_rows(height: int, begin: int, step: int, block: int = 1) -> int:
     return len(shard_row_list(height, begin, step, block))
 
 
+class UncheckedFrames:
+    """Which slices of a Rasterizer's workspace hold frames that no stats() has read yet.  A call renders into slices 0 .. k-1
+    (enqueue: slice 0; enqueue_batch: one per view of a launch sequence), so these are always the first `slices`.  libgsr keeps an
+    overflow record per slice: a slice's first frame since the last stats() starts a new one, later frames add to it (keep_flags)."""
+
+    def __init__(self):
+        self.slices = 0      # slices 0 .. slices - 1 hold unchecked frames
+        self.empty = False   # the last enqueue was a shard without tile rows: no kernel ran, its counters are all zero
+
+    def to_reset(self, k: int) -> range:
+        """Slices a call into 0 .. k-1 resets first: when slice 0 holds unchecked frames the call keeps every slice's record, so
+        those of its slices that hold none start from an empty one (stats() leaves the record it read in the slice)."""
+        return range(self.slices, k) if self.slices else range(0)
+
+    def wrote(self, k: int) -> None:
+        """A call rendered into slices 0 .. k-1 (k = 0: an empty shard)."""
+        self.slices, self.empty = max(self.slices, k), k == 0
+
+    def read(self) -> int:
+        """stats() reads slices 0 .. read() - 1: the unchecked ones, else slice 0 once more (none after an empty shard); the record starts over."""
+        n = self.slices if self.empty else max(self.slices, 1)
+        self.slices = 0
+        return n
+
+
+def _render_checked(rasterizers, streams, opts: GsrOptions, attempt, slack_div: int, what: str):
+    """The retry loop of Rasterizer.render / render_batch and FramesInFlight.render_batch: `attempt(o)` enqueues the frames with
+    options `o`, then each rasterizer with anything to report runs stats() on its stream (None: the current one).  They share their
+    bounds: a frame over the pair bound grows all pair buffers to the worst need (+ 1 / slack_div); one short of depth-sort passes
+    re-runs with the learned bound, or with every pass once the need reported is no higher than what was enqueued.  The caller's own
+    depth_sort_passes is re-raised; after MAX_RETRIES re-renders so is the last attempt's status (pair overflow before sort passes)."""
+    r0, unbounded = rasterizers[0], False
+    for _ in range(MAX_RETRIES + 1):
+        for r in rasterizers:  # a depth-sort bound one of them has learned holds for all
+            r.sort_passes = max(q.sort_passes for q in rasterizers)
+        o = opts if unbounded else r0.bounded(opts)
+        frames = attempt(o)
+        failed = []
+        for r, s in zip(rasterizers, streams):
+            if r.unchecked.slices or r.unchecked.empty:
+                with torch.cuda.stream(s):
+                    try:
+                        r.stats()
+                    except (_lib.GsrPairOverflow, _lib.GsrSortPasses) as e:
+                        failed.append((e, r.last_stats))
+        if not failed:
+            return frames
+        short = [e for e, _ in failed if isinstance(e, _lib.GsrSortPasses)]
+        if short and opts.depth_sort_passes != 0:
+            raise short[0]  # the caller's own bound
+        need = max([st["n_pairs_bbox"] for e, st in failed if isinstance(e, _lib.GsrPairOverflow)], default=0)
+        if need >= _lib.GSR_MAX_PAIRS:
+            raise _lib.GsrError(_lib.GSR_ERR_PAIR_OVERFLOW, f"a frame needs {need} pairs, more than libgsr can index")
+        if need:
+            grown = int(min(_lib.GSR_MAX_PAIRS, need + need // slack_div + 1024))
+            if grown <= r0.max_pairs:
+                raise _lib.GsrError(_lib.GSR_ERR_PAIR_OVERFLOW, f"pair overflow persists at max_pairs = {r0.max_pairs} (need {need})")
+            for r in rasterizers:
+                r.max_pairs = grown
+        if short:  # stats() has raised the learned bound to the need
+            unbounded = o.depth_sort_passes >= max(r.sort_passes for r in rasterizers)
+    e, st = max(failed, key=lambda f: isinstance(f[0], _lib.GsrPairOverflow))
+    raise type(e)(e.code, f"{what} still incomplete after {MAX_RETRIES} re-renders: {st}")
+
+
 class Rasterizer:
     """Owns the scratch workspace for one scene and renders frames of it.
 
@@ -276,11 +342,9 @@ class Rasterizer:
         # are read): passed as GsrOptions.depth_sort_passes so that the passes a frame does not need are not even enqueued
         self.sort_passes = 0
         self._ws: Optional[torch.Tensor] = None
-        self._last_empty = False   # the last enqueue was a shard without tile rows: no kernel ran, its counters are all zero
-        self._chained = False      # frames have been enqueued since the last stats(): the next one keeps their overflow record
-        self._used = 1             # slices that hold unchecked frames (stats() reads them all)
         self._ws_key = None
         self._slice = 0            # bytes per slice of the workspace
+        self.unchecked = UncheckedFrames()
         self.last_stats: Optional[Dict[str, int]] = None
         self.last_slice_stats: list = []   # stats() per slice: the last view each slice rendered
 
@@ -292,15 +356,21 @@ class Rasterizer:
             self._ws = None  # free the old one first
             self._ws = torch.empty(nbytes * self.views, dtype=torch.uint8, device=self.scene.device)
             assert self._ws.data_ptr() % 256 == 0 and nbytes % 256 == 0
-            # libgsr needs no initialisation (every frame clears its control block); the head of every slice is zeroed so that a
-            # gsr_read_stats BEFORE any frame has run there reads zeros rather than whatever the allocator left, and so that a
-            # batch chained behind unchecked single frames (keep_flags) finds an empty record in the slices they never used
-            for v in range(self.views):
-                self._ws[v * nbytes: v * nbytes + min(4096, nbytes)].zero_()
             self._ws_key, self._slice = key, nbytes
-            self._chained = self._last_empty = False
-            self._used = 1
+            self.unchecked = UncheckedFrames()
+            self._reset_slices(range(self.views))
         return self._ws
+
+    def _reset_slices(self, slices: range) -> None:
+        """Zero the head of these slices (libgsr needs no initialisation): an empty overflow record for a frame rendered with keep_flags,
+        and zeros for a gsr_read_stats before any frame has run there rather than whatever the allocator left."""
+        for v in slices:
+            self._ws[v * self._slice: v * self._slice + min(4096, self._slice)].zero_()
+
+    def _views_per_launch(self, opts: GsrOptions, n_cams: int) -> int:
+        """Views per launch sequence of gsr_render_batch, view j in slice j: api.hip views_per_launch for this workspace."""
+        k = min(self.views, opts.batch_views) if opts.batch_views > 0 else self.views
+        return min(k, max(n_cams, 1))
 
     def _out_shape(self, cam: GsrCamera, opts: GsrOptions):
         if opts.output_layout == 0:
@@ -338,92 +408,51 @@ class Rasterizer:
         elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or not out.is_cuda:
             raise ValueError(f"out must be a contiguous {dtype} CUDA tensor of shape {shape}")
         if out.numel() == 0:  # a shard that owns no tile row (more ranks than tile rows): nothing to render
-            self._last_empty = True
+            self.unchecked.wrote(0)
             return out
-        if self._chained and not opts.keep_flags:
+        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
             opts = GsrOptions.from_buffer_copy(opts)
             opts.keep_flags = 1
         sc = self.scene.c_struct()
         tptr = final_T.data_ptr() if final_T is not None else None
         check(lib.gsr_render_forward(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(),
                                      out.data_ptr(), tptr, _stream_ptr(self.scene.device)))
-        self._chained, self._last_empty = True, False
+        self.unchecked.wrote(1)
         return out
 
     def stats(self) -> Dict[str, int]:
-        """Counters of the last enqueued frame (synchronises the stream); its overflow record covers every frame since the
-        previous stats().  Raises GsrPairOverflow / GsrSortPasses when one of them exceeded a bound."""
-        if self._ws is None or self._last_empty:  # no workspace yet / an empty shard: no kernel ran, nothing to read
-            self.last_stats = {k: 0 for k, _ in GsrStats._fields_ if not k.startswith("_")}
-            self.last_slice_stats = [self.last_stats]
-            return self.last_stats
-        # every slice that holds unchecked frames (one, unless batches ran): the last view each rendered, its record sticky over all of them
+        """Counters of the last enqueued frame (synchronises the stream; zeros for a shard without tile rows).  Reads every slice
+        that holds frames enqueued since the previous stats() and raises GsrPairOverflow / GsrSortPasses if one exceeded a bound:
+        then, also after an empty shard, last_stats holds the worst slice's figures and last_slice_stats every slice read."""
         per, worst_rc = [], 0
-        for v in range(self._used):
+        for v in range(self.unchecked.read() if self._ws is not None else 0):
             st = GsrStats()
             rc = lib.gsr_read_stats(self._ws.data_ptr() + v * self._slice, self._slice, C.byref(st), _stream_ptr(self.scene.device))
             per.append(st.as_dict())
             self.sort_passes = max(self.sort_passes, int(st.sort_passes))  # also when a frame was short of passes: the retry has them
             if rc == _lib.GSR_ERR_PAIR_OVERFLOW or (rc != 0 and worst_rc != _lib.GSR_ERR_PAIR_OVERFLOW):
                 worst_rc = rc
-        self._chained, self._used = False, 1  # the next frame starts from a cleared control block
-        self.last_slice_stats = per
-        self.last_stats = dict(per[0])
+        zeros = not per or (self.unchecked.empty and not worst_rc)  # nothing read, or an empty shard behind frames that were fine
+        self.last_slice_stats = [{k: 0 for k, _ in GsrStats._fields_ if not k.startswith("_")}] if zeros else per
+        self.last_stats = dict(self.last_slice_stats[0])
         if worst_rc:  # what a re-render needs: the worst slice's figures
-            self.last_stats["n_pairs_bbox"] = max(d["n_pairs_bbox"] for d in per)
-            self.last_stats["sort_passes"] = max(d["sort_passes"] for d in per)
-            self.last_stats["overflow"] = 0
+            self.last_stats = dict(per[0], n_pairs_bbox=max(d["n_pairs_bbox"] for d in per), sort_passes=max(d["sort_passes"] for d in per))
             for d in per:
                 self.last_stats["overflow"] |= d["overflow"]
         check(worst_rc)
         return self.last_stats
 
-    @staticmethod
-    def _incomplete(what: str, stats) -> "_lib.GsrError":
-        """The error of a frame that is still over a bound after every retry: the status the LAST attempt reported
-        (pair overflow before sort passes), never GSR_ERR_BAD_ARG — no argument was bad."""
-        ov = int((stats or {}).get("overflow", 0))
-        if ov & 1 or not ov & 2:
-            return _lib.GsrPairOverflow(_lib.GSR_ERR_PAIR_OVERFLOW, f"{what}: {stats}")
-        return _lib.GsrSortPasses(_lib.GSR_ERR_SORT_PASSES, f"{what}: {stats}")
-
-    def _grow_pairs(self, slack_div: int) -> None:
-        """After GsrPairOverflow: room for what the worst frame needed, or give up when that cannot be had."""
-        need = int(self.last_stats["n_pairs_bbox"])
-        if need >= _lib.GSR_MAX_PAIRS:
-            raise _lib.GsrError(_lib.GSR_ERR_PAIR_OVERFLOW, f"the frame needs {need} pairs, more than libgsr can index")
-        grown = int(min(_lib.GSR_MAX_PAIRS, need + need // slack_div + 1024))
-        if grown <= self.max_pairs:
-            raise _lib.GsrError(_lib.GSR_ERR_PAIR_OVERFLOW, f"pair overflow persists at max_pairs = {self.max_pairs} (need {need})")
-        self.max_pairs = grown
-
     def render(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None,
                return_T: bool = False):
         """Render one frame and verify it is complete: grows the pair buffer / raises the learned depth-sort bound and
-        re-renders when the frame exceeded one (at most MAX_RETRIES times)."""
-        opts = opts or make_options()
-        unbounded, tried = False, -1
-        for _ in range(MAX_RETRIES + 1):
-            final_T = None
-            if return_T:
-                _, tshape = self._out_shape(cam, opts)
-                final_T = torch.ones(tshape, dtype=torch.float32, device=self.scene.device)
-            # (frames enqueued before this one and not yet checked share its overflow record: if one of THEM exceeded a bound,
-            # this frame is re-rendered once with room for it — nothing is hidden and nothing is wrong)
-            img = self.enqueue(cam, opts if unbounded else self.bounded(opts), out, final_T)
-            try:
-                self.stats()
-            except _lib.GsrPairOverflow:
-                self._grow_pairs(8)
-                continue
-            except _lib.GsrSortPasses:
-                if opts.depth_sort_passes != 0:
-                    raise  # the caller's own bound
-                unbounded = self.sort_passes <= tried  # stats() raises the learned bound; if it did not grow, enqueue every pass
-                tried = self.sort_passes
-                continue
+        re-renders when the frame exceeded one (_render_checked).  Frames enqueued before this one and not yet checked share
+        its overflow record: if one of THEM exceeded a bound, this frame is re-rendered once with room for it."""
+        def attempt(o):
+            final_T = torch.ones(self._out_shape(cam, o)[1], dtype=torch.float32, device=self.scene.device) if return_T else None
+            img = self.enqueue(cam, o, out, final_T)
             return (img, final_T) if return_T else img
-        raise self._incomplete(f"frame still incomplete after {MAX_RETRIES} re-renders", self.last_stats)
+
+        return _render_checked([self], [None], opts or make_options(), attempt, 8, "frame")
 
     def _batch_out(self, cams, opts: GsrOptions, out: Optional[torch.Tensor]):
         """(out, frame_stride in elements) of a batch: whole frames [B,H,W,3], or with a tile-row shard (output_layout = 2) the
@@ -451,41 +480,32 @@ class Rasterizer:
             raise ValueError("a batch needs at least one view")
         out, stride = self._batch_out(cams, opts, out)
         if out.numel() == 0:  # a shard that owns no tile row
-            self._last_empty = True
+            self.unchecked.wrote(0)
             return out
         arr = (GsrCamera * len(cams))(*cams)
         ws = self._workspace(cams[0].width, cams[0].height)
+        k = self._views_per_launch(opts, len(cams))
+        # a slice's first view starts a new record (libgsr chains the later ones) unless slice 0 holds unchecked frames: then all keep theirs
+        self._reset_slices(self.unchecked.to_reset(k))
         o = GsrOptions.from_buffer_copy(opts)
-        # a slice's first view clears its record (libgsr chains its later views) — unless frames enqueued before are still unchecked
-        o.keep_flags = 1 if (self._chained or opts.keep_flags) else 0
+        o.keep_flags = 1 if (self.unchecked.slices or opts.keep_flags) else 0
         sc = self.scene.c_struct()
         check(lib.gsr_render_batch(C.byref(sc), arr, len(cams), C.byref(o), self.max_pairs, ws.data_ptr(), ws.numel(),
                                    out.data_ptr(), stride, _stream_ptr(self.scene.device)))
-        per_launch = self.views if o.batch_views == 0 else min(self.views, o.batch_views)
-        self._used = max(self._used, min(per_launch, len(cams)))
-        self._chained, self._last_empty = True, False
+        self.unchecked.wrote(k)
         return out
 
     def render_batch(self, cams, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Several views of the resident scene in one call: [B,H,W,3] (a tile-row shard: [B,rows*16,W,3]), `views` of them per launch
         sequence.  Pair buffers and the depth-sort bound are sized on the fly: a view that exceeds one makes the batch re-run with
-        room for the worst view (at most MAX_RETRIES times)."""
-        opts = opts or make_options()
+        room for the worst view (_render_checked)."""
         cams = list(cams)
-        unbounded = False
-        for _ in range(MAX_RETRIES + 1):
-            o = opts if unbounded else self.bounded(opts)
+        def attempt(o):
+            nonlocal out
             out = self.enqueue_batch(cams, o, out)
-            try:
-                self.stats()
-                return out
-            except _lib.GsrPairOverflow:
-                self._grow_pairs(4)
-            except _lib.GsrSortPasses:
-                if opts.depth_sort_passes != 0:
-                    raise
-                unbounded = o.depth_sort_passes >= self.sort_passes  # the reported need did not exceed what was enqueued: play safe
-        raise self._incomplete(f"batch still incomplete after {MAX_RETRIES} re-renders", self.last_stats)
+            return out
+
+        return _render_checked([self], [None], opts or make_options(), attempt, 4, "batch")
 
     def fit_pairs(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, slack: float = 1.25) -> int:
         """Size the pair buffers to this view: one probing frame, then max_pairs = slack * D (+ margin).
@@ -580,9 +600,9 @@ class FramesInFlight:
 
     def render_batch(self, cams, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Rasterizer.render_batch with the views spread round robin over the slots (gsr_render_batch_slots; with `views` > 1 each
-        slot takes `views` consecutive cameras per launch sequence): [B,H,W,3],
-        bit-identical to the single-stream batch.  The current stream waits for every slot before this returns; a view that
-        overflows the pair buffers makes the batch re-run with room for it."""
+        slot takes `views` consecutive cameras per launch sequence): [B,H,W,3], bit-identical to the single-stream batch.  The
+        current stream waits for every slot before this returns; a view that exceeds a bound makes the batch re-run with room for
+        it (_render_checked).  Frames submit()ted and not yet checked are checked first: their errors are raised."""
         opts = opts or make_options()
         if opts.output_layout != 0 or opts.tile_row_step > 1:
             raise ValueError("render_batch renders whole [H,W,3] frames")
@@ -601,49 +621,28 @@ class FramesInFlight:
         n = len(self.rasterizers)
         cur = torch.cuda.current_stream(dev)
         r0 = self.rasterizers[0]
-        unbounded = False
-        for _ in range(MAX_RETRIES + 1):
+
+        def attempt(o):
             wss = [r._workspace(W, H) for r in self.rasterizers]  # all of one size: the slots share max_pairs
-            for st in self.streams:
-                st.wait_stream(cur)  # `out` (and the workspaces) may have been allocated / used on the current stream
+            for k, r in enumerate(self.rasterizers):
+                self.streams[k].wait_stream(cur)  # `out` (and the workspaces) may have been allocated / used on the current stream
+                if r.unchecked.slices:  # frames submit()ted and not yet checked: read (and report) their record before the batch clears it
+                    self.stats(k)
+            o = GsrOptions.from_buffer_copy(o)
+            o.keep_flags = 0  # a slot's first view clears its record, libgsr chains the slot's later views
             ws_arr = (C.c_void_p * n)(*[w.data_ptr() for w in wss])
             st_arr = (C.c_void_p * n)(*[int(st.cuda_stream) for st in self.streams])
-            self.set_sort_passes(max(r.sort_passes for r in self.rasterizers))
-            o = GsrOptions.from_buffer_copy(opts if unbounded else r0.bounded(opts))
-            for k in range(n):  # frames submit()ted and not yet checked: read (and report) their record before the batch clears it
-                if self.rasterizers[k]._chained:
-                    self.stats(k)
-            o.keep_flags = 0  # a slot's first view clears its record, libgsr chains the slot's later views
             check(lib.gsr_render_batch_slots(C.byref(sc), arr, len(cams), C.byref(o), r0.max_pairs, ws_arr, wss[0].numel(), st_arr, n,
                                              out.data_ptr(), H * W * 3))
-            per_launch = min(r0.views if o.batch_views == 0 else min(r0.views, o.batch_views), len(cams))
-            groups = (len(cams) + per_launch - 1) // per_launch
-            used = min(n, groups)
-            sizes = [min(per_launch, len(cams) - g * per_launch) for g in range(groups)]
-            for k, r in enumerate(self.rasterizers[:used]):
-                r._chained, r._last_empty, r._used = True, False, max(sizes[k::n])  # slices its groups rendered into
-            need, short = 0, False
-            for k in range(used):
-                try:
-                    self.stats(k)
-                except _lib.GsrPairOverflow:
-                    need = max(need, int(self.rasterizers[k].last_stats["n_pairs_bbox"]))
-                except _lib.GsrSortPasses:
-                    if opts.depth_sort_passes != 0:
-                        raise
-                    short = True  # stats() has raised that slot's learned bound; the re-run shares it
-            for k in range(n):
-                self.wait(k)
-            if need == 0 and not short:
-                return out
-            if need:
-                if need >= _lib.GSR_MAX_PAIRS:
-                    raise _lib.GsrError(_lib.GSR_ERR_PAIR_OVERFLOW, f"a view needs {need} pairs, more than libgsr can index")
-                self.set_max_pairs(int(min(_lib.GSR_MAX_PAIRS, need + need // 4 + 1024)))
-            if short:
-                unbounded = o.depth_sort_passes >= max(r.sort_passes for r in self.rasterizers)  # the need did not grow: play safe
-        raise Rasterizer._incomplete(f"batch still incomplete after {MAX_RETRIES} re-renders",
-                                     max((r.last_stats or {} for r in self.rasterizers), key=lambda d: d.get("overflow", 0)))
+            k = r0._views_per_launch(o, len(cams))
+            sizes = [min(k, len(cams) - i) for i in range(0, len(cams), k)]  # launch sequence g renders on slot g % n
+            for s, r in enumerate(self.rasterizers[:len(sizes)]):
+                r.unchecked.wrote(max(sizes[s::n]))  # the slices its launch sequences rendered into
+            for s in range(n):
+                self.wait(s)
+            return out
+
+        return _render_checked(self.rasterizers, self.streams, opts, attempt, 4, "batch")
 
     def wait(self, slot: int) -> None:
         torch.cuda.current_stream(self.scene.device).wait_stream(self.streams[slot])
