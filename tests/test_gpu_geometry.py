@@ -1,7 +1,7 @@
 """GPU: frames at and past the geometry limits where binning and the pair sort change kernels.
 
-The binning / pair-sort stage picks its kernels from the frame's tile grid (gsr_internal.h rect_fits_8bit, coarse_capable,
-pair_keys_16bit; binning.hip tile_keying, tile_lists, launch_binning):
+The binning / pair-sort stage picks its kernels from the frame's tile grid (api.hip plan_frame fills gsr_internal.h FramePlan;
+launch_binning, launch_pair_sort and launch_blend read it):
   - the tile rect rides through the depth sort packed as 4 x u8 while tiles_x, tiles_y <= 256, and is gathered by id past that;
   - with the packed rect, pairs are (gaussian, 32x32 cell) pairs (coarse binning), otherwise (gaussian, 16x16 tile) pairs;
   - pair keys are (row << bits_x) | column with one spare row value for culled pairs: 2 bytes while bits_x + bits_y <= 16,
@@ -36,16 +36,16 @@ def _path(W, H, fine_binning=False):
     """The kernel choice of the binning and pair-sort stage for a W x H frame, restated from the C++ (ordinary scene sizes:
     n <= 2^28)."""
     tiles_x, tiles_y = -(-W // TILE), -(-H // TILE)
-    packed = tiles_x <= 256 and tiles_y <= 256               # gsr_internal.h rect_fits_8bit
-    coarse = packed and not fine_binning                     # coarse_capable (+ n <= 2^28) and tile_keying: opts.fine_binning == 0
-    grid_x = (tiles_x + 1) // 2 if coarse else tiles_x       # binning.hip tile_keying: 32x32 cells or 16x16 tiles
+    packed = tiles_x <= 256 and tiles_y <= 256               # FramePlan.packed_rect
+    coarse = packed and not fine_binning                     # FramePlan.coarse (+ n <= 2^28): opts.fine_binning == 0
+    grid_x = (tiles_x + 1) // 2 if coarse else tiles_x       # FramePlan.grid_x / grid_y: 32x32 cells or 16x16 tiles
     grid_y = (tiles_y + 1) // 2 if coarse else tiles_y
     bits_x = max(1, _ceil_log2(grid_x))
     bits_y = max(1, _ceil_log2(grid_y + 1))                  # one spare row value marks culled pairs (drop_from = grid_y << bits_x)
     key_bits = bits_x + bits_y
     return dict(packed=packed, coarse=coarse, bits_x=bits_x, bits_y=bits_y, key_bits=key_bits,
-                key16=key_bits <= 16,                        # gsr_internal.h pair_keys_16bit
-                pair_passes=(key_bits + 7) // 8,             # launch_pair_sort: 8-bit digits; tile_lists() reads pval[passes & 1]
+                key16=key_bits <= 16,                        # FramePlan.key16
+                pair_passes=(key_bits + 7) // 8,             # FramePlan.pair_passes: 8-bit digits; the lists end in pval[lists_buf = passes & 1]
                 drop_from=grid_y << bits_x, tiles_x=tiles_x, tiles_y=tiles_y, n_tiles=tiles_x * tiles_y)
 
 

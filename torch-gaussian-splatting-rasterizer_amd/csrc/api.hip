@@ -119,6 +119,80 @@ static int check_frame(int64_t n, const GsrCamera *cam, const GsrOptions *opts, 
     return GSR_OK;
 }
 
+static int ceil_log2(int v)
+{
+    int bits = 0;
+    while ((1 << bits) < v) ++bits;
+    return bits;
+}
+
+// two quadrants per wave from this many tiles per launch on (measured: 4080 tiles better with two, 2040 with one); below, one quadrant per wave (see blend_walk_kernel)
+#ifndef GSR_BLEND_HALF_MIN_TILES
+#define GSR_BLEND_HALF_MIN_TILES 3000
+#endif
+constexpr int BLEND_HALF_MIN_TILES = GSR_BLEND_HALF_MIN_TILES;  // (the macro: tools/ A/B builds)
+// the pipelined one-quadrant walk (96 VGPRs: 5 waves per SIMD = 1280 four-wave workgroups resident) up to this many tiles per launch;
+// GsrOptions.blend_pipe_tiles overrides it (experiments and tests: -1 switches the variant off)
+constexpr int BLEND_PIPE_MAX_TILES = 1280;
+
+FramePlan plan_frame(const Workspace &ws, const GsrOptions &opts)
+{
+    FramePlan p;
+    // ---- stage 1.  The tile rect packs into 32 bits when the tile grid fits 8 bits per coordinate (frames up to 4096 px): the
+    // preprocess writes that form, the depth sort carries it as a second payload and binning reads it in depth order
+    p.packed_rect = ws.tiles_x <= 256 && ws.tiles_y <= 256;
+    p.rs = row_shard_of(opts);
+    // A multi-GPU shard's preprocess (preprocess.hip) hands the depth sort a compact list of (key, id, rect) records of the rank's
+    // visible gaussians instead of one key per gaussian.  Progressive frames (draw_limit) rank ALL gaussians the reference
+    // draws, so they take the whole-frame path.
+    if (opts.tile_row_step <= 1 || opts.draw_limit != 0) p.compact_input = false;
+    else if (opts.shard_preprocess != 0) p.compact_input = opts.shard_preprocess == 2;  // A/B: 1 = whole-frame kernel, 2 = three-phase kernel
+    else p.compact_input = opts.tile_row_step >= 5;  // measured: 2 and 4 shards are as fast or faster through the whole-frame kernel
+    // progressive frames rank every gaussian the reference draws, whatever rows it touches: no row test then
+    p.cull_rs = opts.draw_limit > 0 ? RowShard{0, 1, 0} : p.rs;
+    // ---- depth sort: four passes cover any depth range; a shard's compact records are few (its visible gaussians): smaller
+    // tiles, more workgroups, shorter serial chains
+    p.depth_passes = opts.depth_sort_passes >= 1 && opts.depth_sort_passes <= 4 ? opts.depth_sort_passes : 4;
+    p.depth_items = p.compact_input ? DEPTH_SORT_ITEMS_SHARD : DEPTH_SORT_ITEMS;
+    // ---- binning.  Coarse (per 32x32 cell) when the packed rect exists and the gaussian ids leave four bits of the pair value for
+    // the tile mask.  GsrOptions.fine_binning = 1 forces the fine path (A/B timing, and the test that both build the same frame).
+    p.coarse = p.packed_rect && ws.n <= ((int64_t)1 << COARSE_ID_BITS) && opts.fine_binning == 0;
+    p.grid_x = p.coarse ? ws.ctiles_x : ws.tiles_x;
+    p.grid_y = p.coarse ? ws.ctiles_y : ws.tiles_y;
+    p.bits_x = std::max(1, ceil_log2(p.grid_x));
+    p.bits_y = std::max(1, ceil_log2(p.grid_y + 1));  // one spare row value marks culled pairs
+    p.drop_from = (uint32_t)p.grid_y << p.bits_x;
+    // cells of a shard: pairs of rows (tile_row_block = 2) ARE cell rows — the rank owns cell rows begin + k step whole; with single rows
+    // and an even step the rank's tile rows begin + k step fall into the cell rows (begin >> 1) + k (step >> 1), each holding exactly one
+    // of them; with an odd step (or none) every cell row can hold one.  The expansion keeps only this rank's tiles either way.
+    p.csh = p.rs.step <= 1 ? RowShard{0, 1, 0}
+          : p.rs.bshift == 1 ? RowShard{p.rs.begin, p.rs.step, 0}
+          : p.rs.step % 2 == 0 ? RowShard{p.rs.begin >> 1, p.rs.step >> 1, 0} : RowShard{0, 1, 0};
+    // ---- pair sort.  Keys are uint16_t in memory when every key (the culled row included) fits: 6 B per pair instead of 8
+    // through emit, the sort passes and the range scan, all of them bound by HBM.  8 bits or fewer per pass, the bits split evenly
+    // (13 tile-id bits sort as 7 + 6, not 8 + 5: with 128 digit values a workgroup's runs in the first, far-scattering pass are 32
+    // entries = one full 128-B line per array instead of half a line).  Every pass moves the pairs to the other buffer, from 0.
+    const int key_bits = p.bits_x + p.bits_y;
+    p.key16 = key_bits <= 16;
+    p.pair_passes = (key_bits + 7) / 8;
+    p.pair_bits_pp = (key_bits + p.pair_passes - 1) / p.pair_passes;
+    p.lists_buf = ws.n <= 0 || ws.max_pairs <= 0 ? 0 : p.pair_passes & 1;  // (nothing emitted or sorted: launch_binning)
+    // ---- blend.  Coarse binning hands it the sorted CELL lists (values = gaussian id | tile mask << 28) and cranges[]; the blend of
+    // a tile keeps the entries with its bit while it stages (blend.hip).  Round 2 expanded them into per-tile lists first
+    // (pair_expand_kernel: 34 us, 122 MB of traffic, 16 B of workspace per pair slot); A/B in one process on the bench frame: bin +
+    // sort 0.375 -> 0.341 ms, blend 0.553 -> 0.565 ms, frames and counters identical.
+    p.cell_lists = p.coarse;
+    p.rows = p.rs.rows_before(ws.tiles_y);
+    // which walk: by the tiles of the whole launch (all views: what fills the machine)
+    const int launch_tiles = p.rows * ws.tiles_x * ws.views;
+    const int pipe_max_tiles = opts.blend_pipe_tiles == 0 ? BLEND_PIPE_MAX_TILES : opts.blend_pipe_tiles;
+    p.blend = opts.accum_dtype == 1 ? BlendKernel::TileBf16
+            : opts.blend_impl == 1 ? BlendKernel::Tile
+            : launch_tiles >= BLEND_HALF_MIN_TILES ? BlendKernel::Walk2
+            : launch_tiles <= pipe_max_tiles ? BlendKernel::Walk1Pipe : BlendKernel::Walk1;
+    return p;
+}
+
 }  // namespace gsr
 
 using namespace gsr;
@@ -254,16 +328,16 @@ int gsr_preprocess(const GsrScene *scene, const GsrCamera *cam, const GsrOptions
     // so size-check against the smallest one.
     rc = check_frame(scene->n, cam, opts, 0, workspace, workspace_bytes, &ws);
     if (rc) return rc;
-    return launch_preprocess(*scene, cam, *opts, ws, debug, reset_words_of(opts, false), static_cast<hipStream_t>(stream));
+    return launch_preprocess(*scene, cam, *opts, ws, plan_frame(ws, *opts), debug, reset_words_of(opts, false), static_cast<hipStream_t>(stream));
 }
 
 // depth order: pass 0 drops culled gaussians and leaves V in ctrl; 3 passes on ordinary scenes (sort.hip); then pairs in depth
 // order, stably sorted by tile -> per-tile lists and their ranges; E in ctrl
-static int bin_sort_impl(const GsrOptions *opts, const Workspace &ws, hipStream_t s)
+static int bin_sort_impl(const GsrOptions *opts, const Workspace &ws, const FramePlan &plan, hipStream_t s)
 {
-    const int rc = launch_depth_sort(ws, rect_fits_8bit(ws), shard_compact(*opts), opts->depth_sort_passes, s);
+    const int rc = launch_depth_sort(ws, plan, s);
     if (rc) return rc;
-    return launch_binning(*opts, ws, s);
+    return launch_binning(*opts, ws, plan, s);
 }
 
 int gsr_bin_sort(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
@@ -272,7 +346,7 @@ int gsr_bin_sort(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_
     Workspace ws;
     int rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
     if (rc) return rc;
-    return bin_sort_impl(opts, ws, static_cast<hipStream_t>(stream));
+    return bin_sort_impl(opts, ws, plan_frame(ws, *opts), static_cast<hipStream_t>(stream));
 }
 
 int gsr_blend(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
@@ -287,7 +361,7 @@ int gsr_blend(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrO
     Workspace ws;
     int rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
     if (rc) return rc;
-    return launch_blend(*cam, *opts, ws, tile_lists(ws, *opts), out_image, 0, out_final_T, scene, static_cast<hipStream_t>(stream));
+    return launch_blend(*cam, *opts, ws, plan_frame(ws, *opts), out_image, 0, out_final_T, scene, static_cast<hipStream_t>(stream));
 }
 
 // Stages 1-3 for `views` cameras through ONE launch sequence: view v works in slice v of the workspace (slices of
@@ -311,13 +385,14 @@ static int render_views(const GsrScene *scene, const GsrCamera *cams, int views,
         ws.views = views;
         ws.view_stride = ws.bytes;
     }
+    const FramePlan plan = plan_frame(ws, *opts);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_preprocess(*scene, cams, *opts, ws, nullptr, reset_words_of(opts, keep_batch_words), s);
+    rc = launch_preprocess(*scene, cams, *opts, ws, plan, nullptr, reset_words_of(opts, keep_batch_words), s);
     if (rc) return rc;
-    rc = bin_sort_impl(opts, ws, s);
+    rc = bin_sort_impl(opts, ws, plan, s);
     if (rc) return rc;
     // (the blend finds the scene through what the preprocess above left in each view's control block: same call, same arrays)
-    return launch_blend(cams[0], *opts, ws, tile_lists(ws, *opts), out_images, out_view_stride, out_final_T, nullptr, s);
+    return launch_blend(cams[0], *opts, ws, plan, out_images, out_view_stride, out_final_T, nullptr, s);
 }
 
 int gsr_render_forward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs,
@@ -462,7 +537,9 @@ int gsr_block_visibility(const GsrScene *scene, const GsrCamera *cam, const GsrO
     if (rc) return rc;
     if (!cam || !opts || !scene->block_bounds || (scene->n > 0 && !dead_out)) { set_error("null camera / options / block_bounds / output"); return GSR_ERR_BAD_ARG; }
     if (cam->width <= 0 || cam->height <= 0) { set_error("bad frame size %dx%d", cam->width, cam->height); return GSR_ERR_BAD_ARG; }
-    return launch_block_visibility(*scene, *cam, *opts, dead_out, static_cast<hipStream_t>(stream));
+    Workspace ws;  // nothing to carve: the plan reads the frame's tile grid from it
+    carve_workspace(nullptr, scene->n, cam->width, cam->height, 0, &ws);
+    return launch_block_visibility(*scene, *cam, plan_frame(ws, *opts), dead_out, static_cast<hipStream_t>(stream));
 }
 
 int gsr_sh_to_rgb(int64_t n, const float *means, const float *sh, const float cam_center[3], int32_t degree, float *rgb_out,

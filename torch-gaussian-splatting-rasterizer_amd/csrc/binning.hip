@@ -61,8 +61,6 @@ __device__ __forceinline__ ushort4 unpack_rect8(uint32_t r)
                         (unsigned short)((r >> 24) + 1u));
 }
 
-constexpr int COARSE_ID_BITS = 28;  // coarse pairs: value = gaussian id | (mask of the cell's tiles the gaussian reaches) << 28
-
 // tile rect -> rect of the 32x32 cells (2x2 tiles) it touches; an empty rect stays empty
 __device__ __forceinline__ ushort4 coarse_rect(ushort4 rc)
 {
@@ -221,7 +219,7 @@ __global__ __launch_bounds__(1024) void pair_scan_kernel(uint32_t *__restrict__ 
 // (Round 4 measured the obvious refinement — gaussians of up to four cells, most of them, write their own pairs without search or
 // division, only the larger rects are load-balanced: 46.6 us either way.  The kernel is 13 K workgroups of a ~7-us dependent
 // chain each — counters, ids and rects, scan, stores — eight to a CU: six rounds of latency, not search or store throughput.)
-template <bool PACKED, bool COARSE, typename KeyT>  // KeyT: uint16_t when the keys fit (pair_keys_16bit), else uint32_t
+template <bool PACKED, bool COARSE, typename KeyT>  // KeyT: uint16_t when the keys fit (FramePlan.key16), else uint32_t
 __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t *__restrict__ id_a, const uint32_t *__restrict__ id_b,
                                                                  const uint32_t *__restrict__ r8_a, const uint32_t *__restrict__ r8_b,
                                                                  const FrameCtrl *ctrl, const ushort4 *__restrict__ rect, RowShard sh,
@@ -268,7 +266,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
     float4 q0v = make_float4(0.f, 0.f, 0.f, 0.f), q1v = q0v;
     if (test) { q0v = rec[g].q0; q1v = rec[g].q1; }
     uint32_t total;
-    s_off[tid] = block_excl_scan_256(cnt, scratch, &total);
+    s_off[tid] = block_excl_scan<256>(cnt, scratch, &total);
     if (test) { s_q0[tid] = q0v; s_q1[tid] = q1v; }
     s_id[tid] = g;
     s_geo[tid] = (uint32_t)rc.x | ((uint32_t)(rc.z - rc.x) << 16);
@@ -324,7 +322,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
         // carries the partial.
         __syncthreads();
         uint32_t tot;
-        block_excl_scan_256(entries, scratch, &tot);
+        block_excl_scan<256>(entries, scratch, &tot);
         if (tid == 0) blk_entries[blk] = tot;
     }
     __syncthreads();  // the block's lists in LDS are done with
@@ -368,42 +366,7 @@ __global__ __launch_bounds__(256) void tile_ranges_kernel(const KeyT *__restrict
     }
 }
 
-static int ceil_log2(int v)
-{
-    int bits = 0;
-    while ((1 << bits) < v) ++bits;
-    return bits;
-}
-
-// Coarse binning when the packed rect exists (frames up to 4096 px) and the gaussian ids leave four bits for the tile mask.
-// GsrOptions.fine_binning = 1 forces the fine path (A/B timing, and the test that both build the same frame).
-TileKeying tile_keying(const Workspace &ws, const GsrOptions &opts)
-{
-    TileKeying k;
-    static_assert(COARSE_ID_BITS == 28, "coarse_capable() in gsr_internal.h states the same limits");
-    k.coarse = coarse_capable(ws) && opts.fine_binning == 0;
-    k.grid_x = k.coarse ? ws.ctiles_x : ws.tiles_x;
-    k.grid_y = k.coarse ? ws.ctiles_y : ws.tiles_y;
-    k.bits_x = std::max(1, ceil_log2(k.grid_x));
-    k.bits_y = std::max(1, ceil_log2(k.grid_y + 1));  // one spare row value marks culled pairs
-    k.drop_from = (uint32_t)k.grid_y << k.bits_x;
-    return k;
-}
-
-// Coarse binning hands the blend the sorted CELL lists (values = gaussian id | tile mask << 28) and cranges[]; the blend of a tile
-// keeps the entries with its bit while it stages (blend.hip).  Round 2 expanded them into per-tile lists first (pair_expand_kernel:
-// 34 us, 122 MB of traffic, 16 B of workspace per pair slot); A/B in one process on the bench frame: bin + sort 0.375 -> 0.341 ms,
-// blend 0.553 -> 0.565 ms, frames and counters identical.
-bool blend_reads_cell_lists(const Workspace &ws, const GsrOptions &opts) { return tile_keying(ws, opts).coarse; }
-
-const uint32_t *tile_lists(const Workspace &ws, const GsrOptions &opts)
-{
-    const TileKeying tk = tile_keying(ws, opts);
-    if (ws.n <= 0 || ws.max_pairs <= 0) return ws.pval[0];
-    return ws.pval[((tk.bits_x + tk.bits_y + 7) / 8) & 1];  // ping-pong parity of the tile sort's passes
-}
-
-int launch_binning(const GsrOptions &opts, const Workspace &ws, hipStream_t s)
+int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, hipStream_t s)
 {
     const int n_tiles = ws.tiles_x * ws.tiles_y;
     if (ws.n <= 0) {  // no count kernel to clear the ranges (per tile, and per cell for a blend that reads the cell lists)
@@ -415,15 +378,6 @@ int launch_binning(const GsrOptions &opts, const Workspace &ws, hipStream_t s)
     }
     const unsigned nv = (unsigned)ws.views;  // gridDim.y: one workspace slice per view
     const size_t vs = ws.view_stride;
-    const bool packed_rect = rect_fits_8bit(ws);
-    const RowShard sh = row_shard_of(opts);
-    // cells of a shard: pairs of rows (tile_row_block = 2) ARE cell rows — the rank owns cell rows begin + k step whole; with single rows
-    // and an even step the rank's tile rows begin + k step fall into the cell rows (begin >> 1) + k (step >> 1), each holding exactly one
-    // of them; with an odd step (or none) every cell row can hold one.  The expansion keeps only this rank's tiles either way.
-    const RowShard csh = sh.step <= 1 ? RowShard{0, 1, 0}
-                       : sh.bshift == 1 ? RowShard{sh.begin, sh.step, 0}
-                       : sh.step % 2 == 0 ? RowShard{sh.begin >> 1, sh.step >> 1, 0} : RowShard{0, 1, 0};
-    const TileKeying tk = tile_keying(ws, opts);
     const int n_ctiles = ws.ctiles_x * ws.ctiles_y;
     const uint32_t cap = (uint32_t)ws.max_pairs;
     const uint32_t limit = opts.draw_limit > 0 ? (uint32_t)opts.draw_limit : 0xFFFFFFFFu;
@@ -433,16 +387,15 @@ int launch_binning(const GsrOptions &opts, const Workspace &ws, hipStream_t s)
     const int nblk_count = std::min((nblk_n + COUNT_BLOCKS_PER_WG - 1) / COUNT_BLOCKS_PER_WG, EMIT_GRID_CAP / COUNT_BLOCKS_PER_WG);
     const int nblk_emit = std::min(nblk_n, EMIT_GRID_CAP);
 #define GSR_COUNT(P, C) hipLaunchKernelGGL((pair_count_kernel<P, C>), dim3(nblk_count, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.rect8[0], ws.rect8[1], \
-                                           ws.ctrl, ws.rect, C ? csh : sh, ws.blk_sum, ws.ranges, n_tiles, limit, ws.cranges, n_ctiles, ws.ctrl, \
+                                           ws.ctrl, ws.rect, C ? plan.csh : plan.rs, ws.blk_sum, ws.ranges, n_tiles, limit, ws.cranges, n_ctiles, ws.ctrl, \
                                            C ? (uint32_t)(reinterpret_cast<const char *>(ws.blk_sum) - reinterpret_cast<const char *>(ws.ctrl)) : 0u, nblk_n, nblk_count, vs)
-    const bool k16 = pair_keys_16bit(tk.bits_x + tk.bits_y);  // two-byte keys in memory when they fit (sort.hip)
 #define GSR_EMIT_T(P, C, T) hipLaunchKernelGGL((pair_emit_kernel<P, C, T>), dim3(nblk_emit, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.rect8[0], ws.rect8[1], \
-                                          ws.ctrl, ws.rect, C ? csh : sh, tk.bits_x, tk.grid_y, ws.rec, ws.blk_sum, cap, reinterpret_cast<T *>(ws.pkey[0]), ws.pval[0], limit, \
-                                          sh, ws.blk_sum, nblk_emit, vs)
-#define GSR_EMIT(P, C) do { if (k16) GSR_EMIT_T(P, C, uint16_t); else GSR_EMIT_T(P, C, uint32_t); } while (0)
-    if (tk.coarse) GSR_COUNT(true, true); else if (packed_rect) GSR_COUNT(true, false); else GSR_COUNT(false, false);
+                                          ws.ctrl, ws.rect, C ? plan.csh : plan.rs, plan.bits_x, plan.grid_y, ws.rec, ws.blk_sum, cap, reinterpret_cast<T *>(ws.pkey[0]), ws.pval[0], limit, \
+                                          plan.rs, ws.blk_sum, nblk_emit, vs)
+#define GSR_EMIT(P, C) do { if (plan.key16) GSR_EMIT_T(P, C, uint16_t); else GSR_EMIT_T(P, C, uint32_t); } while (0)
+    if (plan.coarse) GSR_COUNT(true, true); else if (plan.packed_rect) GSR_COUNT(true, false); else GSR_COUNT(false, false);
     hipLaunchKernelGGL(pair_scan_kernel, dim3(1, nv), dim3(1024), 0, s, ws.blk_sum, nblk_n, ws.ctrl, cap, vs);
-    if (tk.coarse) GSR_EMIT(true, true); else if (packed_rect) GSR_EMIT(true, false); else GSR_EMIT(false, false);
+    if (plan.coarse) GSR_EMIT(true, true); else if (plan.packed_rect) GSR_EMIT(true, false); else GSR_EMIT(false, false);
 #undef GSR_COUNT
 #undef GSR_EMIT
 #undef GSR_EMIT_T
@@ -450,14 +403,15 @@ int launch_binning(const GsrOptions &opts, const Workspace &ws, hipStream_t s)
     if (ws.max_pairs <= 0) return GSR_OK;
     // stable sort by cell / tile key; the first pass drops the pairs the emit kernel culled and leaves their count in ctrl
     int pbuf = 0;
-    uint32_t *n_sorted = tk.coarse ? &ws.ctrl->n_cpairs : &ws.ctrl->n_pairs;
-    const int rc = launch_pair_sort(ws, 0, &ws.ctrl->n_slots, 0, tk.bits_x + tk.bits_y, tk.drop_from, n_sorted, &pbuf, s);
+    uint32_t *n_sorted = plan.coarse ? &ws.ctrl->n_cpairs : &ws.ctrl->n_pairs;
+    const int rc = launch_pair_sort(ws, plan, &ws.ctrl->n_slots, n_sorted, &pbuf, s);
     if (rc) return rc;
+    if (pbuf != plan.lists_buf) { set_error("pair sort left the lists in buffer %d, the blend reads %d", pbuf, plan.lists_buf); return GSR_ERR_HIP; }
     const int grid = (int)std::min<int64_t>((ws.max_pairs + 1023) / 1024, 8192);
-    if (k16) hipLaunchKernelGGL(tile_ranges_kernel<uint16_t>, dim3(grid, nv), dim3(256), 0, s, reinterpret_cast<const uint16_t *>(ws.pkey[pbuf]), n_sorted,
-                                tk.coarse ? ws.cranges : ws.ranges, tk.bits_x, tk.grid_x, tk.grid_x * tk.grid_y, (uint32_t)grid * 256u, vs);
-    else hipLaunchKernelGGL(tile_ranges_kernel<uint32_t>, dim3(grid, nv), dim3(256), 0, s, ws.pkey[pbuf], n_sorted, tk.coarse ? ws.cranges : ws.ranges, tk.bits_x,
-                            tk.grid_x, tk.grid_x * tk.grid_y, (uint32_t)grid * 256u, vs);
+    if (plan.key16) hipLaunchKernelGGL(tile_ranges_kernel<uint16_t>, dim3(grid, nv), dim3(256), 0, s, reinterpret_cast<const uint16_t *>(ws.pkey[pbuf]), n_sorted,
+                                plan.coarse ? ws.cranges : ws.ranges, plan.bits_x, plan.grid_x, plan.grid_x * plan.grid_y, (uint32_t)grid * 256u, vs);
+    else hipLaunchKernelGGL(tile_ranges_kernel<uint32_t>, dim3(grid, nv), dim3(256), 0, s, ws.pkey[pbuf], n_sorted, plan.coarse ? ws.cranges : ws.ranges, plan.bits_x,
+                            plan.grid_x, plan.grid_x * plan.grid_y, (uint32_t)grid * 256u, vs);
     GSR_HIP(hipGetLastError());
     return GSR_OK;
 }

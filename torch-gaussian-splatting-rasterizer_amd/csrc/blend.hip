@@ -957,7 +957,7 @@ __global__ __launch_bounds__(256) void tile_order_kernel(const uint2 *__restrict
     }
     __syncthreads();
     uint32_t total;
-    bucket_start[tid] = block_excl_scan_256(bucket_cnt[tid], scratch, &total);
+    bucket_start[tid] = block_excl_scan<256>(bucket_cnt[tid], scratch, &total);
     __syncthreads();
     for (int j = tid; j < n; j += 256) {
         const int tile = tile_of(j);
@@ -1089,7 +1089,7 @@ __global__ __launch_bounds__(256) void blend_kernel(BlendArgs args)
 // batch.  QPW = 1: 256 threads, wave = one quadrant, 256 entries per batch — the same walk with quadrant B switched off.
 // Two quadrants per wave share LDS reads and part of the quadratic (7-8 % faster on a whole frame), but with few tiles per CU
 // (a multi-GPU rank's shard) four waves per tile fill the SIMDs better and halve the per-tile critical path (G = 8 shard:
-// 0.52 vs 0.65 ms), so launch_blend picks by tile count.  Same lists, same per-quadrant classification and saturation tests,
+// 0.52 vs 0.65 ms), so plan_frame (api.hip) picks by tile count.  Same lists, same per-quadrant classification and saturation tests,
 // same arithmetic as blend_kernel.
 template <int QPW, bool PIPE>  // PIPE (QPW = 1 only): the pipelined walk, 96 VGPRs, for grids that 5 waves per SIMD hold
 __global__ __launch_bounds__(256 / QPW, PIPE ? 5 : 8) void blend_walk_kernel(BlendArgs args)
@@ -1208,16 +1208,7 @@ __global__ __launch_bounds__(256 / QPW, PIPE ? 5 : 8) void blend_walk_kernel(Ble
     }
 }
 
-// two quadrants per wave from this many tiles per launch on (measured: 4080 tiles better with two, 2040 with one); below, one quadrant per wave (see blend_walk_kernel)
-#ifndef GSR_BLEND_HALF_MIN_TILES
-#define GSR_BLEND_HALF_MIN_TILES 3000
-#endif
-constexpr int BLEND_HALF_MIN_TILES = GSR_BLEND_HALF_MIN_TILES;  // (the macro: tools/ A/B builds)
-// the pipelined one-quadrant walk (96 VGPRs: 5 waves per SIMD = 1280 four-wave workgroups resident) up to this many tiles per launch;
-// GsrOptions.blend_pipe_tiles overrides it (experiments and tests: -1 switches the variant off)
-constexpr int BLEND_PIPE_MAX_TILES = 1280;
-
-int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const uint32_t *lists, void *out_image,
+int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, void *out_image,
                  size_t out_view_stride, float *out_T, const GsrScene *scene, hipStream_t s)
 {
     if (ws.views > 1 && (out_T || scene)) { set_error("final T / an explicit scene: single views only"); return GSR_ERR_BAD_ARG; }
@@ -1233,8 +1224,8 @@ int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &
     a.ranges = ws.ranges;
     a.cranges = ws.cranges;
     a.ctiles_x = ws.ctiles_x;
-    a.cell_lists = blend_reads_cell_lists(ws, opts) ? 1 : 0;
-    a.pval = lists;
+    a.cell_lists = plan.cell_lists ? 1 : 0;
+    a.pval = ws.pval[plan.lists_buf];
     a.rec = ws.rec;
     a.ctrl = ws.ctrl;
     a.out = out_image;
@@ -1245,14 +1236,13 @@ int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &
     a.xlim = opts.reference_compat ? cam.width - 1 : cam.width;
     a.ylim = opts.reference_compat ? cam.height - 1 : cam.height;
     a.tiles_x = ws.tiles_x;
-    a.rs = row_shard_of(opts);
-    a.rows = a.rs.rows_before(ws.tiles_y);
+    a.rs = plan.rs;
+    a.rows = plan.rows;
     a.layout = opts.output_layout;
     a.out_bf16 = opts.output_dtype == 1;
     a.early_T = opts.early_out_T;
     // the colour-saturation rule (blend_args.h) leaves T unfinished: when the caller asks for the final T it is an output like the colour
     a.sat_scale = (opts.saturation_rule == 0 && out_T == nullptr) ? 0x1p-25f : 0.0f;
-    const int pipe_max_tiles = opts.blend_pipe_tiles == 0 ? BLEND_PIPE_MAX_TILES : opts.blend_pipe_tiles;
     if (a.rows <= 0 || a.tiles_x <= 0) return GSR_OK;
     const int rows_per_xcd = (a.rows + 7) / 8;
     const int slots_per_group = rows_per_xcd * a.tiles_x;
@@ -1261,14 +1251,14 @@ int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &
                        slots_per_group, ws.tile_order,
                        (uint32_t)(reinterpret_cast<const char *>(ws.blend_stats) - reinterpret_cast<const char *>(ws.ctrl)),
                        a.cell_lists ? ws.cranges : nullptr, ws.ctiles_x, opts.no_order_hint ? nullptr : ws.tile_work, ws.view_stride);
-    // which walk: by the tiles of the whole launch (all views: what fills the machine)
-    const int launch_tiles = a.rows * a.tiles_x * ws.views;
     const dim3 grid(8u * (unsigned)slots_per_group, nv);
-    if (opts.accum_dtype == 1) hipLaunchKernelGGL(blend_kernel<true>, grid, dim3(256), 0, s, a);
-    else if (opts.blend_impl == 1) hipLaunchKernelGGL(blend_kernel<false>, grid, dim3(256), 0, s, a);
-    else if (launch_tiles >= BLEND_HALF_MIN_TILES) hipLaunchKernelGGL((blend_walk_kernel<2, false>), grid, dim3(128), 0, s, a);
-    else if (launch_tiles <= pipe_max_tiles) hipLaunchKernelGGL((blend_walk_kernel<1, true>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((blend_walk_kernel<1, false>), grid, dim3(256), 0, s, a);
+    switch (plan.blend) {
+    case BlendKernel::TileBf16: hipLaunchKernelGGL(blend_kernel<true>, grid, dim3(256), 0, s, a); break;
+    case BlendKernel::Tile: hipLaunchKernelGGL(blend_kernel<false>, grid, dim3(256), 0, s, a); break;
+    case BlendKernel::Walk2: hipLaunchKernelGGL((blend_walk_kernel<2, false>), grid, dim3(128), 0, s, a); break;
+    case BlendKernel::Walk1Pipe: hipLaunchKernelGGL((blend_walk_kernel<1, true>), grid, dim3(256), 0, s, a); break;
+    case BlendKernel::Walk1: hipLaunchKernelGGL((blend_walk_kernel<1, false>), grid, dim3(256), 0, s, a); break;
+    }
     GSR_HIP(hipGetLastError());
     return GSR_OK;
 }

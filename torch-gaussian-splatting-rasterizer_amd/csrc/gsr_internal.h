@@ -135,46 +135,6 @@ int hip_fail(hipError_t e, const char *what);
         if (e__ != hipSuccess) return gsr::hip_fail(e__, #call); \
     } while (0)
 
-// ---- kernels' host launchers (each returns GSR_OK / GSR_ERR_HIP) --------------------------------
-// cams: ws.views cameras (one frame size); ctrl_reset_words: how much of each view's control block the frame clears
-int launch_preprocess(const GsrScene &scene, const GsrCamera *cams, const GsrOptions &opts, const Workspace &ws,
-                      const GsrDebugOut *dbg, int ctrl_reset_words, hipStream_t s);
-int launch_block_visibility(const GsrScene &scene, const GsrCamera &cam, const GsrOptions &opts, unsigned char *dead, hipStream_t s);
-int launch_scene_bounds(int64_t n, const float *means, const float *log_scales, float *bounds, hipStream_t s);
-int launch_sh_to_rgb(int64_t n, const float *means, const float *sh, const float cc[3], int degree, float *rgb, hipStream_t s);
-int launch_cov3d(int64_t n, const float *log_scales, const float *quats, float *out, hipStream_t s);
-int launch_project(int64_t n, const float *means, const float w2c[16], float *out, hipStream_t s);
-int launch_cov2d(int64_t n, const float *cov3d, const float *cam_means, const float w2c[16], float fx, float fy, float limx, float limy,
-                 float *out, hipStream_t s);
-int launch_bbox(int64_t n, const float *screen_means, const float *cov2d, float W, float H, int64_t *out, hipStream_t s);
-int launch_rasterize_gaussian(int64_t g, const int64_t *bboxes, float *screen, const float *screen_means, const float *sigmas,
-                              const float *rgb, float *opacity_buffer, const float *opacity, int W, int H, hipStream_t s);
-
-// Depth order (sort.hip): stable LSD radix sort of the depth keys; leaves V in FrameCtrl.n_visible and the sorted ids (+ packed
-// rects) in val[p] / rect8[p], p = FrameCtrl.sort_passes & 1 (decided on the device from the frame's key range).  passes: how
-// many to enqueue (GsrOptions.depth_sort_passes; 0 = 4).
-int launch_depth_sort(const Workspace &ws, bool packed_rect, bool compact_input, int passes, hipStream_t s);
-// gsr_scene_order (sort.hip): Morton-curve permutation of the gaussians, built with the radix passes of the pair sort
-size_t scene_order_bytes(int64_t n);
-int launch_scene_order(int64_t n, const float *means, uint32_t *perm_out, void *workspace, hipStream_t s);
-// Stable radix sort of the pair arrays over key bits [first_bit, key_bits); the first pass drops keys >= drop_from and leaves the
-// survivor count in *n_out.  in_buf / *result_buf: which of pkey[]/pval[] holds input / output.
-int launch_pair_sort(const Workspace &ws, int in_buf, const uint32_t *n_dev, int first_bit, int key_bits, uint32_t drop_from,
-                     uint32_t *n_out, int *result_buf, hipStream_t s);
-// The pair sort keeps its keys as uint16_t in memory when every key (the culled row included) fits: 6 B per pair instead of 8 through
-// emit, both sort passes and the range scan, all of them bound by HBM.  key_bits = TileKeying.bits_x + bits_y.
-inline bool pair_keys_16bit(int key_bits) { return key_bits <= 16; }
-// Pair keys: (tile row << bits_x) | tile column; culled pairs carry the row `tiles_y` and are dropped from drop_from on.
-struct TileKeying {
-    int bits_x, bits_y;   // of the grid the pairs are generated on: tiles, or 32x32 cells when `coarse`
-    uint32_t drop_from;
-    bool coarse;          // pairs are generated and sorted per 32x32 cell; the blend filters the cell lists by tile (binning.hip)
-    int grid_x, grid_y;
-};
-TileKeying tile_keying(const Workspace &ws, const GsrOptions &opts);
-inline bool rect_fits_8bit(const Workspace &ws) { return ws.tiles_x <= 256 && ws.tiles_y <= 256; }
-// Can this frame bin per 32x32 cell (binning.hip)?  Needs the packed rect and pair values of 28 id bits + 4 mask bits.
-inline bool coarse_capable(const Workspace &ws) { return rect_fits_8bit(ws) && ws.n <= ((int64_t)1 << 28); }
 // Which tile rows a rank owns (multi-GPU sharding, GsrOptions.tile_row_begin / _step / _block): blocks of 2^bshift consecutive tile
 // rows, block b is the rank's when b % step == begin.  bshift 0: the rows begin, begin + step, ...; bshift 1: pairs of rows = the
 // tile rows of one 32x32 cell row.  The rank's rows in ascending order are its STRIP rows (output_layout = 2): index k <-> row_at(k).
@@ -205,23 +165,71 @@ inline RowShard row_shard_of(const GsrOptions &o)
     return RowShard{o.tile_row_begin, o.tile_row_step < 1 ? 1 : o.tile_row_step, o.tile_row_block == 2 ? 1 : 0};
 }
 
-// A multi-GPU shard's preprocess (preprocess.hip) hands the depth sort a compact list of (key, id, rect) records of the rank's
-// visible gaussians instead of one key per gaussian.  Progressive frames (draw_limit) rank ALL gaussians the reference
-// draws, so they take the whole-frame path.
-inline bool shard_compact(const GsrOptions &o)
-{
-    if (o.tile_row_step <= 1 || o.draw_limit != 0) return false;
-    if (o.shard_preprocess != 0) return o.shard_preprocess == 2;  // A/B: 1 = whole-frame kernel, 2 = three-phase kernel
-    return o.tile_row_step >= 5;  // measured: 2 and 4 shards are as fast or faster through the whole-frame kernel
-}
+// ---- the frame's plan -----------------------------------------------------------------------------
+// Every host-side choice a frame makes: which kernel variants run and which buffer each stage leaves its result in.  Decided once per
+// entry point by plan_frame (api.hip), where the reasons stand; the launchers below read their choices from it and derive none.
+enum class BlendKernel {
+    Tile,       // blend_kernel<false>: one workgroup per tile, fp32 accumulators (GsrOptions.blend_impl = 1)
+    TileBf16,   // blend_kernel<true>: the same with bf16 accumulators (GsrOptions.accum_dtype = 1)
+    Walk2,      // blend_walk_kernel<2, false>: two quadrants per wave
+    Walk1,      // blend_walk_kernel<1, false>: one quadrant per wave
+    Walk1Pipe,  // blend_walk_kernel<1, true>: one quadrant per wave, pipelined
+};
+constexpr int COARSE_ID_BITS = 28;  // coarse pairs: value = gaussian id | (mask of the cell's tiles the gaussian reaches) << 28
+struct FramePlan {
+    // stage 1 (preprocess.hip)
+    bool packed_rect;      // the tile rect is written packed into rect8[0] and rides through the depth sort as a second payload; else ushort4 in rect[], gathered by id
+    bool compact_input;    // the three-phase shard kernel hands the depth sort compact (key, id, rect) records; else the whole-frame kernel (its K-view form when ws.views > 1) one key per gaussian
+    RowShard rs;           // the rank's tile rows
+    RowShard cull_rs;      // the rows block-level culling tests a block against
+    // depth sort (sort.hip)
+    int depth_passes;      // radix passes enqueued (1..4)
+    int depth_items;       // keys per thread: DEPTH_SORT_ITEMS or DEPTH_SORT_ITEMS_SHARD
+    // binning and pair sort (binning.hip, sort.hip).  Pair keys: (grid row << bits_x) | grid column; culled pairs carry the row
+    // grid_y and are dropped from drop_from on
+    bool coarse;           // pairs are generated and sorted per 32x32 cell (grid = cells); else per tile
+    int grid_x, grid_y, bits_x, bits_y;
+    uint32_t drop_from;
+    RowShard csh;          // the cell rows the rank's tile rows fall into
+    bool key16;            // pair keys are uint16_t in memory (the first half of each pkey buffer)
+    int pair_passes, pair_bits_pp;  // radix passes of the pair sort, and key bits each takes (the last: what is left)
+    int lists_buf;         // pval[lists_buf] holds the lists (gaussian ids [| tile mask << COARSE_ID_BITS]) that ranges[] / cranges[] index after launch_binning
+    // blend (blend.hip)
+    bool cell_lists;       // the blend filters the 32x32-cell lists by tile bit itself
+    int rows;              // tile rows the rank blends
+    BlendKernel blend;
+};
+FramePlan plan_frame(const Workspace &ws, const GsrOptions &opts);  // ws: after check_frame, with ws.views set
+
+// ---- kernels' host launchers (each returns GSR_OK / GSR_ERR_HIP) --------------------------------
+// cams: ws.views cameras (one frame size); ctrl_reset_words: how much of each view's control block the frame clears
+int launch_preprocess(const GsrScene &scene, const GsrCamera *cams, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
+                      const GsrDebugOut *dbg, int ctrl_reset_words, hipStream_t s);
+int launch_block_visibility(const GsrScene &scene, const GsrCamera &cam, const FramePlan &plan, unsigned char *dead, hipStream_t s);
+int launch_scene_bounds(int64_t n, const float *means, const float *log_scales, float *bounds, hipStream_t s);
+int launch_sh_to_rgb(int64_t n, const float *means, const float *sh, const float cc[3], int degree, float *rgb, hipStream_t s);
+int launch_cov3d(int64_t n, const float *log_scales, const float *quats, float *out, hipStream_t s);
+int launch_project(int64_t n, const float *means, const float w2c[16], float *out, hipStream_t s);
+int launch_cov2d(int64_t n, const float *cov3d, const float *cam_means, const float w2c[16], float fx, float fy, float limx, float limy,
+                 float *out, hipStream_t s);
+int launch_bbox(int64_t n, const float *screen_means, const float *cov2d, float W, float H, int64_t *out, hipStream_t s);
+int launch_rasterize_gaussian(int64_t g, const int64_t *bboxes, float *screen, const float *screen_means, const float *sigmas,
+                              const float *rgb, float *opacity_buffer, const float *opacity, int W, int H, hipStream_t s);
+
+// Depth order (sort.hip): stable LSD radix sort of the depth keys; leaves V in FrameCtrl.n_visible and the sorted ids (+ packed
+// rects) in val[p] / rect8[p], p = FrameCtrl.sort_passes & 1 (decided on the device from the frame's key range).
+int launch_depth_sort(const Workspace &ws, const FramePlan &plan, hipStream_t s);
+// gsr_scene_order (sort.hip): Morton-curve permutation of the gaussians, built with the radix passes of the pair sort
+size_t scene_order_bytes(int64_t n);
+int launch_scene_order(int64_t n, const float *means, uint32_t *perm_out, void *workspace, hipStream_t s);
+// Stable radix sort of the pair arrays in pkey[0] / pval[0] by the plan's keys (sort.hip); needs max_pairs > 0
+int launch_pair_sort(const Workspace &ws, const FramePlan &plan, const uint32_t *n_dev, uint32_t *n_out, int *result_buf, hipStream_t s);
 // Stage 2b: pairs of the depth-sorted gaussians -> per-tile depth-ordered lists + ranges[] (count, scan, emit, sort, ranges,
 // and with coarse binning the expansion).
-int launch_binning(const GsrOptions &opts, const Workspace &ws, hipStream_t s);
-const uint32_t *tile_lists(const Workspace &ws, const GsrOptions &opts);  // the array ranges[] / cranges[] index after launch_binning (gaussian ids [| tile mask << 28])
-bool blend_reads_cell_lists(const Workspace &ws, const GsrOptions &opts);  // coarse binning: the blend filters the 32x32-cell lists by tile bit itself
+int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, hipStream_t s);
 // out_image: view 0's frame, view v's lies v * out_view_stride BYTES further (out_T: single views only).  scene: where deferred
 // colours are evaluated from (single views only); nullptr = what the preprocess left in the workspace's control block
-int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const uint32_t *lists, void *out_image,
+int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, void *out_image,
                  size_t out_view_stride, float *out_T, const GsrScene *scene, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
@@ -237,28 +245,8 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
     return v;
 }
 
-// Exclusive scan across a 256-thread workgroup (4 waves).  `scratch` = 8 uint32 of LDS.  Returns the
+// Exclusive scan across a workgroup of THREADS = 64 * WAVES threads.  `scratch` = 2 * WAVES uint32 of LDS.  Returns the
 // exclusive prefix of `v`; *total receives the workgroup sum.  Contains two __syncthreads().
-__device__ __forceinline__ uint32_t block_excl_scan_256(uint32_t v, uint32_t *scratch, uint32_t *total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t incl = wave_incl_scan(v);
-    if (lane == 63) scratch[wave] = incl;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) {
-        const uint32_t s = scratch[w];
-        if (w < wave) base += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return base + incl - v;
-}
-
-
-// The same for THREADS = 64 * WAVES threads; `scratch` = 2 * WAVES uint32 of LDS.
 template <int THREADS>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t *scratch, uint32_t *total)
 {

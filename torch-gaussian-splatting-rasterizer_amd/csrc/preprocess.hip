@@ -622,7 +622,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
         cand |= k ? 1u << r : 0u;
     }
     uint32_t ncand;
-    uint32_t cpos = block_excl_scan_256((uint32_t)__popc(cand), s_scan, &ncand);
+    uint32_t cpos = block_excl_scan<256>((uint32_t)__popc(cand), s_scan, &ncand);
 #pragma unroll
     for (int r = 0; r < SHARD_PER; ++r)
         if ((cand >> r) & 1u) s_cand[cpos++] = (uint32_t)(i0 + r);
@@ -693,7 +693,7 @@ __global__ __launch_bounds__(256) void shard_compact_kernel(const uint32_t *__re
         mine += (c.x + c.y) + (c.z + c.w);
     }
     uint32_t before;
-    block_excl_scan_256(mine, scratch, &before);
+    block_excl_scan<256>(mine, scratch, &before);
     // the eight runs as ONE list of T records: record j lies in the run whose prefix it has passed (the eight prefixes stay in
     // registers), so that every thread's loads are independent of one another — four in flight before the first store
     uint32_t pre[COMPACT_RUNS + 1];
@@ -783,25 +783,23 @@ __global__ __launch_bounds__(256) void block_flags_kernel(GsrScene sc, CamBatch 
     if (b < nblk) view_slice(dead0, vstride)[b] = block_dead(sc.block_bounds + 8 * b, cams.cam[blockIdx.y], rs) ? 1 : 0;
 }
 
-static void launch_block_flags(const GsrScene &scene, const CamBatch &kb, int views, size_t vstride, const GsrOptions &opts, unsigned char *dead, hipStream_t s)
+static void launch_block_flags(const GsrScene &scene, const CamBatch &kb, int views, size_t vstride, const RowShard &rs, unsigned char *dead, hipStream_t s)
 {
     const int64_t nblk = (scene.n + GSR_BOUNDS_BLOCK - 1) / GSR_BOUNDS_BLOCK;
-    // progressive frames rank every gaussian the reference draws, whatever rows it touches: no row test then
-    const RowShard rs = opts.draw_limit > 0 ? RowShard{0, 1, 0} : row_shard_of(opts);
     hipLaunchKernelGGL(block_flags_kernel, dim3((unsigned)((nblk + 255) / 256), (unsigned)views), dim3(256), 0, s, scene, kb, vstride, rs, dead);
 }
 
-int launch_block_visibility(const GsrScene &scene, const GsrCamera &cam, const GsrOptions &opts, unsigned char *dead, hipStream_t s)
+int launch_block_visibility(const GsrScene &scene, const GsrCamera &cam, const FramePlan &plan, unsigned char *dead, hipStream_t s)
 {
     if (scene.n <= 0) return GSR_OK;
     CamBatch kb;
     for (int v = 0; v < MAX_VIEWS; ++v) kb.cam[v] = make_cam(cam);
-    launch_block_flags(scene, kb, 1, 0, opts, dead, s);
+    launch_block_flags(scene, kb, 1, 0, plan.cull_rs, dead, s);
     GSR_HIP(hipGetLastError());
     return GSR_OK;
 }
 
-int launch_preprocess(const GsrScene &scene, const GsrCamera *cams, const GsrOptions &opts, const Workspace &ws,
+int launch_preprocess(const GsrScene &scene, const GsrCamera *cams, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
                       const GsrDebugOut *dbg, int ctrl_reset_words, hipStream_t s)
 {
     const int views = ws.views;
@@ -818,8 +816,8 @@ int launch_preprocess(const GsrScene &scene, const GsrCamera *cams, const GsrOpt
     GsrDebugOut d;
     memset(&d, 0, sizeof d);
     if (dbg) d = *dbg;
-    const RowShard rs = row_shard_of(opts);
-    const int packed = rect_fits_8bit(ws) ? 1 : 0;
+    const RowShard rs = plan.rs;
+    const int packed = plan.packed_rect ? 1 : 0;
     const bool h16 = scene.sh_dtype == 1;
     // from how many visible gaussians per wave on the wave's SH rows are fetched whole through LDS (load_sh48_wave);
     // GsrOptions.sh_dense_min overrides it for experiments (65 = never).  Swept on the bench frame (file order / Morton order): >= 56: 0.273 / 0.216 ms,
@@ -832,8 +830,8 @@ int launch_preprocess(const GsrScene &scene, const GsrCamera *cams, const GsrOpt
     // kernel costs what the skipped loads return — 5.4 + 84.2 us against 82.6 us without; with rows in pairs, rank 2 of 8, four views:
     // 9.4 + 218.7 against 222)
     const unsigned char *blk_dead = nullptr;
-    if (scene.block_bounds != nullptr && !dbg && !shard_compact(opts)) {
-        launch_block_flags(scene, kb, views, ws.view_stride, opts, ws.blk_dead, s);
+    if (scene.block_bounds != nullptr && !dbg && !plan.compact_input) {
+        launch_block_flags(scene, kb, views, ws.view_stride, plan.cull_rs, ws.blk_dead, s);
         blk_dead = ws.blk_dead;
     }
 #define GSR_LAUNCH_PRE(DBG, H16, COL)                                                                                         \
@@ -847,7 +845,7 @@ int launch_preprocess(const GsrScene &scene, const GsrCamera *cams, const GsrOpt
     // debug outputs cover every gaussian: for a shard (below) that is a pass of its own, whose other outputs are then
     // overwritten
     if (dbg) { if (h16) GSR_LAUNCH_PRE(true, true, true); else GSR_LAUNCH_PRE(true, false, true); }
-    if (shard_compact(opts)) {
+    if (plan.compact_input) {
         const unsigned sgrid = (unsigned)((scene.n + SHARD_SPAN - 1) / SHARD_SPAN);
         // the workgroups' runs go to the "out" halves of the depth sort's ping-pong buffers, idle until its pass 0 scatters
         // into them (after shard_compact_kernel has read them); their lengths to blk_sum, idle until the pair count

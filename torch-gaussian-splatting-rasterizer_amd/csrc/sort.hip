@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void radix_rowscan_kernel(uint32_t *__restrict
         for (int j = 0; j < 4; ++j) v[j] = (i0 + j < nblk) ? row[i0 + j] : 0u;
         const uint32_t mine = v[0] + v[1] + v[2] + v[3];
         uint32_t total;
-        uint32_t ex = block_excl_scan_256(mine, scratch, &total) + carry;
+        uint32_t ex = block_excl_scan<256>(mine, scratch, &total) + carry;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (i0 + j < nblk) row[i0 + j] = ex;
@@ -284,24 +284,25 @@ static void launch_pass(const KeyT *kin, const uint32_t *vin, const uint32_t *v2
 #undef GSR_SCATTER
 }
 
-// Depth order of the gaussians (rasterize.py:424-425).  Four passes enqueued unless the caller bounds them (GsrOptions.
-// depth_sort_passes), 3 run on ordinary scenes (header); a plan that needs more than were enqueued is flagged.
+// Depth order of the gaussians (rasterize.py:424-425).  plan.depth_passes radix passes are enqueued: four unless the caller bounds
+// them (GsrOptions.depth_sort_passes), 3 run on ordinary scenes (header); a frame that needs more than were enqueued is flagged.
 // Afterwards FrameCtrl.n_visible = V and the sorted ids / packed rects are in val[p] / rect8[p], p = sort_passes & 1.
 template <int ITEMS>
-static int depth_sort_passes(const Workspace &ws, bool packed_rect, bool compact_input, int passes, hipStream_t s)
+static int depth_sort_passes(const Workspace &ws, const FramePlan &plan, hipStream_t s)
 {
     constexpr int TILE = DEPTH_SORT_THREADS * ITEMS;
     const int nblk = (int)((ws.n + TILE - 1) / TILE);
     if (nblk > ws.hist_blocks) { set_error("radix sort: %d tiles exceed the histogram stride %d", nblk, ws.hist_blocks); return GSR_ERR_WORKSPACE; }
     // compact_input (multi-GPU shard): the input is FrameCtrl.n_records (key, id[, rect]) records in id order, left in
     // key[0] / val[0] / rect8[0] by preprocess.hip, instead of one key per gaussian
+    const bool compact_input = plan.compact_input;
     const uint32_t *cnt_dev = compact_input ? &ws.ctrl->n_records : nullptr;
-    const int enq = passes >= 1 && passes <= 4 ? passes : 4;
+    const int enq = plan.depth_passes;
     for (int p = 0; p < enq; ++p) {
         const PassSpec ps = {0, 0u, DEPTH_KEY_BASE, KEY_INVALID, p, enq};
         const int in = p & 1, out = in ^ 1;
         const bool first = p == 0;
-        if (packed_rect)
+        if (plan.packed_rect)
             launch_pass<DEPTH_SORT_THREADS, ITEMS, true>(ws.key[in], ws.val[in], ws.rect8[in], ws.key[out], ws.val[out], ws.rect8[out], cnt_dev, ws.n, ps,
                                                      first, first && !compact_input, first ? &ws.ctrl->n_visible : nullptr, ws, s);
         else
@@ -313,37 +314,29 @@ static int depth_sort_passes(const Workspace &ws, bool packed_rect, bool compact
     return GSR_OK;
 }
 
-int launch_depth_sort(const Workspace &ws, bool packed_rect, bool compact_input, int passes, hipStream_t s)
+int launch_depth_sort(const Workspace &ws, const FramePlan &plan, hipStream_t s)
 {
     if (ws.n <= 0) return GSR_OK;
-    // a shard's compact records are few (its visible gaussians): smaller tiles, more workgroups, shorter serial chains
-    return compact_input ? depth_sort_passes<DEPTH_SORT_ITEMS_SHARD>(ws, packed_rect, true, passes, s)
-                         : depth_sort_passes<DEPTH_SORT_ITEMS>(ws, packed_rect, false, passes, s);
+    return plan.depth_items == DEPTH_SORT_ITEMS_SHARD ? depth_sort_passes<DEPTH_SORT_ITEMS_SHARD>(ws, plan, s)
+                                                      : depth_sort_passes<DEPTH_SORT_ITEMS>(ws, plan, s);
 }
 
-// Stable sort of the (tile key, gaussian id) pairs over key bits [first_bit, key_bits), 8 bits or fewer per pass, the bits
-// split evenly (13 tile-id bits sort as 7 + 6, not 8 + 5: with 128 digit values a workgroup's runs in the first,
-// far-scattering pass are 32 entries = one full 128-B line per array instead of half a line).  The first pass run here
-// drops keys >= drop_from (pairs culled at emission) and leaves the survivor count in *n_out.  in_buf: which of
-// pkey[]/pval[] holds the input; *result_buf: which holds the output.
-int launch_pair_sort(const Workspace &ws, int in_buf, const uint32_t *n_dev, int first_bit, int key_bits, uint32_t drop_from,
-                     uint32_t *n_out, int *result_buf, hipStream_t s)
+// Stable sort of the (tile key, gaussian id) pairs in pkey[0] / pval[0] over the plan's key bits, plan.pair_bits_pp per pass.
+// The first pass drops keys >= plan.drop_from (pairs culled at emission) and leaves the survivor count in *n_out.
+// *result_buf: which of pkey[] / pval[] holds the output.  Needs max_pairs > 0.
+int launch_pair_sort(const Workspace &ws, const FramePlan &plan, const uint32_t *n_dev, uint32_t *n_out, int *result_buf, hipStream_t s)
 {
-    *result_buf = in_buf;
-    if (ws.max_pairs <= 0 || key_bits <= first_bit) return GSR_OK;
     constexpr int TILE = PAIR_SORT_THREADS * PAIR_SORT_ITEMS;
     const int nblk = (int)((ws.max_pairs + TILE - 1) / TILE);
     if (nblk > ws.hist_blocks) { set_error("radix sort: %d tiles exceed the histogram stride %d", nblk, ws.hist_blocks); return GSR_ERR_WORKSPACE; }
-    const int bits = key_bits - first_bit;
-    const int passes = (bits + 7) / 8;
-    const int bits_pp = (bits + passes - 1) / passes;
-    int cur = in_buf;
+    const int key_bits = plan.bits_x + plan.bits_y, bits_pp = plan.pair_bits_pp;
+    int cur = 0;
     const uint32_t *cnt_dev = n_dev;
-    for (int p = 0; p < passes; ++p) {
-        const int shift = first_bit + bits_pp * p;
-        const PassSpec ps = {shift, (1u << std::min(bits_pp, key_bits - shift)) - 1u, 0u, drop_from, -1, 0};
+    for (int p = 0; p < plan.pair_passes; ++p) {
+        const int shift = bits_pp * p;
+        const PassSpec ps = {shift, (1u << std::min(bits_pp, key_bits - shift)) - 1u, 0u, plan.drop_from, -1, 0};
         const bool first = p == 0;
-        if (pair_keys_16bit(key_bits))  // the keys lie in the first half of each pkey buffer, two bytes each (binning.hip writes them so)
+        if (plan.key16)  // the keys lie in the first half of each pkey buffer, two bytes each (binning.hip writes them so)
             launch_pass<PAIR_SORT_THREADS, PAIR_SORT_ITEMS, false, uint16_t>(reinterpret_cast<const uint16_t *>(ws.pkey[cur]), ws.pval[cur], nullptr,
                                                                             reinterpret_cast<uint16_t *>(ws.pkey[cur ^ 1]), ws.pval[cur ^ 1], nullptr, cnt_dev,
                                                                             ws.max_pairs, ps, first, false, first ? n_out : nullptr, ws, s);
