@@ -112,7 +112,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_count_kernel(const uint32_t
         if (t == 0) { ctrl_w->n_pairs = 0u; ctrl_w->ent_off = ent_off; }
     }
     for (uint32_t c = t; c < (uint32_t)n_tiles; c += stride) ranges[c] = make_uint2(0u, 0u);  // tile ranges are rebuilt every frame
-    const bool odd = (ctrl->sort_passes & 1u) != 0;
+    const bool odd = ctrl->sort_buf != 0;
     const uint32_t *sorted_ids = odd ? id_b : id_a, *sorted_rect8 = odd ? r8_b : r8_a;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t lim = n < draw_limit ? n : draw_limit;
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
     __shared__ float4 s_q1[EMIT_THREADS];
     __shared__ uint32_t s_fine[COARSE ? EMIT_THREADS : 1];  // coarse: the gaussian's packed TILE rect
     const uint32_t n = ctrl->n_visible;
-    const bool odd = (ctrl->sort_passes & 1u) != 0;
+    const bool odd = ctrl->sort_buf != 0;
     const uint32_t *sorted_ids = odd ? id_b : id_a, *sorted_rect8 = odd ? r8_b : r8_a;
     const int tid = threadIdx.x;
     // the grid is capped (launch_binning) and strides over the emit blocks the frame has: sized by the bound n >= V it launched more

@@ -20,7 +20,7 @@ struct FrameCtrl {
     uint32_t n_pairs;       // E  (pairs that survive footprint culling; written by tile-sort pass 0)
     uint32_t overflow;
     uint32_t max_list_len;
-    uint32_t sort_passes;   // depth-sort plan of this frame (sort.hip): passes it needs (1..4) — the sorted ids end up in val[sort_passes & 1]
+    uint32_t sort_passes;   // depth-sort plan of this frame (sort.hip): passes it needs (1..4) — the sorted ids end up in val[sort_buf]
     unsigned long long wave_entries;  // (quadrant, entry) pairs evaluated by the blend   } totals of blend_stats[], filled in
     unsigned long long fetched_entries;  // list entries staged by the blend              } by gsr_read_stats
     unsigned long long colour_evals;     // deferred colours evaluated by the blend       }
@@ -41,7 +41,8 @@ struct FrameCtrl {
     float col_cc[3];         // GsrCamera.cam_center
     int32_t col_degree;      // GsrScene.sh_degree
     int32_t col_sh16;        // GsrScene.sh_dtype
-    uint32_t _pad0;
+    uint32_t sort_buf;       // which of val[] / rect8[] the last depth-sort pass that RAN wrote: min(sort_passes, passes enqueued) & 1.
+                             // A frame short of passes (flagged, to be re-rendered) still hands binning a buffer this frame's sort filled
     uint32_t depth_key_max;  // maximum of the frame's valid depth keys (pass-0 histogram).  Cleared with the frame AND by the pass-0
                              // rowscan once consumed (gsr_bin_sort may be repeated on one gsr_preprocess).
     // ---- everything below survives the per-frame clear of a frame rendered with GsrOptions.keep_flags (and of the later views
@@ -217,7 +218,7 @@ int launch_rasterize_gaussian(int64_t g, const int64_t *bboxes, float *screen, c
                               const float *rgb, float *opacity_buffer, const float *opacity, int W, int H, hipStream_t s);
 
 // Depth order (sort.hip): stable LSD radix sort of the depth keys; leaves V in FrameCtrl.n_visible and the sorted ids (+ packed
-// rects) in val[p] / rect8[p], p = FrameCtrl.sort_passes & 1 (decided on the device from the frame's key range).
+// rects) in val[p] / rect8[p], p = FrameCtrl.sort_buf (decided on the device from the frame's key range).
 int launch_depth_sort(const Workspace &ws, const FramePlan &plan, hipStream_t s);
 // gsr_scene_order (sort.hip): Morton-curve permutation of the gaussians, built with the radix passes of the pair sort
 size_t scene_order_bytes(int64_t n);

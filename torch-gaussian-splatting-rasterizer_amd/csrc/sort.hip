@@ -23,7 +23,7 @@
 // pass-0 rowscan turns that into the plan for the remaining passes (FrameCtrl.sort_*): the B - 9 remaining bits split
 // evenly over as few passes of <= 9 bits as possible.  A scene whose depths span 0.2 .. 83 (B <= 27) sorts in 9 + 9 + 9;
 // the launch sequence is fixed at four passes (the host cannot know B without a sync) and the kernels of an unused pass
-// return at once.  Consumers find the sorted buffer from the plan (sort_passes & 1).
+// return at once.  Consumers find the sorted buffer from the plan (FrameCtrl.sort_buf).
 // Roofline: HBM.  Per pass per element: 4 B (hist) + 8..12 B read + 8..12 B written.
 #include <algorithm>
 #include "gsr_internal.h"
@@ -121,6 +121,9 @@ __global__ __launch_bounds__(256) void radix_rowscan_kernel(uint32_t *__restrict
         // counters otherwise describe its LAST view, whose own plan may fit)
         ctrl->batch_sort_passes = max(ctrl->batch_sort_passes, 1u + rest_passes);
         if (1u + rest_passes > (uint32_t)ps.enqueued) ctrl->batch_overflow |= 2u;  // the caller's bound was too small: the frame is wrong
+        // wrong, but harmless: binning reads the buffer the last pass that RUNS writes (a permutation of the visible ids, part sorted).
+        // By the plan's parity alone a bound of 1 under a 2- or 4-pass plan pointed it at val[0], which no pass of this frame writes
+        ctrl->sort_buf = min(1u + rest_passes, (uint32_t)ps.enqueued) & 1u;
         ctrl->sort_key_bits = bits;
         ctrl->sort_bits_rest = rest_passes ? (rest + rest_passes - 1) / rest_passes : 0u;
         ctrl->depth_key_max = 0u;  // consumed: a repeated gsr_bin_sort starts from 0 again (the frame clear zeroes it too)
@@ -286,7 +289,7 @@ static void launch_pass(const KeyT *kin, const uint32_t *vin, const uint32_t *v2
 
 // Depth order of the gaussians (rasterize.py:424-425).  plan.depth_passes radix passes are enqueued: four unless the caller bounds
 // them (GsrOptions.depth_sort_passes), 3 run on ordinary scenes (header); a frame that needs more than were enqueued is flagged.
-// Afterwards FrameCtrl.n_visible = V and the sorted ids / packed rects are in val[p] / rect8[p], p = sort_passes & 1.
+// Afterwards FrameCtrl.n_visible = V and the sorted ids / packed rects are in val[p] / rect8[p], p = FrameCtrl.sort_buf.
 template <int ITEMS>
 static int depth_sort_passes(const Workspace &ws, const FramePlan &plan, hipStream_t s)
 {
