@@ -25,7 +25,8 @@
 extern "C" {
 #endif
 
-#define GSR_VERSION 600 /* 0.6.0: several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+#define GSR_VERSION 600 /* 0.6.0 (additions since, no existing entry point or struct changed: gsr_blend_features / gsr_render_features —
+                            depth, alpha and caller-supplied channels composited with the colour frame's weights): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -254,6 +255,29 @@ int gsr_blend(const GsrScene *scene /* may be NULL */, int64_t n, const GsrCamer
 /* Stages 1-3 back to back: the whole render call of rasterize.py:354-446. */
 int gsr_render_forward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs,
                        void *workspace, size_t workspace_bytes, void *out_image, float *out_final_T, void *stream);
+
+/* Stage 3 for the caller's own per-gaussian values (no reference counterpart: rasterize.py composites the SH colour and nothing else):
+ * out_map[p][c] = sum_i w_i(p) features[i][c], c = 0..2, over the same depth-ordered lists and with the same weights w_i = alpha_i T_i
+ * as the colour frame — the arithmetic of gsr_blend with features[i] in the place of the colour, unclamped: with the gaussians' colours
+ * as features the map is gsr_blend's frame bit for bit.  Depth map: features[i] = z_cam; accumulated alpha: features[i] = 1 (then
+ * out = 1 - final T up to rounding).  features [n,3] float32 in the order of the scene arrays; finite values for every gaussian that
+ * can be drawn.  An alternative stage 3: needs gsr_preprocess and gsr_bin_sort on the workspace first, may be called any number of
+ * times (more than three channels: three at a time), and mixes freely with gsr_blend — it reads the records' geometry and opacity
+ * only, never their colour words, and leaves the launch-order hint of the colour frames alone, so a gsr_blend before or after it
+ * renders the bits it renders alone.  out_map: layout per opts->output_layout with 3 channels, float32; out_final_T may be NULL.
+ * Honoured options: reference_compat, tile_row_begin / _step / _block, output_layout, no_footprint_cull, draw_limit, fine_binning,
+ * depth_sort_passes, keep_flags, early_out_T.  A quadrant of 64 pixels stops once T <= early_out_T for all of them: with 0 (default) that
+ * is T == 0.0f, which is exact for finite features; the colour-saturation rule of gsr_blend rests on colours in [0, 1] and does not
+ * apply, so saturation_rule, blend_impl, blend_pipe_tiles, no_order_hint and colour_stage are ignored.  GSR_ERR_BAD_ARG for
+ * output_dtype = 1 and accum_dtype = 1 (the maps are float32).  Single views.  gsr_read_stats afterwards describes this blend
+ * (wave_entries, fetched_entries; colour_evals = 0). */
+int gsr_blend_features(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                       size_t workspace_bytes, const float *features /* [n,3] */, float *out_map, float *out_final_T, void *stream);
+
+/* Stages 1-3 back to back with the feature blend as stage 3.  The preprocess runs as with colour_stage = 0 whatever opts says: no SH
+ * row is read (scene->sh must still be a valid array: a later gsr_blend on this workspace evaluates colours from it). */
+int gsr_render_features(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                        size_t workspace_bytes, const float *features /* [n,3] */, float *out_map, float *out_final_T, void *stream);
 
 /* Several views of ONE resident scene (the reference renders one view per process, rasterize.py:315-329; BASELINE configs[3] is a
  * camera set).  cams[n_cams] [host] must share width/height; frame i goes to out_images + i * frame_stride (in elements of the

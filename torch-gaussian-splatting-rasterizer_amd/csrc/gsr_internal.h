@@ -232,6 +232,11 @@ int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan 
 // colours are evaluated from (single views only); nullptr = what the preprocess left in the workspace's control block
 int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, void *out_image,
                  size_t out_view_stride, float *out_T, const GsrScene *scene, hipStream_t s);
+// The blend's launch order (blend.hip, tile_order_kernel): returns the launch slots per view; use_hint: by what each tile staged last frame
+int launch_tile_order(const Workspace &ws, const FramePlan &plan, bool use_hint, hipStream_t s);
+// Stage 3 for caller-supplied channels (blend_features.hip): out_map[p] = sum_i w_i(p) features[i], single views only
+int launch_blend_features(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *features,
+                          float *out_map, float *out_T, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

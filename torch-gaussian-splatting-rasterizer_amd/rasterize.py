@@ -164,8 +164,9 @@ def load_view(input_dir: str, scene_index: int, scale_factor: int):
 
 
 def render_scene(input_dir: str, trained_model_path: str, scene_index: int = 0, scale_factor: int = 2, device: str = "cuda",
-                 reference_compat: bool = True, early_out_T: float = 0.0, scene_order: str = "morton") -> torch.Tensor:
-    """The render call of the reference (:327-446) as a function: returns the frame [H,W,3] float32 on `device`.
+                 reference_compat: bool = True, early_out_T: float = 0.0, scene_order: str = "morton", with_depth: bool = False):
+    """The render call of the reference (:327-446) as a function: returns the frame [H,W,3] float32 on `device`; with_depth=True:
+    (frame, depth [H,W], alpha [H,W]) — the gaussians' camera-space depth and 1 composited with the frame's weights (Rasterizer.render_rgbd).
     scene_order: "morton" (default) uploads the gaussians along a Morton curve of their means (~10 % faster frames), "file" keeps the
     .ply's order.  Same frame either way except where gaussians at EXACTLY equal depth overlap: those are drawn in storage order
     (the reference's torch.sort, :425, leaves them undefined; "file" is what its CPU sort does in practice)."""
@@ -175,7 +176,8 @@ def render_scene(input_dir: str, trained_model_path: str, scene_index: int = 0, 
     ply_path = os.path.join(trained_model_path, "point_cloud/iteration_30000/point_cloud.ply")
     logger.info("Fetching trained model from: %s", ply_path)
     scene = renderer.GaussianScene.from_ply(ply_path, device=device, spatial_order=scene_order == "morton")
-    return renderer.Rasterizer(scene).render(cam, renderer.make_options(reference_compat=reference_compat, early_out_T=early_out_T))
+    R, opts = renderer.Rasterizer(scene), renderer.make_options(reference_compat=reference_compat, early_out_T=early_out_T)
+    return R.render_rgbd(cam, opts) if with_depth else R.render(cam, opts)
 
 
 def _to_png_array(frame: torch.Tensor) -> np.ndarray:

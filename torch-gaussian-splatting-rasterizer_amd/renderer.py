@@ -454,6 +454,111 @@ class Rasterizer:
 
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "frame")
 
+    # -- feature, depth and alpha maps -----------------------------------------------------------------
+    def _feature_groups(self, features: torch.Tensor, scene_order: bool):
+        """[n, C] caller values -> ceil(C / 3) contiguous [n, 3] float32 arrays in the scene's order (the last zero-padded)."""
+        _require_cuda(features, "features")
+        if features.dim() != 2 or features.shape[0] != self.scene.n or features.shape[1] < 1 or features.dtype != torch.float32:
+            raise ValueError(f"features must be a float32 tensor of shape [{self.scene.n}, C >= 1], got {features.dtype} {tuple(features.shape)}")
+        if features.device != self.scene.device:
+            raise ValueError("features must live on the scene's device")
+        if not scene_order and self.scene.order_t is not None:
+            features = features.index_select(0, self.scene.order_t)
+        groups = []
+        for c0 in range(0, features.shape[1], 3):
+            g = features[:, c0:c0 + 3]
+            if g.shape[1] < 3:
+                g = torch.cat([g, torch.zeros((self.scene.n, 3 - g.shape[1]), dtype=torch.float32, device=self.scene.device)], 1)
+            if self.scene.n == 0:  # an empty tensor has no address; libgsr refuses a null array
+                g = torch.zeros((1, 3), dtype=torch.float32, device=self.scene.device)
+            groups.append(g.contiguous())
+        return groups
+
+    def _depth_features(self, cam: GsrCamera) -> torch.Tensor:
+        """[n, 3] = (z_cam, 1, 0) in the scene's order; z_cam = column 2 of gsr_project_to_camera_space for the camera's w2c."""
+        n, dev = self.scene.n, self.scene.device
+        f = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        if n:
+            pc = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            check(lib.gsr_project_to_camera_space(n, self.scene.t["means"].data_ptr(), cam.w2c, pc.data_ptr(), _stream_ptr(dev)))
+            f[:, 0] = pc[:, 2]
+            f[:, 1] = 1.0
+        return f
+
+    def _enqueue_maps(self, cam: GsrCamera, opts: GsrOptions, groups, want_T: bool, with_image: bool):
+        """One preprocess and one bin / sort, then (with_image) the colour blend and one feature blend per group of three channels,
+        on the current stream, unchecked like enqueue().  Returns (image or None, [maps], T or None)."""
+        ws = self._workspace(cam.width, cam.height)
+        shape, tshape = self._out_shape(cam, opts)
+        dev = self.scene.device
+        new = torch.zeros if opts.output_layout == 2 else torch.empty  # strips may include rows below the frame's last pixel row
+        maps = [new(shape, dtype=torch.float32, device=dev) for _ in groups]
+        T = torch.ones(tshape, dtype=torch.float32, device=dev) if want_T else None
+        img = new(shape, dtype=torch.bfloat16 if opts.output_dtype == 1 else torch.float32, device=dev) if with_image else None
+        if maps[0].numel() == 0:  # a shard that owns no tile row
+            self.unchecked.wrote(0)
+            return img, maps, T
+        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
+            opts = GsrOptions.from_buffer_copy(opts)
+            opts.keep_flags = 1
+        sc, sp = self.scene.c_struct(), _stream_ptr(dev)
+        n, mp, wp, wn = self.scene.n, self.max_pairs, ws.data_ptr(), ws.numel()
+        tptr = T.data_ptr() if want_T else None
+        rest = groups
+        if with_image:
+            fo = GsrOptions.from_buffer_copy(opts)  # the maps are float32 whatever the frame is stored as
+            fo.output_dtype = 0
+            check(lib.gsr_preprocess(C.byref(sc), C.byref(cam), C.byref(opts), wp, wn, None, sp))
+            check(lib.gsr_bin_sort(n, C.byref(cam), C.byref(opts), mp, wp, wn, sp))
+            check(lib.gsr_blend(C.byref(sc), n, C.byref(cam), C.byref(opts), mp, wp, wn, img.data_ptr(), None, sp))
+            opts = fo
+        else:
+            check(lib.gsr_render_features(C.byref(sc), C.byref(cam), C.byref(opts), mp, wp, wn, groups[0].data_ptr(), maps[0].data_ptr(), tptr, sp))
+            rest, tptr = groups[1:], None
+        for g, m in zip(rest, maps[len(maps) - len(rest):]):
+            check(lib.gsr_blend_features(n, C.byref(cam), C.byref(opts), mp, wp, wn, g.data_ptr(), m.data_ptr(), tptr, sp))
+            tptr = None  # every group ends with the same T: one store is enough
+        self.unchecked.wrote(1)
+        return img, maps, T
+
+    def render_features(self, cam: GsrCamera, features: torch.Tensor, opts: Optional[GsrOptions] = None, return_T: bool = False,
+                        scene_order: bool = False):
+        """Composite the caller's per-gaussian values with the colour frame's weights: out[p] = sum_i w_i(p) features[i], w_i = alpha_i T_i
+        over the same depth-ordered lists (gsr_render_features / gsr_blend_features).  features: [n, C] float32 on the scene's device,
+        C >= 1, indexed like the file the scene was loaded from (scene_order=True: like the scene's resident arrays).  Returns
+        [H, W, C] (layouts as render()), and the final transmittance [H, W] with return_T.  One preprocess and one bin / sort, then
+        ceil(C / 3) blends; checked and re-rendered on overflow like render().  Values are not clamped; they must be finite."""
+        groups = self._feature_groups(features, scene_order)
+        n_ch = int(features.shape[1])
+
+        def attempt(o):
+            _, maps, T = self._enqueue_maps(cam, o, groups, return_T, False)
+            out = maps[0] if len(maps) == 1 else torch.cat(maps, -1)
+            out = out if out.shape[-1] == n_ch else out[..., :n_ch].contiguous()
+            return (out, T) if return_T else out
+
+        return _render_checked([self], [None], opts or make_options(), attempt, 8, "feature map")
+
+    def render_depth(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, normalize: bool = False):
+        """(depth [H, W], alpha [H, W]): depth = sum_i w_i z_i with z = the gaussians' camera-space depth, alpha = sum_i w_i (= 1 - final T
+        up to rounding).  normalize=True divides depth by alpha where alpha > 0 (the expected depth of what was hit), 0 elsewhere."""
+        m = self.render_features(cam, self._depth_features(cam), opts, scene_order=True)
+        depth, alpha = m[..., 0].contiguous(), m[..., 1].contiguous()
+        if normalize:
+            depth = torch.where(alpha > 0, depth / alpha, torch.zeros_like(depth))
+        return depth, alpha
+
+    def render_rgbd(self, cam: GsrCamera, opts: Optional[GsrOptions] = None):
+        """(image, depth, alpha): render()'s frame, bit for bit, and render_depth()'s maps from ONE preprocess and ONE bin / sort — the
+        colour blend and the feature blend run on the same lists."""
+        groups = self._feature_groups(self._depth_features(cam), True)
+
+        def attempt(o):
+            img, maps, _ = self._enqueue_maps(cam, o, groups, False, True)
+            return img, maps[0][..., 0].contiguous(), maps[0][..., 1].contiguous()
+
+        return _render_checked([self], [None], opts or make_options(), attempt, 8, "frame")
+
     def _batch_out(self, cams, opts: GsrOptions, out: Optional[torch.Tensor]):
         """(out, frame_stride in elements) of a batch: whole frames [B,H,W,3], or with a tile-row shard (output_layout = 2) the
         strips [B,rows*16,W,3]."""
