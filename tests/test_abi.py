@@ -112,13 +112,22 @@ def test_product_never_touches_the_oracle():
 
 
 def test_the_blend_walk_in_the_source_is_what_its_generator_prints():
-    """csrc/blend.hip carries ~290 lines of generated asm (the survivor walk); tools/gen_blend_walk.py is their source of truth."""
+    """The two survivor walks (~285 and ~340 lines of asm, each a complete statement with its operand and clobber lists) live in
+    csrc/blend_walk2.inc and csrc/blend_walk1p.inc; tools/gen_blend_walk.py is their source of truth.  Both committed files are what
+    the generator prints, byte for byte; blend.hip includes both and carries no instruction of a walk itself."""
     import subprocess
     import sys
 
-    out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "gen_blend_walk.py")], capture_output=True, text=True, check=True).stdout
-    src = open(os.path.join(REPO, "torch-gaussian-splatting-rasterizer_amd", "csrc", "blend.hip")).read()
-    assert out.rstrip("\n") in src
+    csrc = os.path.join(REPO, "torch-gaussian-splatting-rasterizer_amd", "csrc")
+    src = open(os.path.join(csrc, "blend.hip")).read()
+    for name, inc in (("two_quadrants", "blend_walk2.inc"), ("pipelined", "blend_walk1p.inc")):
+        out = subprocess.run([sys.executable, os.path.join(REPO, "tools", "gen_blend_walk.py"), name], capture_output=True, check=True).stdout
+        assert out == open(os.path.join(csrc, inc), "rb").read(), inc
+        assert out.count(b"v_cmpx_") >= 8 and out.rstrip().endswith(b");"), inc
+        assert src.count(f'#include "{inc}"') == 1, inc
+    code = re.sub(r"//.*", "", src)
+    for word in ("v_cmpx_", "v_exp_f32", "ds_read_b128", "s_bitset0_b64"):
+        assert word not in code, word
 
 
 def test_the_library_reads_no_environment_and_keeps_no_function_statics():

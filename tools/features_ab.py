@@ -3,7 +3,7 @@
 process (MI355X guide, rule 24).  Stages 1-2 run once (colour_stage = 1: every record carries its colour), then per round:
   A  gsr_blend with blend_impl = 1, saturation_rule = 1: blend_kernel, the plain-C kernel — same entries, same T == 0 stop rule,
      same blend_one, colours read from the record
-  B  gsr_blend_features with features (z_cam, 1, 0): blend_features_kernel
+  B  gsr_blend_features with features (z_cam, 1, 0): the same kernel under the feature policy
 each between two events — median and min over rounds, the spread, B / A, and the two blends' counters (they must agree).
 Then whole calls, synchronised: Rasterizer.render against render_depth and render_rgbd in ms per frame.
 usage: tools/features_ab.py [--workload bicycle] [--rounds 15] [--early-out-T 0]"""
@@ -72,7 +72,7 @@ def main():
                 stats[name] = R.stats()
     print(f"{a.workload}: {n} gaussians, {W}x{H}, {a.rounds} interleaved rounds (blend stage alone, tile-order kernel included)")
     med = {}
-    for name, what in (("A", "gsr_blend, blend_impl=1 saturation_rule=1 (blend_kernel)"), ("B", "gsr_blend_features (blend_features_kernel)")):
+    for name, what in (("A", "gsr_blend, blend_impl=1 saturation_rule=1 (blend_kernel)"), ("B", "gsr_blend_features (blend_kernel<FeatureBlend>)")):
         t = np.array(times[name])
         med[name] = float(np.median(t))
         print(f"  {name}: median {np.median(t):.4f} ms  min {t.min():.4f} ms  max {t.max():.4f} ms  spread (max - min) / median {(t.max() - t.min()) / np.median(t) * 100:.1f} %"

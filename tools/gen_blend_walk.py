@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
-"""Prints the asm text of the blend kernel's survivor walk (blend_walk2_asm in csrc/blend.hip).  The kernel source carries the
-output verbatim; this script documents how it was produced.
+"""Generates the blend kernel's two survivor walks as complete `asm volatile( ... );` statements: csrc/blend_walk2.inc (the body of
+blend_walk2_asm in csrc/blend.hip) and csrc/blend_walk1p.inc (blend_walk1p_asm).  blend.hip and tools/walk_latency.hip #include the
+committed files; the statements name their C operands by the wrappers' parameter names, and PLANE.
+
+    python tools/gen_blend_walk.py two_quadrants | pipelined     print one statement
+    python tools/gen_blend_walk.py --write                       refresh both files (tests/test_abi.py compares them with the output)
 
 Two quadrants (a 16x8 half-tile) per wave, a lane = two pixels 8 columns apart.  Records roll through two register sets; one
 set of LDS reads per record serves both quadrants, and so do dy, C*dy and t1 = fma(C dy, dy, L) of the quadratic; which
 quadrants a record is evaluated on comes from the masks %[ma] / %[mb], guarded or not from %[fa] / %[fb].
 Registers: v40/v41 LDS addresses, then temporaries; set A = v42..v51, set B = v52..v61; v39/v62/v63 temporaries."""
 import itertools
+import re
 
 label = itertools.count(10)
 MAXA, MINA = "0x3f7d70a4", "0x3b808081"  # 0.99f, 1/255
@@ -123,8 +128,50 @@ def pipelined():
     return L
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# The statements.  An asm statement takes at most 30 operands, so the walks name their VGPRs outright; the clobber list is every
+# VGPR the text names, read back from the text itself.
+OPERANDS = {
+    "two_quadrants": (
+        '[Ta] "+v"(Ta), [Cra] "+v"(Cra), [Cga] "+v"(Cga), [Cba] "+v"(Cba), [Tb] "+v"(Tb), [Crb] "+v"(Crb), [Cgb] "+v"(Cgb),\n'
+        '          [Cbb] "+v"(Cbb), [m] "+s"(m), [ia] "=&s"(ia), [ib] "=&s"(ib)',
+        '[base] "v"(lds_chunk), [fpxa] "v"(fpxa), [fpxb] "v"(fpxb), [fpy] "v"(fpy), [ma] "s"(ma), [mb] "s"(mb), [fa] "s"(fa), [fb] "s"(fb),\n'
+        '          [p1] "i"(PLANE), [p2] "i"(2 * PLANE)'),
+    "pipelined": (
+        '[T] "+v"(T), [Cr] "+v"(Cr), [Cg] "+v"(Cg), [Cb] "+v"(Cb), [m] "+s"(m), [ia] "=&s"(ia), [ib] "=&s"(ib), [ic] "=&s"(ic)',
+        '[base] "v"(lds_chunk), [fpx] "v"(fpx), [fpy] "v"(fpy), [fa] "s"(fa), [p1] "i"(PLANE), [p2] "i"(2 * PLANE)'),
+}
+FILES = {"two_quadrants": "blend_walk2.inc", "pipelined": "blend_walk1p.inc"}
+
+
+def named_vgprs(lines):
+    regs = set()
+    for lo, hi in re.findall(r"\bv\[(\d+):(\d+)\]", "\n".join(lines)):
+        regs.update(range(int(lo), int(hi) + 1))
+    regs.update(int(r) for r in re.findall(r"\bv(\d+)\b", "\n".join(lines)))
+    return sorted(regs)
+
+
+def statement(name):
+    lines = {"two_quadrants": two_quadrants, "pipelined": pipelined}[name]()
+    outs, ins = OPERANDS[name]
+    clobbers = ['"vcc"', '"scc"', '"memory"'] + ['"v%d"' % r for r in named_vgprs(lines)]
+    rows = [", ".join(clobbers[i:i + 16]) for i in range(0, len(clobbers), 16)]
+    head = "    // generated by tools/gen_blend_walk.py %s -- do not edit\n    asm volatile(\n" % name
+    text = "\n".join('        "%s\\n\\t"' % l for l in lines)
+    return head + text + "\n        : " + outs + "\n        : " + ins + "\n        : " + ",\n          ".join(rows) + ");\n"
+
+
 if __name__ == "__main__":
+    import os
     import sys
 
-    lines = pipelined() if len(sys.argv) > 1 and sys.argv[1] == "pipelined" else two_quadrants()
-    print("\n".join('        "%s\\n\\t"' % l for l in lines))
+    if sys.argv[1:] == ["--write"]:
+        csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "torch-gaussian-splatting-rasterizer_amd", "csrc")
+        for name, f in FILES.items():
+            with open(os.path.join(csrc, f), "w") as fh:
+                fh.write(statement(name))
+    elif len(sys.argv) == 2 and sys.argv[1] in FILES:
+        sys.stdout.write(statement(sys.argv[1]))
+    else:
+        sys.exit(__doc__)

@@ -94,16 +94,60 @@ __device__ __forceinline__ float bf16_round(float x)
 __device__ __forceinline__ void store_rgb(const BlendArgs &a, size_t o, float r, float g, float b)
 {
     if (a.out_bf16) {
-        auto bf = [](float x) {
-            const uint32_t u = __float_as_uint(x);
-            return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-        };
+        auto bf = [](float x) { return (unsigned short)(__float_as_uint(bf16_round(x)) >> 16); };
         unsigned short *p = static_cast<unsigned short *>(a.out) + o;
         p[0] = bf(r); p[1] = bf(g); p[2] = bf(b);
     } else {
         float *p = static_cast<float *>(a.out) + o;
         p[0] = r; p[1] = g; p[2] = b;
     }
+}
+
+// Where pixel (x, y) of tile row ty lies in the frame, in pixels: the colour is at 3 * that, the final T at it.
+__device__ __forceinline__ size_t frame_pixel(const BlendArgs &a, int ty, int x, int y)
+{
+    return a.layout == 0 ? (size_t)y * a.W + x                                          // image [H,W,3]
+         : a.layout == 1 ? (size_t)x * a.H + y                                          // screen [W,H,3]
+                         : (size_t)(a.rs.index_of(ty) * 16 + (y - ty * 16)) * a.W + x;  // strip
+}
+
+// One finished pixel into the frame and, where asked for, the final T map.
+__device__ __forceinline__ void store_pixel(const BlendArgs &a, int ty, int x, int y, float T, float Cr, float Cg, float Cb)
+{
+    if (x < a.W && y < a.H) {
+        const bool drawn = x < a.xlim && y < a.ylim;  // Q1: last column / row stay black, T stays 1
+        const size_t pix = frame_pixel(a, ty, x, y);
+        store_rgb(a, pix * 3, drawn ? Cr : 0.0f, drawn ? Cg : 0.0f, drawn ? Cb : 0.0f);
+        if (a.out_T) a.out_T[pix] = drawn ? T : 1.0f;
+    }
+}
+
+// Host: the arguments every blend launch fills the same way.  What is left zero differs between them: tile_work, sat_scale,
+// out_bf16, col_*, the view strides.
+inline BlendArgs blend_args_common(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, void *out,
+                                   float *out_T)
+{
+    BlendArgs a = {};
+    a.ranges = ws.ranges;
+    a.cranges = ws.cranges;
+    a.ctiles_x = ws.ctiles_x;
+    a.cell_lists = plan.cell_lists ? 1 : 0;
+    a.pval = ws.pval[plan.lists_buf];
+    a.rec = ws.rec;
+    a.ctrl = ws.ctrl;
+    a.out = out;
+    a.out_T = out_T;
+    a.stats = ws.blend_stats;
+    a.order = ws.tile_order;
+    a.W = cam.width; a.H = cam.height;
+    a.xlim = opts.reference_compat ? cam.width - 1 : cam.width;
+    a.ylim = opts.reference_compat ? cam.height - 1 : cam.height;
+    a.tiles_x = ws.tiles_x;
+    a.rs = plan.rs;
+    a.rows = plan.rows;
+    a.layout = opts.output_layout;
+    a.early_T = opts.early_out_T;
+    return a;
 }
 
 }  // namespace gsr

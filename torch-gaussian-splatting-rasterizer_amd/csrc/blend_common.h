@@ -1,8 +1,14 @@
 // blend_common.h — what every blend kernel shares (blend.hip: the colour frame; blend_features.hip: caller-supplied channels):
-// the per-(pixel, entry) arithmetic and the staging of a tile's depth-ordered list.
+// the per-(pixel, entry) arithmetic, the staging of a tile's depth-ordered list, and the skeleton of a tile's workgroup — prologue
+// (tile_of_slot, empty_slot, tile_coords), batch loop (batches_begin, next_batch), stat words (blend_stats_out); the pixel store is blend_args.h's store_pixel.
+// blend_kernel, at the end, is the plain-C blend built from them, one instantiation per policy: the colour frame's
+// (blend.hip, ColourBlend) and the feature maps' (blend_features.hip, FeatureBlend).  blend.hip's blend_walk_kernel, the product,
+// takes prologue, stat words and pixel store from here and spells the batch loop out around its hand-scheduled walk (its comment
+// says why).
 #pragma once
 #include "gsr_internal.h"
 #include "blend_args.h"
+#include "footprint.h"
 
 namespace gsr {
 
@@ -107,6 +113,186 @@ __device__ __forceinline__ int tile_list_next(const BlendArgs &a, TileList<THREA
     t.head += nb;
     t.qlen -= nb;
     return nb;
+}
+
+// ---- the skeleton of a tile's workgroup ------------------------------------------------------------------------------------------
+// Every blend kernel: THREADS = 256 / QPW threads per 16x16 tile, a wave QPW of its 8x8 quadrants, a lane one pixel of each.
+// The kernels pass their own tid / lane / wave in: re-deriving them here from threadIdx.x (unsigned) compiles to other code.
+// The workgroup's LDS: each kernel declares the arrays as __shared__ variables of its own and hands their addresses over.
+struct BlendLds {
+    float4 *s0, *s1, *s2;   // staged records, one plane of THREADS entries per 16-B part: q0, q1, q2 (or what stands in for it)
+    uint32_t *ring, *wc;    // TileList<THREADS>::RING and 2 * WAVES words (tile_list_next)
+    int *done;              // waves that have finished
+    uint32_t *col;          // the workgroup's deferred-colour evaluations (COLOUR kernels only)
+};
+
+struct TilePixel {
+    int tile, tx, ty;
+    int qx, qy;      // first pixel of the wave's quadrant (QPW = 2: of the left one)
+    int px, py;      // the lane's pixel (QPW = 2: and (px + 8, py))
+    uint32_t *stat;  // the launch slot's BLEND_STAT_WORDS counters
+};
+
+// Prologue: t = tile_of_slot(a); if (t.tile < 0) return empty_slot(t, tid); tile_coords<QPW>(a, lane, wave, t).  The branch stays
+// in the kernel: as a helper's return value it compiles to a flag that is tested again, and the product kernels spill.
+__device__ __forceinline__ TilePixel tile_of_slot(const BlendArgs &a)
+{
+    TilePixel t;
+    t.tile = a.order[blockIdx.x];
+    t.stat = a.stats + (size_t)blockIdx.x * BLEND_STAT_WORDS;
+    return t;
+}
+
+__device__ __forceinline__ void empty_slot(const TilePixel &t, int tid)
+{
+    if (tid < BLEND_STAT_WORDS) t.stat[tid] = 0;
+}
+
+template <int QPW>
+__device__ __forceinline__ void tile_coords(const BlendArgs &a, int lane, int wave, TilePixel &t)
+{
+    t.ty = t.tile / a.tiles_x; t.tx = t.tile - t.ty * a.tiles_x;
+    t.qx = t.tx * 16 + (QPW == 1 ? (wave & 1) * 8 : 0); t.qy = t.ty * 16 + (QPW == 1 ? wave >> 1 : wave) * 8;
+    t.px = t.qx + (lane & 7); t.py = t.qy + (lane >> 3);
+}
+
+// The batch loop: list = batches_begin(...); while (const int nb = next_batch(..., fetched, stage)) { consume nb staged entries }.
+// next_batch stages the tile's list THREADS entries at a time — q0 and q1 of entry `id` from its record, the third plane from
+// stage(id) — counts them in `fetched` (workgroup-uniform) and returns the batch's size, or 0 once the list has ended or every wave
+// has called wave_finished.  The consuming side stays in the kernel's body: as a callable that captures the accumulators, the
+// compiler sinks blend_one's `T - w` below the survivor loop's two arms, away from the multiply it contracts with into
+// fma(-T, alpha, T), and the plain kernel's frames are no longer the asm walks' bit for bit.
+template <int THREADS, bool COLOUR>
+__device__ __forceinline__ TileList<THREADS> batches_begin(const BlendArgs &a, const TilePixel &t, int tid, const BlendLds &lds)
+{
+    if (tid == 0) { *lds.done = 0; if (COLOUR) *lds.col = 0; }
+    return tile_list_of<THREADS>(a, t.tile, t.tx, t.ty);
+}
+
+template <int THREADS, class Stage>
+__device__ __forceinline__ int next_batch(const BlendArgs &a, TileList<THREADS> &list, int tid, const BlendLds &lds, uint32_t &fetched,
+                                          Stage stage)
+{
+    for (;;) {
+        __syncthreads();  // previous batch fully consumed (and *lds.done initialised); a refilled ring published
+        if (*lds.done == THREADS / 64) return 0;  // uniform: every wave saturated
+        uint32_t id = 0;
+        const int nb = tile_list_next<THREADS>(a, list, lds.ring, lds.wc, &id);
+        if (nb < 0) continue;
+        if (nb == 0) return 0;
+        fetched += (uint32_t)nb;
+        if (tid < nb) {
+            const GaussRec *r = a.rec + id;
+            lds.s0[tid] = r->q0;
+            lds.s1[tid] = r->q1;
+            lds.s2[tid] = stage(id);
+        }
+        __syncthreads();
+        return nb;
+    }
+}
+
+// A wave that has finished says so, once.
+__device__ __forceinline__ void wave_finished(const BlendLds &lds, int lane)
+{
+    if (lane == 0) atomicAdd(lds.done, 1);
+}
+
+// Epilogue, every thread: the counters gsr_read_stats totals.  COLOUR, the colour frame's kernels: stat[5] = the workgroup's
+// deferred-colour evaluations (wave totals into LDS, one store), and tile_work = next frame's launch-order hint.  The feature
+// blend evaluates no colour and leaves tile_work what the last colour blend left.
+template <int THREADS, bool COLOUR>
+__device__ __forceinline__ void blend_stats_out(const BlendArgs &a, const TilePixel &t, int tid, int lane, int wave, const BlendLds &lds,
+                                                uint32_t evaluated, uint32_t fetched, uint32_t col_evals)
+{
+    if (lane == 0) {
+        t.stat[wave] = evaluated;
+        if (THREADS == 128) t.stat[2 + wave] = 0;
+    }
+    if (COLOUR) {
+        if (tid == 0) { t.stat[4] = fetched; a.tile_work[t.tile] = fetched + 1u; }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) col_evals += (uint32_t)__shfl_xor((int)col_evals, d, 64);
+        if (lane == 0 && col_evals) atomicAdd(lds.col, col_evals);
+        __syncthreads();
+        if (tid == 0) t.stat[5] = *lds.col;
+    } else if (tid == 0) {
+        t.stat[4] = fetched; t.stat[5] = 0;
+    }
+}
+
+// The plain-C statement of the blend: one 256-thread workgroup per tile, wave = 8x8 quadrant, lane = pixel.  The policy P says
+//   - stage(a, id, evals): the third LDS plane of gaussian `id`, {log2 opacity, c0, c1, c2};
+//   - acc_round(T, C0, C1, C2): what happens to the accumulators after every entry;
+//   - finished(a, T, C0, C1, C2, undrawn): has this pixel stopped changing?
+//   - COLOUR (blend_stats_out), MIN_WAVES (per SIMD, for the register allocator).
+template <class P>
+__global__ __launch_bounds__(256, P::MIN_WAVES) void blend_kernel(BlendArgs args, const P policy)
+{
+    const BlendArgs a = blend_args_of_view(args);
+    __shared__ float4 srec[3][256];
+    __shared__ int s_done;
+    __shared__ uint32_t s_col;
+    __shared__ uint32_t s_ring[TileList<256>::RING], s_wc[2 * TileList<256>::WAVES];
+    const BlendLds lds = {srec[0], srec[1], srec[2], s_ring, s_wc, &s_done, &s_col};
+    const float4 *const s0 = srec[0], *const s1 = srec[1], *const s2 = srec[2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    TilePixel t = tile_of_slot(a);
+    if (t.tile < 0) return empty_slot(t, tid);  // uniform
+    tile_coords<1>(a, lane, wave, t);
+    const float fpx = (float)t.px, fpy = (float)t.py;
+    const float qx0 = (float)t.qx, qx1 = (float)(t.qx + 7), qy0 = (float)t.qy, qy1 = (float)(t.qy + 7);
+
+    float T = 1.0f, C0 = 0.0f, C1 = 0.0f, C2 = 0.0f;
+    const bool undrawn = a.sat_scale != 0.0f && !(t.px < a.xlim && t.py < a.ylim);  // never stored: finished from the start
+    uint32_t evaluated = 0;  // wave-uniform
+    uint32_t col_evals = 0;  // per thread: deferred colours this thread evaluated while staging
+
+    auto stage = [&](uint32_t id) __attribute__((always_inline)) { return policy.stage(a, id, col_evals); };
+    bool wave_done = false;
+    uint32_t fetched = 0;  // workgroup-uniform
+    TileList<256> list = batches_begin<256, P::COLOUR>(a, t, tid, lds);
+    while (const int nb = next_batch<256>(a, list, tid, lds, fetched, stage)) {
+        if (wave_done) continue;
+        for (int chunk = 0; chunk < nb; chunk += 64) {
+            const int e = chunk + lane;
+            const bool hit = e < nb && footprint_hits_rect(s0[e], s1[e], qx0, qx1, qy0, qy1);
+            unsigned long long m = __ballot(hit);
+            evaluated += (uint32_t)__popcll(m);
+            // two survivors per trip so that the second one's LDS reads overlap the first one's arithmetic
+            while (m) {
+                const int k0 = chunk + (__ffsll((long long)m) - 1);
+                m &= m - 1;
+                const float2 ga = *reinterpret_cast<const float2 *>(&s0[k0]);  // wave-uniform address: LDS broadcast
+                const float4 ca = s1[k0];
+                const float4 oa = s2[k0];
+                asm volatile("" ::"v"(ca.w));  // keep the read a ds_read_b128 (4 LDS cycles); a b96 costs 8
+                if (m) {
+                    const int k1 = chunk + (__ffsll((long long)m) - 1);
+                    m &= m - 1;
+                    const float2 gb = *reinterpret_cast<const float2 *>(&s0[k1]);
+                    const float4 cb = s1[k1];
+                    const float4 ob = s2[k1];
+                    asm volatile("" ::"v"(cb.w));
+                    blend_one(ga, ca, oa, fpx, fpy, T, C0, C1, C2);
+                    policy.acc_round(T, C0, C1, C2);
+                    blend_one(gb, cb, ob, fpx, fpy, T, C0, C1, C2);
+                    policy.acc_round(T, C0, C1, C2);
+                } else {
+                    blend_one(ga, ca, oa, fpx, fpy, T, C0, C1, C2);
+                    policy.acc_round(T, C0, C1, C2);
+                }
+            }
+            if (__all(policy.finished(a, T, C0, C1, C2, undrawn))) {
+                wave_done = true;
+                wave_finished(lds, lane);
+                break;
+            }
+        }
+    }
+
+    blend_stats_out<256, P::COLOUR>(a, t, tid, lane, wave, lds, evaluated, fetched, col_evals);
+    store_pixel(a, t.ty, t.px, t.py, T, C0, C1, C2);
 }
 
 }  // namespace gsr

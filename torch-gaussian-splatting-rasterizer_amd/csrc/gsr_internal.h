@@ -170,8 +170,8 @@ inline RowShard row_shard_of(const GsrOptions &o)
 // Every host-side choice a frame makes: which kernel variants run and which buffer each stage leaves its result in.  Decided once per
 // entry point by plan_frame (api.hip), where the reasons stand; the launchers below read their choices from it and derive none.
 enum class BlendKernel {
-    Tile,       // blend_kernel<false>: one workgroup per tile, fp32 accumulators (GsrOptions.blend_impl = 1)
-    TileBf16,   // blend_kernel<true>: the same with bf16 accumulators (GsrOptions.accum_dtype = 1)
+    Tile,       // blend_kernel<ColourBlend<false>>: one workgroup per tile, fp32 accumulators (GsrOptions.blend_impl = 1)
+    TileBf16,   // blend_kernel<ColourBlend<true>>: the same with bf16 accumulators (GsrOptions.accum_dtype = 1)
     Walk2,      // blend_walk_kernel<2, false>: two quadrants per wave
     Walk1,      // blend_walk_kernel<1, false>: one quadrant per wave
     Walk1Pipe,  // blend_walk_kernel<1, true>: one quadrant per wave, pipelined
