@@ -26,7 +26,8 @@ extern "C" {
 #endif
 
 #define GSR_VERSION 600 /* 0.6.0 (additions since, no existing entry point or struct changed: gsr_blend_features / gsr_render_features —
-                            depth, alpha and caller-supplied channels composited with the colour frame's weights): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            depth, alpha and caller-supplied channels composited with the colour frame's weights; gsr_blend_channels /
+                            gsr_render_channels + GSR_MAX_FEATURE_CHANNELS — any number of channels, rows at a caller's stride, many channels per walk of the lists): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -278,6 +279,30 @@ int gsr_blend_features(int64_t n, const GsrCamera *cam, const GsrOptions *opts, 
  * row is read (scene->sh must still be a valid array: a later gsr_blend on this workspace evaluates colours from it). */
 int gsr_render_features(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                         size_t workspace_bytes, const float *features /* [n,3] */, float *out_map, float *out_final_T, void *stream);
+
+/* gsr_blend_features for 1 <= channels <= GSR_MAX_FEATURE_CHANNELS channels, read where the caller keeps them:
+ * out_map[p][c] = sum_i w_i(p) features[i * feature_stride + c], c = 0 .. channels - 1.  One walk of the tile lists composites up to 16
+ * channels (the geometry of a (pixel, gaussian) evaluation is paid once per walk, not once per three channels); more channels are
+ * further walks inside this one call, on the caller's stream.  Every channel is, bit for bit and at any early_out_T, the channel
+ * gsr_blend_features composites from the same values, and gsr_read_stats afterwards describes one walk (every walk stages and
+ * evaluates the same entries: wave_entries and fetched_entries are gsr_blend_features').  features: float32, any 4-byte-aligned
+ * address, rows feature_stride >= channels floats apart (a column window of a wider array needs no copy; rows on 16-byte boundaries
+ * are read with 16-byte loads); finite values for every gaussian that can be drawn.  out_map: layout per opts->output_layout with
+ * `channels` channels, float32, contiguous; out_final_T may be NULL.  Semantics, honoured and ignored options, and what it leaves alone
+ * on the workspace (the records' colour words, the launch-order hint) are gsr_blend_features'.  GSR_ERR_BAD_ARG, before any HIP call
+ * or look at the workspace, for a null camera, options, features or output map, channels < 1 or > GSR_MAX_FEATURE_CHANNELS,
+ * feature_stride < channels, output_dtype = 1, accum_dtype = 1.  Single views. */
+#define GSR_MAX_FEATURE_CHANNELS 1024
+int gsr_blend_channels(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                       size_t workspace_bytes, const float *features /* row i at features + i * feature_stride */,
+                       int32_t channels, int64_t feature_stride, float *out_map /* [.., channels] */, float *out_final_T,
+                       void *stream);
+
+/* Stages 1-3 back to back with gsr_blend_channels as stage 3; the preprocess runs as with colour_stage = 0, like gsr_render_features'. */
+int gsr_render_channels(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                        size_t workspace_bytes, const float *features /* row i at features + i * feature_stride */,
+                        int32_t channels, int64_t feature_stride, float *out_map /* [.., channels] */, float *out_final_T,
+                        void *stream);
 
 /* Several views of ONE resident scene (the reference renders one view per process, rasterize.py:315-329; BASELINE configs[3] is a
  * camera set).  cams[n_cams] [host] must share width/height; frame i goes to out_images + i * frame_stride (in elements of the

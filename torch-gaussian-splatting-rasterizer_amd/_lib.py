@@ -28,6 +28,7 @@ GSR_MAX_GAUSSIANS = 0x7FFFFFFF
 GSR_MAX_FRAME_SIDE = 65535 * 16
 GSR_MAX_BATCH_VIEWS = 8
 GSR_BOUNDS_BLOCK = 64
+GSR_MAX_FEATURE_CHANNELS = 1024  # gsr_blend_channels / gsr_render_channels
 
 
 class GsrError(RuntimeError):
@@ -126,7 +127,7 @@ EXPORTS = [
     "gsr_version", "gsr_last_error", "gsr_default_options", "gsr_camera_setup", "gsr_workspace_bytes",
     "gsr_preprocess", "gsr_bin_sort", "gsr_blend", "gsr_render_forward", "gsr_read_stats", "gsr_sh_to_rgb", "gsr_cov3d",
     "gsr_render_batch", "gsr_render_batch_slots", "gsr_scene_order", "gsr_scene_order_bytes", "gsr_scene_bounds", "gsr_block_visibility", "gsr_project_to_camera_space", "gsr_compute_2d_covariance", "gsr_compute_covering_bbox", "gsr_rasterize_gaussian",
-    "gsr_blend_features", "gsr_render_features",
+    "gsr_blend_features", "gsr_render_features", "gsr_blend_channels", "gsr_render_channels",
 ]
 
 
@@ -153,6 +154,8 @@ def _load() -> C.CDLL:
     L.gsr_blend.argtypes = [C.POINTER(GsrScene), i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
     L.gsr_blend_features.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp]
     L.gsr_render_features.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp]
+    L.gsr_blend_channels.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp]
+    L.gsr_render_channels.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp]
     L.gsr_render_forward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
     L.gsr_render_batch.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, vp, sz, vp, i64, vp]
     L.gsr_render_batch_slots.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, C.POINTER(vp), sz,

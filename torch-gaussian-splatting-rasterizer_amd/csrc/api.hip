@@ -445,6 +445,59 @@ int gsr_render_features(const GsrScene *scene, const GsrCamera *cam, const GsrOp
     return launch_blend_features(*cam, o, ws, plan, features, out_map, out_final_T, s);
 }
 
+// What gsr_blend_channels / gsr_render_channels refuse before anything else (and before any HIP call)
+static int check_channels(const GsrCamera *cam, const GsrOptions *opts, const float *features, int32_t channels, int64_t feature_stride,
+                          const float *out_map)
+{
+    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    if (!features) { set_error("null features"); return GSR_ERR_BAD_ARG; }
+    if (!out_map) { set_error("null output map"); return GSR_ERR_BAD_ARG; }
+    if (channels < 1 || channels > GSR_MAX_FEATURE_CHANNELS) {
+        set_error("bad channels %d (1 .. %d)", channels, GSR_MAX_FEATURE_CHANNELS); return GSR_ERR_BAD_ARG;
+    }
+    if (feature_stride < channels) {
+        set_error("bad feature_stride %lld: rows of %d channels overlap", (long long)feature_stride, channels); return GSR_ERR_BAD_ARG;
+    }
+    if (opts->output_dtype == 1) { set_error("feature maps are float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("feature maps are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+int gsr_blend_channels(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
+                       const float *features, int32_t channels, int64_t feature_stride, float *out_map, float *out_final_T, void *stream)
+{
+    int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    return launch_blend_channels(*cam, *opts, ws, plan_frame(ws, *opts), features, channels, feature_stride, out_map, out_final_T,
+                                 static_cast<hipStream_t>(stream));
+}
+
+int gsr_render_channels(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                        size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, float *out_map,
+                        float *out_final_T, void *stream)
+{
+    int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
+    if (rc) return rc;
+    rc = check_scene(scene);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    GsrOptions o = *opts;
+    o.colour_stage = 0;  // as in gsr_render_features: no SH row is read, the records keep their "unevaluated" marks
+    const FramePlan plan = plan_frame(ws, o);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
+    if (rc) return rc;
+    rc = bin_sort_impl(&o, ws, plan, s);
+    if (rc) return rc;
+    return launch_blend_channels(*cam, o, ws, plan, features, channels, feature_stride, out_map, out_final_T, s);
+}
+
 // How many views go through one launch sequence: as many slices as the workspace holds, at most MAX_VIEWS, GsrOptions.batch_views
 // (when set) and the views there are.  0: the workspace does not hold one view.
 static int views_per_launch(const GsrScene *scene, const GsrCamera *cam0, const GsrOptions *opts, int64_t max_pairs, size_t workspace_bytes, int32_t n_cams)

@@ -237,6 +237,9 @@ int launch_tile_order(const Workspace &ws, const FramePlan &plan, bool use_hint,
 // Stage 3 for caller-supplied channels (blend_features.hip): out_map[p] = sum_i w_i(p) features[i], single views only
 int launch_blend_features(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *features,
                           float *out_map, float *out_T, hipStream_t s);
+// The same for `channels` channels, rows `stride` floats apart, up to 16 channels per walk (blend_channels.hip): one launch per group
+int launch_blend_channels(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *features,
+                          int channels, int64_t stride, float *out_map, float *out_T, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

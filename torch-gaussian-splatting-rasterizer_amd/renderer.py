@@ -326,6 +326,11 @@ def _render_checked(rasterizers, streams, opts: GsrOptions, attempt, slack_div: 
     raise type(e)(e.code, f"{what} still incomplete after {MAX_RETRIES} re-renders: {st}")
 
 
+# render_features: maps of more channels than this go through gsr_render_channels (many channels per walk of the tile lists), the
+# others through the three-channel blend.  DESIGN.md §5.11 has the measurement the rule rests on.
+WIDE_BLEND_ABOVE = 3
+
+
 class Rasterizer:
     """Owns the scratch workspace for one scene and renders frames of it.
 
@@ -521,13 +526,64 @@ class Rasterizer:
         self.unchecked.wrote(1)
         return img, maps, T
 
+    def _feature_rows(self, features: torch.Tensor, scene_order: bool) -> torch.Tensor:
+        """[n, C] caller values -> a float32 tensor in the scene's order that gsr_render_channels reads where it lies: rows of unit
+        element stride, stride(0) >= C apart.  The caller's own tensor (a column window of a wider one included) whenever it already
+        is in the scene's order and laid out so; else ONE copy (the gather through scene.order_t, or .contiguous())."""
+        _require_cuda(features, "features")
+        if features.dim() != 2 or features.shape[0] != self.scene.n or features.shape[1] < 1 or features.dtype != torch.float32:
+            raise ValueError(f"features must be a float32 tensor of shape [{self.scene.n}, C >= 1], got {features.dtype} {tuple(features.shape)}")
+        if features.device != self.scene.device:
+            raise ValueError("features must live on the scene's device")
+        if features.shape[1] > _lib.GSR_MAX_FEATURE_CHANNELS:
+            raise ValueError(f"at most {_lib.GSR_MAX_FEATURE_CHANNELS} channels per call, got {features.shape[1]}")
+        if self.scene.n == 0:  # an empty tensor has no address; libgsr refuses a null array
+            return torch.zeros((1, features.shape[1]), dtype=torch.float32, device=self.scene.device)
+        if not scene_order and self.scene.order_t is not None:
+            return features.index_select(0, self.scene.order_t)
+        if features.stride(1) == 1 and features.stride(0) >= features.shape[1]:
+            return features
+        return features.contiguous()
+
+    def _enqueue_channels(self, cam: GsrCamera, opts: GsrOptions, rows: torch.Tensor, want_T: bool):
+        """One preprocess, one bin / sort and one gsr_blend_channels (gsr_render_channels) on the current stream, unchecked like
+        enqueue(): the [.., C] map is written in place, no group copies.  Returns (map, T or None)."""
+        ws = self._workspace(cam.width, cam.height)
+        shape, tshape = self._out_shape(cam, opts)
+        dev, n_ch = self.scene.device, int(rows.shape[1])
+        new = torch.zeros if opts.output_layout == 2 else torch.empty  # strips may include rows below the frame's last pixel row
+        out = new(shape[:2] + (n_ch,), dtype=torch.float32, device=dev)
+        T = torch.ones(tshape, dtype=torch.float32, device=dev) if want_T else None
+        if out.numel() == 0:  # a shard that owns no tile row
+            self.unchecked.wrote(0)
+            return out, T
+        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
+            opts = GsrOptions.from_buffer_copy(opts)
+            opts.keep_flags = 1
+        sc = self.scene.c_struct()
+        check(lib.gsr_render_channels(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), rows.data_ptr(),
+                                      n_ch, int(rows.stride(0)), out.data_ptr(), T.data_ptr() if want_T else None, _stream_ptr(dev)))
+        self.unchecked.wrote(1)
+        return out, T
+
     def render_features(self, cam: GsrCamera, features: torch.Tensor, opts: Optional[GsrOptions] = None, return_T: bool = False,
                         scene_order: bool = False):
         """Composite the caller's per-gaussian values with the colour frame's weights: out[p] = sum_i w_i(p) features[i], w_i = alpha_i T_i
         over the same depth-ordered lists (gsr_render_features / gsr_blend_features).  features: [n, C] float32 on the scene's device,
         C >= 1, indexed like the file the scene was loaded from (scene_order=True: like the scene's resident arrays).  Returns
         [H, W, C] (layouts as render()), and the final transmittance [H, W] with return_T.  One preprocess and one bin / sort, then
-        ceil(C / 3) blends; checked and re-rendered on overflow like render().  Values are not clamped; they must be finite."""
+        for C <= 3 one three-channel blend (gsr_render_features), for C > 3 gsr_render_channels: up to 16 channels per walk of the
+        tile lists, read from the caller's tensor without a copy when scene_order=True and its rows have unit element stride
+        (column windows of a wider tensor included), written straight into the [.., C] map.  Every channel is bit for bit what it is
+        as a map of its own.  Checked and re-rendered on overflow like render().  Values are not clamped; they must be finite."""
+        if features.dim() == 2 and features.shape[1] > WIDE_BLEND_ABOVE:
+            rows = self._feature_rows(features, scene_order)
+
+            def attempt_wide(o):
+                out, T = self._enqueue_channels(cam, o, rows, return_T)
+                return (out, T) if return_T else out
+
+            return _render_checked([self], [None], opts or make_options(), attempt_wide, 8, "feature map")
         groups = self._feature_groups(features, scene_order)
         n_ch = int(features.shape[1])
 
