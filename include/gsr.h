@@ -27,7 +27,8 @@ extern "C" {
 
 #define GSR_VERSION 600 /* 0.6.0 (additions since, no existing entry point or struct changed: gsr_blend_features / gsr_render_features —
                             depth, alpha and caller-supplied channels composited with the colour frame's weights; gsr_blend_channels /
-                            gsr_render_channels + GSR_MAX_FEATURE_CHANNELS — any number of channels, rows at a caller's stride, many channels per walk of the lists): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            gsr_render_channels + GSR_MAX_FEATURE_CHANNELS — any number of channels, rows at a caller's stride, many channels per walk of the lists; gsr_blend_channels_backward /
+                            gsr_render_channels_backward — the transpose of gsr_blend_channels in the channels: the gradient of a map with respect to the per-gaussian rows): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -303,6 +304,32 @@ int gsr_render_channels(const GsrScene *scene, const GsrCamera *cam, const GsrOp
                         size_t workspace_bytes, const float *features /* row i at features + i * feature_stride */,
                         int32_t channels, int64_t feature_stride, float *out_map /* [.., channels] */, float *out_final_T,
                         void *stream);
+
+/* The transpose of gsr_blend_channels under the same camera and options:
+ * grad_features[i * grad_stride + c] += sum_p w_i(p) grad_map[p][c], c = 0 .. channels - 1, with the weights w_i = alpha_i T_i the
+ * forward composites with, bit for bit, over the forward's lists and with its stop rule.  out_map is linear in the features, so this
+ * is its exact gradient with respect to them; nothing flows through the geometry or the opacities.  It ADDS into grad_features (the
+ * caller zeroes it, or keeps summing over views); rows of gaussians no pixel draws are not touched.  grad_map: float32, contiguous,
+ * layout per opts->output_layout with `channels` channels (what gsr_blend_channels writes); pixels the forward leaves 0 (the undrawn
+ * last column / row of reference_compat) contribute nothing.  grad_features: float32, rows grad_stride >= channels floats apart.
+ * Honoured and ignored options, and what it leaves alone on the workspace, are gsr_blend_channels'; gsr_read_stats afterwards
+ * describes the walk (wave_entries / fetched_entries are the forward's).  Nothing else is written: no map, no final T.
+ *   - The sums are float atomic adds: their value depends on the order the adds arrive in, so two calls with the same input can
+ *     differ in the last bits.
+ *   - grad_map must be finite.
+ *   - grad_features must not alias grad_map.
+ * GSR_ERR_BAD_ARG, before any HIP call or look at the workspace, for a null camera, options, grad_map or grad_features, channels < 1
+ * or > GSR_MAX_FEATURE_CHANNELS, grad_stride < channels, output_dtype = 1, accum_dtype = 1.  Single views. */
+int gsr_blend_channels_backward(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                                size_t workspace_bytes, const float *grad_map /* [.., channels], layout per opts->output_layout */,
+                                int32_t channels, float *grad_features /* row i at + i * grad_stride */, int64_t grad_stride,
+                                void *stream);
+
+/* gsr_preprocess (as with colour_stage = 0) + gsr_bin_sort + gsr_blend_channels_backward */
+int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                                 size_t workspace_bytes, const float *grad_map /* [.., channels], layout per opts->output_layout */,
+                                 int32_t channels, float *grad_features /* row i at + i * grad_stride */, int64_t grad_stride,
+                                 void *stream);
 
 /* Several views of ONE resident scene (the reference renders one view per process, rasterize.py:315-329; BASELINE configs[3] is a
  * camera set).  cams[n_cams] [host] must share width/height; frame i goes to out_images + i * frame_stride (in elements of the

@@ -128,6 +128,7 @@ EXPORTS = [
     "gsr_preprocess", "gsr_bin_sort", "gsr_blend", "gsr_render_forward", "gsr_read_stats", "gsr_sh_to_rgb", "gsr_cov3d",
     "gsr_render_batch", "gsr_render_batch_slots", "gsr_scene_order", "gsr_scene_order_bytes", "gsr_scene_bounds", "gsr_block_visibility", "gsr_project_to_camera_space", "gsr_compute_2d_covariance", "gsr_compute_covering_bbox", "gsr_rasterize_gaussian",
     "gsr_blend_features", "gsr_render_features", "gsr_blend_channels", "gsr_render_channels",
+    "gsr_blend_channels_backward", "gsr_render_channels_backward",
 ]
 
 
@@ -156,6 +157,8 @@ def _load() -> C.CDLL:
     L.gsr_render_features.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp]
     L.gsr_blend_channels.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp]
     L.gsr_render_channels.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp]
+    L.gsr_blend_channels_backward.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, vp, i64, vp]
+    L.gsr_render_channels_backward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, vp, i64, vp]
     L.gsr_render_forward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
     L.gsr_render_batch.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, vp, sz, vp, i64, vp]
     L.gsr_render_batch_slots.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, C.POINTER(vp), sz,

@@ -498,6 +498,60 @@ int gsr_render_channels(const GsrScene *scene, const GsrCamera *cam, const GsrOp
     return launch_blend_channels(*cam, o, ws, plan, features, channels, feature_stride, out_map, out_final_T, s);
 }
 
+// What gsr_blend_channels_backward / gsr_render_channels_backward refuse before anything else (and before any HIP call)
+static int check_channels_backward(const GsrCamera *cam, const GsrOptions *opts, const float *grad_map, int32_t channels,
+                                   const float *grad_features, int64_t grad_stride)
+{
+    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    if (!grad_map) { set_error("null gradient map"); return GSR_ERR_BAD_ARG; }
+    if (!grad_features) { set_error("null feature gradient"); return GSR_ERR_BAD_ARG; }
+    if (channels < 1 || channels > GSR_MAX_FEATURE_CHANNELS) {
+        set_error("bad channels %d (1 .. %d)", channels, GSR_MAX_FEATURE_CHANNELS); return GSR_ERR_BAD_ARG;
+    }
+    if (grad_stride < channels) {
+        set_error("bad grad_stride %lld: rows of %d channels overlap", (long long)grad_stride, channels); return GSR_ERR_BAD_ARG;
+    }
+    if (opts->output_dtype == 1) { set_error("gradient maps are float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("feature gradients are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+int gsr_blend_channels_backward(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                                size_t workspace_bytes, const float *grad_map, int32_t channels, float *grad_features, int64_t grad_stride,
+                                void *stream)
+{
+    int rc = check_channels_backward(cam, opts, grad_map, channels, grad_features, grad_stride);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    return launch_blend_channels_backward(*cam, *opts, ws, plan_frame(ws, *opts), grad_map, channels, grad_features, grad_stride,
+                                          static_cast<hipStream_t>(stream));
+}
+
+int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                                 size_t workspace_bytes, const float *grad_map, int32_t channels, float *grad_features,
+                                 int64_t grad_stride, void *stream)
+{
+    int rc = check_channels_backward(cam, opts, grad_map, channels, grad_features, grad_stride);
+    if (rc) return rc;
+    rc = check_scene(scene);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    GsrOptions o = *opts;
+    o.colour_stage = 0;  // as in gsr_render_channels: the lists and records of the forward it transposes
+    const FramePlan plan = plan_frame(ws, o);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
+    if (rc) return rc;
+    rc = bin_sort_impl(&o, ws, plan, s);
+    if (rc) return rc;
+    return launch_blend_channels_backward(*cam, o, ws, plan, grad_map, channels, grad_features, grad_stride, s);
+}
+
 // How many views go through one launch sequence: as many slices as the workspace holds, at most MAX_VIEWS, GsrOptions.batch_views
 // (when set) and the views there are.  0: the workspace does not hold one view.
 static int views_per_launch(const GsrScene *scene, const GsrCamera *cam0, const GsrOptions *opts, int64_t max_pairs, size_t workspace_bytes, int32_t n_cams)

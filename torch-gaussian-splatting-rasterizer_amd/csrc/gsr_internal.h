@@ -240,6 +240,9 @@ int launch_blend_features(const GsrCamera &cam, const GsrOptions &opts, const Wo
 // The same for `channels` channels, rows `stride` floats apart, up to 16 channels per walk (blend_channels.hip): one launch per group
 int launch_blend_channels(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *features,
                           int channels, int64_t stride, float *out_map, float *out_T, hipStream_t s);
+// The transpose of launch_blend_channels in the channels (blend_channels_backward.hip): grad_features[i] += sum_p w_i(p) grad_map[p]
+int launch_blend_channels_backward(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
+                                   const float *grad_map, int channels, float *grad_features, int64_t stride, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

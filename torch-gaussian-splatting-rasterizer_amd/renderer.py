@@ -326,6 +326,35 @@ def _render_checked(rasterizers, streams, opts: GsrOptions, attempt, slack_div: 
     raise type(e)(e.code, f"{what} still incomplete after {MAX_RETRIES} re-renders: {st}")
 
 
+def file_order_gradient(buf: torch.Tensor, order_t: Optional[torch.Tensor]) -> torch.Tensor:
+    """A per-gaussian gradient in the scene's order -> in the order of the file the scene was loaded from: the transpose of the
+    gather `rows = features.index_select(0, order_t)` (row j of the scene is row order_t[j] of the file).  order_t=None: the scene
+    kept the file's order and `buf` itself is returned.  Works on CPU and GPU tensors."""
+    if order_t is None:
+        return buf
+    return torch.empty_like(buf).index_copy_(0, order_t, buf)
+
+
+class _RenderFeatures(torch.autograd.Function):
+    """render_features as a differentiable function of the features alone: the map is linear in them, so the backward is the
+    transpose under the same camera and options (Rasterizer.feature_gradient); nothing flows to the geometry or the opacities."""
+
+    @staticmethod
+    def forward(ctx, features, rasterizer, cam, opts, return_T, scene_order):
+        ctx.rasterizer, ctx.scene_order = rasterizer, scene_order
+        ctx.cam = GsrCamera.from_buffer_copy(cam)
+        ctx.opts = GsrOptions.from_buffer_copy(opts or make_options())
+        res = rasterizer._render_features(cam, features.detach(), opts, return_T, scene_order)
+        if return_T:
+            ctx.mark_non_differentiable(res[1])
+        return res
+
+    @staticmethod
+    def backward(ctx, grad_out, *_):
+        g = ctx.rasterizer.feature_gradient(ctx.cam, grad_out, ctx.opts, scene_order=ctx.scene_order)
+        return g, None, None, None, None, None
+
+
 # render_features: maps of more channels than this go through gsr_render_channels (many channels per walk of the tile lists), the
 # others through the three-channel blend.  DESIGN.md §5.11 has the measurement the rule rests on.
 WIDE_BLEND_ABOVE = 3
@@ -575,7 +604,15 @@ class Rasterizer:
         for C <= 3 one three-channel blend (gsr_render_features), for C > 3 gsr_render_channels: up to 16 channels per walk of the
         tile lists, read from the caller's tensor without a copy when scene_order=True and its rows have unit element stride
         (column windows of a wider tensor included), written straight into the [.., C] map.  Every channel is bit for bit what it is
-        as a map of its own.  Checked and re-rendered on overflow like render().  Values are not clamped; they must be finite."""
+        as a map of its own.  Checked and re-rendered on overflow like render().  Values are not clamped; they must be finite.
+        Differentiable in `features`: when they require a gradient (and grad mode is on) the map carries a grad_fn whose backward
+        is feature_gradient() under the same camera and options; the values are those of the detached tensor, bit for bit, and T
+        is not differentiable.  No gradient flows to the scene."""
+        if features.requires_grad and torch.is_grad_enabled():
+            return _RenderFeatures.apply(features, self, cam, opts, return_T, scene_order)
+        return self._render_features(cam, features, opts, return_T, scene_order)
+
+    def _render_features(self, cam: GsrCamera, features: torch.Tensor, opts: Optional[GsrOptions], return_T: bool, scene_order: bool):
         if features.dim() == 2 and features.shape[1] > WIDE_BLEND_ABOVE:
             rows = self._feature_rows(features, scene_order)
 
@@ -594,6 +631,86 @@ class Rasterizer:
             return (out, T) if return_T else out
 
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "feature map")
+
+    # -- the gradient of a feature map with respect to the features -------------------------------------------------------------
+    def feature_gradient(self, cam: GsrCamera, grad_map: torch.Tensor, opts: Optional[GsrOptions] = None,
+                         out: Optional[torch.Tensor] = None, scene_order: bool = False) -> torch.Tensor:
+        """The transpose of render_features under the same camera and options: [n, C] with row i = sum_p w_i(p) grad_map[p]
+        (gsr_render_channels_backward; every C >= 1 goes through it).  grad_map: [H, W, C] as render_features lays the map out
+        (made contiguous float32), finite.  Returned in the order of the file the scene was loaded from (scene_order=True: of the
+        scene's resident arrays).  With `out` — [n, C] float32 on the scene's device, in the SCENE's order, unit element stride, rows
+        at least C apart — the gradient is ACCUMULATED into `out` and `out` is returned: summing over a batch of views needs no
+        temporary.  Stages 1-2 are re-run on every call and checked like any frame; float atomic sums may differ in the last bits
+        between two calls."""
+        opts = opts or make_options()
+        dev, n = self.scene.device, self.scene.n
+        _require_cuda(grad_map, "grad_map")
+        shape, _ = self._out_shape(cam, opts)
+        if grad_map.dim() != 3 or tuple(grad_map.shape[:2]) != shape[:2] or not 1 <= grad_map.shape[2] <= _lib.GSR_MAX_FEATURE_CHANNELS:
+            raise ValueError(f"grad_map must have shape {shape[:2]} + (1 <= C <= {_lib.GSR_MAX_FEATURE_CHANNELS},), got {tuple(grad_map.shape)}")
+        if grad_map.device != dev:
+            raise ValueError("grad_map must live on the scene's device")
+        n_ch = int(grad_map.shape[2])
+        gm = grad_map.detach().to(torch.float32).contiguous()
+        if out is not None:
+            if tuple(out.shape) != (n, n_ch) or out.dtype != torch.float32 or out.device != dev or (
+                    n and (out.stride(1) != 1 or out.stride(0) < n_ch)):
+                raise ValueError(f"out must be a float32 tensor of shape [{n}, {n_ch}] on the scene's device with unit element stride")
+        if n == 0 or gm.numel() == 0:  # nothing to draw, or a shard that owns no tile row: the gradient is zero
+            return out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
+        ws_args = lambda: (self._workspace(cam.width, cam.height).data_ptr(), self._ws.numel())
+        sp = _stream_ptr(dev)
+
+        def chained(o):  # slice 0 holds unchecked frames: add to their record
+            if self.unchecked.slices and not o.keep_flags:
+                o = GsrOptions.from_buffer_copy(o)
+                o.keep_flags = 1
+            return o
+
+        if out is None:
+            buf = torch.empty((n, n_ch), dtype=torch.float32, device=dev)
+
+            def attempt(o):  # a re-run after an overflow starts from zero again
+                o, sc = chained(o), self.scene.c_struct()
+                wp, wn = ws_args()
+                buf.zero_()
+                check(lib.gsr_render_channels_backward(C.byref(sc), C.byref(cam), C.byref(o), self.max_pairs, wp, wn, gm.data_ptr(), n_ch,
+                                                       buf.data_ptr(), n_ch, sp))
+                self.unchecked.wrote(1)
+                return buf
+
+            _render_checked([self], [None], opts, attempt, 8, "feature gradient")
+            return buf if scene_order else file_order_gradient(buf, self.scene.order_t)
+
+        # Accumulating: an incomplete walk must not reach `out`, so stages 1-2 are checked (and re-run) first, then the blend adds
+        def attempt_lists(o):
+            o, sc = GsrOptions.from_buffer_copy(chained(o)), self.scene.c_struct()
+            o.colour_stage = 0  # as gsr_render_channels_backward
+            wp, wn = ws_args()
+            check(lib.gsr_preprocess(C.byref(sc), C.byref(cam), C.byref(o), wp, wn, None, sp))
+            check(lib.gsr_bin_sort(n, C.byref(cam), C.byref(o), self.max_pairs, wp, wn, sp))
+            self.unchecked.wrote(1)
+            return o
+
+        o = _render_checked([self], [None], opts, attempt_lists, 8, "feature gradient")
+        wp, wn = ws_args()
+        check(lib.gsr_blend_channels_backward(n, C.byref(cam), C.byref(o), self.max_pairs, wp, wn, gm.data_ptr(), n_ch, out.data_ptr(),
+                                              int(out.stride(0)), sp))
+        return out
+
+    def blend_weights(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """[n]: every gaussian's blend weight summed over the drawn pixels of this view, sum_p w_i(p) — feature_gradient of a
+        one-channel map of ones; the importance score pruning works with.  Returned in the file's order; with `out` ([n] float32,
+        contiguous, in the SCENE's order) the weights are accumulated into it, e.g. over a camera set."""
+        opts = opts or make_options()
+        shape, _ = self._out_shape(cam, opts)
+        ones = torch.ones(shape[:2] + (1,), dtype=torch.float32, device=self.scene.device)
+        if out is not None:
+            if out.dim() != 1 or not out.is_contiguous():
+                raise ValueError("out must be a contiguous [n] tensor")
+            self.feature_gradient(cam, ones, opts, out=out.unsqueeze(1))
+            return out
+        return self.feature_gradient(cam, ones, opts).squeeze(1)
 
     def render_depth(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, normalize: bool = False):
         """(depth [H, W], alpha [H, W]): depth = sum_i w_i z_i with z = the gaussians' camera-space depth, alpha = sum_i w_i (= 1 - final T
