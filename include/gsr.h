@@ -192,8 +192,10 @@ typedef struct GsrStats {
     uint64_t wave_entries;  /* (8x8 quadrant, entry) pairs the blend actually evaluated: 64 pixel evaluations each */
     uint64_t fetched_entries; /* list entries the blend staged (<= n_pairs: a saturated tile stops fetching) */
     uint64_t colour_evals;  /* sh_to_rgb evaluations (192-B SH rows read) by the blend: colour_stage = 0 evaluates a gaussian when a tile
-                               first stages it; tiles racing for the same gaussian may each evaluate it (same result), so this is an
-                               UPPER-BOUND estimate of the gaussians coloured and varies by a few per cent from run to run.  0 when the
+                               first stages an entry of it that NEEDS the colour — one whose exact footprint hits an 8x8 quadrant of the
+                               tile that has not finished; an entry over finished quadrants only, or over none, leaves the record
+                               pending for the next tile.  Tiles racing for the same gaussian may each evaluate it (same result), so this
+                               is an UPPER-BOUND estimate of the gaussians coloured and varies by a few per cent from run to run.  0 when the
                                preprocess evaluated the colours (colour_stage = 1: n_visible evaluations there). */
 } GsrStats;
 

@@ -99,10 +99,11 @@ __device__ __forceinline__ int tile_list_next(const BlendArgs &a, TileList<THREA
             if (w < wave) { o0 += c0; o1 += c1; }
             tot0 += c0; tot1 += c1;
         }
-        const unsigned long long lt = (1ull << lane) - 1ull;
+        // set bits below this lane (v_mbcnt: no lane mask to keep in registers across the walks)
+        auto below = [](unsigned long long b) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(b >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)b, 0u)); };
         const uint32_t tail = t.head + t.qlen;
-        if (f0) s_ring[(tail + o0 + (uint32_t)__popcll(b0 & lt)) & (RING - 1)] = v0 & LIST_ID_MASK;
-        if (f1) s_ring[(tail + tot0 + o1 + (uint32_t)__popcll(b1 & lt)) & (RING - 1)] = v1 & LIST_ID_MASK;
+        if (f0) s_ring[(tail + o0 + below(b0)) & (RING - 1)] = v0 & LIST_ID_MASK;
+        if (f1) s_ring[(tail + tot0 + o1 + below(b1)) & (RING - 1)] = v1 & LIST_ID_MASK;
         t.qlen += tot0 + tot1;
         t.pos += 2 * THREADS;
         return -1;
@@ -122,9 +123,57 @@ __device__ __forceinline__ int tile_list_next(const BlendArgs &a, TileList<THREA
 struct BlendLds {
     float4 *s0, *s1, *s2;   // staged records, one plane of THREADS entries per 16-B part: q0, q1, q2 (or what stands in for it)
     uint32_t *ring, *wc;    // TileList<THREADS>::RING and 2 * WAVES words (tile_list_next)
-    int *done;              // waves that have finished
+    int *done;              // waves that have finished (next_batch / wave_finished; nullptr in blend_walk_kernel, whose live word stands in for it)
     uint32_t *col;          // the workgroup's deferred-colour evaluations (COLOUR kernels only)
 };
+
+// What the colour kernels add to a staged batch (lazy colours, blend.hip staged_q2): one class word per entry — bit q = the entry can
+// touch quadrant q of the tile (q = 2 * lower half + right half), bit 4 + q = it may take the walk's unguarded path there
+// (footprint_classify) — and the workgroup's word of quadrants that are still live.  The staging thread classifies its entry once,
+// for all four quadrants; the waves take their masks from the class words, and a pending colour is evaluated only for an entry
+// with a hit in a live quadrant.
+struct BlendClassLds {
+    uint32_t *cls;   // THREADS class words
+    uint32_t *live;  // bit q: quadrant q has not finished (read after the batch's top barrier: workgroup-uniform)
+};
+
+// The pixel-centre bounds of the four quadrants of the tile whose first pixel is (x0, y0): quadrant q spans x[2 * (q & 1)] ..
+// x[2 * (q & 1) + 1], y[2 * (q >> 1)] .. y[2 * (q >> 1) + 1].  Called where a batch is staged, with x0 and y0 made opaque there: left
+// to itself the compiler computes the eight floats once, ahead of the batch loop, as eight vector registers that it then spills around
+// the walks; this way they cost eight conversions per batch and no register.
+struct QuadBounds {
+    float x[4], y[4];
+};
+__device__ __forceinline__ QuadBounds quad_bounds(int x0, int y0)
+{
+    asm volatile("" : "+s"(x0), "+s"(y0));  // (workgroup-uniform: scalar registers)
+    QuadBounds b;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        b.x[k] = (float)(x0 + 8 * (k >> 1) + 7 * (k & 1));
+        b.y[k] = (float)(y0 + 8 * (k >> 1) + 7 * (k & 1));
+    }
+    return b;
+}
+
+// An entry's class word on the tile with the quadrants `b`.  FAST = false: hit bits only (footprint_hits_rect: the same value as
+// footprint_classify's hit), for the plain kernel, which has no unguarded path.
+template <bool FAST>
+__device__ __forceinline__ uint32_t footprint_class4(const float4 q0, const float4 q1, float L, const QuadBounds &b)
+{
+    uint32_t c = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float fx0 = b.x[2 * (q & 1)], fx1 = b.x[2 * (q & 1) + 1], fy0 = b.y[2 * (q >> 1)], fy1 = b.y[2 * (q >> 1) + 1];
+        if (FAST) {
+            const FootprintClass f = footprint_classify(q0, q1, L, fx0, fx1, fy0, fy1);
+            c |= (f.hit ? 1u : 0u) << q | (f.fast ? 16u : 0u) << q;
+        } else {
+            c |= (footprint_hits_rect(q0, q1, fx0, fx1, fy0, fy1) ? 1u : 0u) << q;
+        }
+    }
+    return c;
+}
 
 struct TilePixel {
     int tile, tx, ty;
@@ -158,24 +207,29 @@ __device__ __forceinline__ void tile_coords(const BlendArgs &a, int lane, int wa
 
 // The batch loop: list = batches_begin(...); while (const int nb = next_batch(..., fetched, stage)) { consume nb staged entries }.
 // next_batch stages the tile's list THREADS entries at a time — q0 and q1 of entry `id` from its record, the third plane from
-// stage(id) — counts them in `fetched` (workgroup-uniform) and returns the batch's size, or 0 once the list has ended or every wave
-// has called wave_finished.  The consuming side stays in the kernel's body: as a callable that captures the accumulators, the
+// stage(id, need) — counts them in `fetched` (workgroup-uniform) and returns the batch's size, or 0 once the list has ended or every
+// wave has called wave_finished.  COLOUR: the staging thread also leaves the entry's class word (hit bits) in cl.cls, and `need` says
+// whether one of the quadrants it hits is still live (*cl.live as the batch's top barrier published it); the other policies stage
+// with need = true and have no class plane.  The consuming side stays in the kernel's body: as a callable that captures the accumulators, the
 // compiler sinks blend_one's `T - w` below the survivor loop's two arms, away from the multiply it contracts with into
 // fma(-T, alpha, T), and the plain kernel's frames are no longer the asm walks' bit for bit.
 template <int THREADS, bool COLOUR>
-__device__ __forceinline__ TileList<THREADS> batches_begin(const BlendArgs &a, const TilePixel &t, int tid, const BlendLds &lds)
+__device__ __forceinline__ TileList<THREADS> batches_begin(const BlendArgs &a, const TilePixel &t, int tid, const BlendLds &lds,
+                                                           const BlendClassLds &cl = {})
 {
-    if (tid == 0) { *lds.done = 0; if (COLOUR) *lds.col = 0; }
+    if (tid == 0) { *lds.done = 0; if (COLOUR) { *lds.col = 0; *cl.live = 0xFu; } }
     return tile_list_of<THREADS>(a, t.tile, t.tx, t.ty);
 }
 
-template <int THREADS, class Stage>
-__device__ __forceinline__ int next_batch(const BlendArgs &a, TileList<THREADS> &list, int tid, const BlendLds &lds, uint32_t &fetched,
-                                          Stage stage)
+template <int THREADS, bool COLOUR, class Stage>
+__device__ __forceinline__ int next_batch(const BlendArgs &a, TileList<THREADS> &list, const TilePixel &t, int tid, const BlendLds &lds,
+                                          const BlendClassLds &cl, uint32_t &fetched, Stage stage)
 {
     for (;;) {
         __syncthreads();  // previous batch fully consumed (and *lds.done initialised); a refilled ring published
         if (*lds.done == THREADS / 64) return 0;  // uniform: every wave saturated
+        uint32_t live = 0;
+        if constexpr (COLOUR) live = *cl.live;
         uint32_t id = 0;
         const int nb = tile_list_next<THREADS>(a, list, lds.ring, lds.wc, &id);
         if (nb < 0) continue;
@@ -183,9 +237,18 @@ __device__ __forceinline__ int next_batch(const BlendArgs &a, TileList<THREADS> 
         fetched += (uint32_t)nb;
         if (tid < nb) {
             const GaussRec *r = a.rec + id;
-            lds.s0[tid] = r->q0;
-            lds.s1[tid] = r->q1;
-            lds.s2[tid] = stage(id);
+            if constexpr (COLOUR) {
+                const float4 q0 = r->q0, q1 = r->q1;
+                const uint32_t c = footprint_class4<false>(q0, q1, 0.0f, quad_bounds(t.tx * 16, t.ty * 16));
+                lds.s0[tid] = q0;
+                lds.s1[tid] = q1;
+                cl.cls[tid] = c;
+                lds.s2[tid] = stage(id, (c & live) != 0u);
+            } else {
+                lds.s0[tid] = r->q0;
+                lds.s1[tid] = r->q1;
+                lds.s2[tid] = stage(id, true);
+            }
         }
         __syncthreads();
         return nb;
@@ -196,6 +259,15 @@ __device__ __forceinline__ int next_batch(const BlendArgs &a, TileList<THREADS> 
 __device__ __forceinline__ void wave_finished(const BlendLds &lds, int lane)
 {
     if (lane == 0) atomicAdd(lds.done, 1);
+}
+
+// Quadrants that have finished leave the live word, once; they never come back.
+__device__ __forceinline__ void quadrants_finished(const BlendClassLds &cl, int lane, uint32_t bits)
+{
+    if (lane == 0) {
+        asm volatile("" : "+v"(bits));  // (the operand is formed here, not kept in a register across the walks)
+        atomicAnd(cl.live, ~bits);
+    }
 }
 
 // Epilogue, every thread: the counters gsr_read_stats totals.  COLOUR, the colour frame's kernels: stat[5] = the workgroup's
@@ -222,7 +294,8 @@ __device__ __forceinline__ void blend_stats_out(const BlendArgs &a, const TilePi
 }
 
 // The plain-C statement of the blend: one 256-thread workgroup per tile, wave = 8x8 quadrant, lane = pixel.  The policy P says
-//   - stage(a, id, evals): the third LDS plane of gaussian `id`, {log2 opacity, c0, c1, c2};
+//   - stage(a, id, evals): the third LDS plane of gaussian `id`, {log2 opacity, c0, c1, c2}; COLOUR: stage(a, id, need, evals),
+//     need = false: no walk will read c0..c2 of this entry;
 //   - acc_round(T, C0, C1, C2): what happens to the accumulators after every entry;
 //   - finished(a, T, C0, C1, C2, undrawn): has this pixel stopped changing?
 //   - COLOUR (blend_stats_out), MIN_WAVES (per SIMD, for the register allocator).
@@ -234,7 +307,9 @@ __global__ __launch_bounds__(256, P::MIN_WAVES) void blend_kernel(BlendArgs args
     __shared__ int s_done;
     __shared__ uint32_t s_col;
     __shared__ uint32_t s_ring[TileList<256>::RING], s_wc[2 * TileList<256>::WAVES];
+    __shared__ uint32_t s_cls[P::COLOUR ? 256 : 1], s_live;
     const BlendLds lds = {srec[0], srec[1], srec[2], s_ring, s_wc, &s_done, &s_col};
+    const BlendClassLds cl = {s_cls, &s_live};  // COLOUR only.  s_done stays the loop's stop word for every policy (next_batch is shared); s_live == 0 says the same
     const float4 *const s0 = srec[0], *const s1 = srec[1], *const s2 = srec[2];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     TilePixel t = tile_of_slot(a);
@@ -248,15 +323,20 @@ __global__ __launch_bounds__(256, P::MIN_WAVES) void blend_kernel(BlendArgs args
     uint32_t evaluated = 0;  // wave-uniform
     uint32_t col_evals = 0;  // per thread: deferred colours this thread evaluated while staging
 
-    auto stage = [&](uint32_t id) __attribute__((always_inline)) { return policy.stage(a, id, col_evals); };
+    auto stage = [&](uint32_t id, bool need) __attribute__((always_inline)) {
+        if constexpr (P::COLOUR) return policy.stage(a, id, need, col_evals);
+        else return policy.stage(a, id, col_evals);
+    };
     bool wave_done = false;
     uint32_t fetched = 0;  // workgroup-uniform
-    TileList<256> list = batches_begin<256, P::COLOUR>(a, t, tid, lds);
-    while (const int nb = next_batch<256>(a, list, tid, lds, fetched, stage)) {
+    TileList<256> list = batches_begin<256, P::COLOUR>(a, t, tid, lds, cl);
+    while (const int nb = next_batch<256, P::COLOUR>(a, list, t, tid, lds, cl, fetched, stage)) {
         if (wave_done) continue;
         for (int chunk = 0; chunk < nb; chunk += 64) {
             const int e = chunk + lane;
-            const bool hit = e < nb && footprint_hits_rect(s0[e], s1[e], qx0, qx1, qy0, qy1);
+            bool hit;  // COLOUR: the bit the staging thread computed (quadrant = wave) — what decided whether the colour was evaluated
+            if constexpr (P::COLOUR) hit = e < nb && (s_cls[e] >> wave & 1u);
+            else hit = e < nb && footprint_hits_rect(s0[e], s1[e], qx0, qx1, qy0, qy1);
             unsigned long long m = __ballot(hit);
             evaluated += (uint32_t)__popcll(m);
             // two survivors per trip so that the second one's LDS reads overlap the first one's arithmetic
@@ -286,6 +366,7 @@ __global__ __launch_bounds__(256, P::MIN_WAVES) void blend_kernel(BlendArgs args
             if (__all(policy.finished(a, T, C0, C1, C2, undrawn))) {
                 wave_done = true;
                 wave_finished(lds, lane);
+                if constexpr (P::COLOUR) quadrants_finished(cl, lane, 1u << wave);
                 break;
             }
         }
