@@ -44,14 +44,34 @@ __device__ __forceinline__ bool resolve_pass(const PassSpec &a, const FrameCtrl 
     return true;
 }
 
+// Which tile a workgroup of the hist / scatter grids takes.  The dispatcher deals workgroups round-robin over the chip's eight XCDs,
+// whose L2s are not coherent with one another: with tile = blockIdx.x the runs that neighbouring tiles write side by side (16 records
+// = 64 B per array and digit in the depth sort) and the 64-B sectors of the digit-major histogram table (16 tiles each) would be put
+// together from, and fetched into, every one of the eight L2s.  So the workgroups of one class (blockIdx.x & 7 — one XCD, as long as
+// gridDim.x is a multiple of 8: launch_pass) take CONSECUTIVE tiles: class k owns tiles [k * per, (k + 1) * per).  per comes from the
+// live count n, not from the grid (sized by the host's bound, about twice the live tiles: a split of the bound would idle XCDs).
+// Placement is for speed only: every live tile is taken exactly once whatever XCD a workgroup lands on, and its output positions
+// come from the scanned table by tile index.  Returns false for a workgroup without a tile (uniform).
+constexpr uint32_t RADIX_XCDS = 8;
+__device__ __forceinline__ bool radix_tile_of(uint32_t n, uint32_t tile_size, uint32_t *tile)
+{
+    const uint32_t live = n / tile_size + (n % tile_size != 0u ? 1u : 0u);
+    const uint32_t per = (live + RADIX_XCDS - 1u) / RADIX_XCDS;
+    const uint32_t slot = blockIdx.x / RADIX_XCDS;
+    *tile = (blockIdx.x % RADIX_XCDS) * per + slot;
+    return slot < per && *tile < live;
+}
+
 // One workgroup of THREADS threads sorts a tile of THREADS * ITEMS records on a digit of up to log2(THREADS) bits: thread t
 // owns digit t in the per-digit steps.  256 threads / 4096 records for the pair sort (8-bit digits and fewer), 512 threads /
 // 8192 records for the depth sort's 9-bit digits: with twice the digit values a 4096-record tile's runs halve (8 records =
 // 32 B per array, measured +35 % per pass); doubling the tile keeps the runs at 16 records and the table reads per record equal.
 // LDS budget: the arrays of a record (key, value, second value) pass through ONE tile-sized buffer one after the other instead of
-// each having its own (three barriers more per tile): 52 KB instead of 116 KB for the depth sort's 512-thread tiles, so that three
-// workgroups share a CU instead of one — the passes are bound by the latency of a tile's dependent phases (load, rank, layout,
-// reorder, store), not by any pipe, and with one workgroup per CU a 410-tile pass ran as two rounds of 256 + 154.
+// each having its own (three barriers more per tile): 52 KB instead of 116 KB for the depth sort's 512-thread tiles, so that LDS
+// leaves room for three workgroups on a CU instead of one.  Two are resident: the scatter kernel's 117-128 VGPRs allow four waves
+// per SIMD, which is two 512-thread workgroups (sort.hip; the compiler's occupancy figure, tools/kernel_resources.sh) — the passes
+// are bound by the latency of a tile's dependent phases (load, rank, layout, reorder, store), not by any pipe, and with one
+// workgroup per CU a 410-tile pass ran as two rounds of 256 + 154.
 template <int THREADS, int ITEMS, bool HAS_V2>
 struct RadixTileSmem {
     static constexpr int TILE = THREADS * ITEMS, WAVES = THREADS / 64, DIGITS = THREADS;

@@ -14,7 +14,7 @@
 //   scatter  one workgroup per tile: per-wave ranking through LDS peer masks -> tile reordered by digit in LDS -> digit
 //            runs written out contiguously (coalesced), position = digit base + scanned hist + rank in run   (radix.h)
 // The element count lives in device memory (n_dev): grids are sized by the host-side bound and surplus workgroups fall
-// through.  16 keys per thread (2048-key tiles measured slower, the fixed per-workgroup costs dominate); the depth sort's
+// through.  Which tile a hist / scatter workgroup takes is a matter of speed only (radix_tile_of, radix.h: consecutive tiles per XCD).  16 keys per thread (2048-key tiles measured slower, the fixed per-workgroup costs dominate); the depth sort's
 // 9-bit passes run 512 threads on 8192 keys, the pair sort's <= 8-bit passes 256 threads on 4096 (radix.h says why).
 //
 // Depth sort in three passes instead of four.  z_cam >= 0.2, so a key's sign and high exponent bits never vary: the sort
@@ -54,8 +54,9 @@ __global__ __launch_bounds__(THREADS) void radix_hist_kernel(const KeyT *__restr
     uint32_t mask;
     if (!resolve_pass(ps, ctrl, &shift, &mask)) return;  // uniform: this depth-sort pass is not needed
     const uint32_t n = load_count(n_dev, n_bound);
-    const uint32_t base = blockIdx.x * (uint32_t)TILE;
-    if (base >= n) return;  // rowscan and scatter stop at the live tiles too
+    uint32_t tile;
+    if (!radix_tile_of(n, (uint32_t)TILE, &tile)) return;  // rowscan and scatter stop at the live tiles too
+    const uint32_t base = tile * (uint32_t)TILE;
     h[threadIdx.x] = 0;
     if (threadIdx.x == 0) s_max = 0;
     __syncthreads();
@@ -91,7 +92,7 @@ __global__ __launch_bounds__(THREADS) void radix_hist_kernel(const KeyT *__restr
     __syncthreads();
     // only the digit values the pass has: a 6-bit pass of the 256-thread pair sort would otherwise write (and its scatter read back)
     // four times the rows — every entry a 64-B sector of its own in this digit-major table
-    if (threadIdx.x <= mask) hist[(size_t)threadIdx.x * hist_blocks + blockIdx.x] = h[threadIdx.x];
+    if (threadIdx.x <= mask) hist[(size_t)threadIdx.x * hist_blocks + tile] = h[threadIdx.x];
     if (ps.dyn_pass == 0 && threadIdx.x == 0) {
         const uint32_t m = s_max;
         // the running maximum only grows: a stale (smaller) value read here costs one redundant atomic, never a wrong result
@@ -176,8 +177,9 @@ __global__ __launch_bounds__(THREADS, 4) void radix_scatter_kernel(
     uint32_t mask;
     if (!resolve_pass(ps, ctrl, &shift, &mask)) return;  // uniform
     const uint32_t n = load_count(n_dev, n_bound);
-    const uint32_t base = blockIdx.x * (uint32_t)TILE;
-    if (base >= n) return;  // uniform per workgroup
+    uint32_t tile;
+    if (!radix_tile_of(n, (uint32_t)TILE, &tile)) return;  // uniform per workgroup
+    const uint32_t base = tile * (uint32_t)TILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
     radix_clear(sm);
@@ -214,8 +216,8 @@ __global__ __launch_bounds__(THREADS, 4) void radix_scatter_kernel(
         const uint32_t tot = has ? ctrl->digit_tot[tid] : 0u;
         uint32_t all_total;
         const uint32_t gs = block_excl_scan<THREADS>(tot, sm.scratch, &all_total);
-        digit_base[tid] = gs + (has ? hist[(size_t)tid * hist_blocks + blockIdx.x] : 0u);
-        if (n_out != nullptr && blockIdx.x == 0 && tid == 0) *n_out = all_total;
+        digit_base[tid] = gs + (has ? hist[(size_t)tid * hist_blocks + tile] : 0u);
+        if (n_out != nullptr && tile == 0 && tid == 0) *n_out = all_total;
     }
     __syncthreads();
 
@@ -272,7 +274,9 @@ static void launch_pass(const KeyT *kin, const uint32_t *vin, const uint32_t *v2
                         const Workspace &ws, hipStream_t s)
 {
     constexpr int TILE = THREADS * ITEMS;
-    const int nblk = (int)((n_bound + TILE - 1) / TILE);
+    // a multiple of RADIX_XCDS workgroups per view: every live tile has one (radix_tile_of), and with gridDim.y = views the
+    // workgroup classes of every view fall on the same XCDs
+    const int nblk = (int)((n_bound + TILE - 1) / TILE + RADIX_XCDS - 1) / RADIX_XCDS * RADIX_XCDS;
     const uint32_t nb = (uint32_t)n_bound;
     const unsigned nv = (unsigned)ws.views;  // gridDim.y: one slice of the workspace per view (gsr_internal.h, view_slice)
     const size_t vs = ws.view_stride;
