@@ -28,7 +28,8 @@ extern "C" {
 #define GSR_VERSION 600 /* 0.6.0 (additions since, no existing entry point or struct changed: gsr_blend_features / gsr_render_features —
                             depth, alpha and caller-supplied channels composited with the colour frame's weights; gsr_blend_channels /
                             gsr_render_channels + GSR_MAX_FEATURE_CHANNELS — any number of channels, rows at a caller's stride, many channels per walk of the lists; gsr_blend_channels_backward /
-                            gsr_render_channels_backward — the transpose of gsr_blend_channels in the channels: the gradient of a map with respect to the per-gaussian rows): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            gsr_render_channels_backward — the transpose of gsr_blend_channels in the channels: the gradient of a map with respect to the per-gaussian rows; gsr_blend_pick /
+                            gsr_render_pick — per-pixel ids: the gaussian of largest weight, the one at which T crosses a threshold, the contributor count): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -332,6 +333,35 @@ int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, co
                                  size_t workspace_bytes, const float *grad_map /* [.., channels], layout per opts->output_layout */,
                                  int32_t channels, float *grad_features /* row i at + i * grad_stride */, int64_t grad_stride,
                                  void *stream);
+
+/* Stage 3 for what no blended channel can hold — per pixel p, over the same depth-ordered lists and with the same weights
+ * w_i = alpha_i T_i (and the same T, bit for bit) as gsr_blend_features (no reference counterpart):
+ *   out_best_id[p]   = the gaussian of largest w_i(p), -1 where no gaussian has w > 0;   out_best_w[p] = that weight (0 with -1);
+ *   out_median_id[p] = the first gaussian in draw order AFTER which the transmittance T is < median_T, -1 if T never gets there:
+ *                      median_T = 0.5 is the "median depth" gaussian of 2DGS / gsplat, which ignores floaters that pull
+ *                      sum w z forward; median_T = 1 the first gaussian with w > 0;
+ *   out_count[p]     = how many gaussians have w_i(p) > 0.
+ * Ids are indices into the caller's scene arrays (the order gsr_preprocess was given them in).  At EXACTLY equal weights the earlier
+ * gaussian in draw order wins; at exactly equal depth the draw order is array-index order, as elsewhere (GsrScene).  Pixels the
+ * frame never draws (the last column / row of reference_compat) hold -1, 0, -1, 0.  Each output is one [H,W] plane of 4-byte values
+ * in opts->output_layout (image [H,W], screen [W,H] or strip [rows * 16, W]); any of the four may be NULL, not all.  out_count == NULL
+ * selects a walk that stops earlier: once a pixel's median is found and T <= best_w no later gaussian can change either id
+ * (w' = fl(alpha' T') <= T' <= T <= best_w and the maximum is strict) — exact, like every stop at early_out_T = 0; with out_count the
+ * walk is gsr_blend_features' (T == 0.0f) and so are wave_entries / fetched_entries.  early_out_T > 0: gaussians behind T <= early_out_T
+ * are not seen — an approximation, as in the feature blend.
+ * An alternative stage 3 like gsr_blend_features: needs gsr_preprocess and gsr_bin_sort on the workspace first, may be called any
+ * number of times and mixes freely with gsr_blend and the feature blends (it reads the records' geometry and opacity only, never
+ * their colour words, and leaves the launch-order hint alone).  Honoured and ignored options are gsr_blend_features'.
+ * GSR_ERR_BAD_ARG, before any HIP call or look at the workspace, for a null camera or options, all four outputs NULL, median_T NaN or
+ * outside (0, 1], output_dtype = 1, accum_dtype = 1.  Single views.  gsr_read_stats afterwards describes this walk (wave_entries,
+ * fetched_entries; colour_evals = 0). */
+int gsr_blend_pick(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
+                   float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id, int32_t *out_count, void *stream);
+
+/* Stages 1-3 back to back with gsr_blend_pick as stage 3; the preprocess runs as with colour_stage = 0, like gsr_render_features'. */
+int gsr_render_pick(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                    size_t workspace_bytes, float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id,
+                    int32_t *out_count, void *stream);
 
 /* Several views of ONE resident scene (the reference renders one view per process, rasterize.py:315-329; BASELINE configs[3] is a
  * camera set).  cams[n_cams] [host] must share width/height; frame i goes to out_images + i * frame_stride (in elements of the

@@ -129,6 +129,7 @@ EXPORTS = [
     "gsr_render_batch", "gsr_render_batch_slots", "gsr_scene_order", "gsr_scene_order_bytes", "gsr_scene_bounds", "gsr_block_visibility", "gsr_project_to_camera_space", "gsr_compute_2d_covariance", "gsr_compute_covering_bbox", "gsr_rasterize_gaussian",
     "gsr_blend_features", "gsr_render_features", "gsr_blend_channels", "gsr_render_channels",
     "gsr_blend_channels_backward", "gsr_render_channels_backward",
+    "gsr_blend_pick", "gsr_render_pick",
 ]
 
 
@@ -159,6 +160,8 @@ def _load() -> C.CDLL:
     L.gsr_render_channels.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp]
     L.gsr_blend_channels_backward.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, vp, i64, vp]
     L.gsr_render_channels_backward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, vp, i64, vp]
+    L.gsr_blend_pick.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, C.c_float, vp, vp, vp, vp, vp]
+    L.gsr_render_pick.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, C.c_float, vp, vp, vp, vp, vp]
     L.gsr_render_forward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
     L.gsr_render_batch.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, vp, sz, vp, i64, vp]
     L.gsr_render_batch_slots.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, C.POINTER(vp), sz,

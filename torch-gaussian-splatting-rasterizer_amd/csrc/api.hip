@@ -552,6 +552,55 @@ int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, co
     return launch_blend_channels_backward(*cam, o, ws, plan, grad_map, channels, grad_features, grad_stride, s);
 }
 
+// What gsr_blend_pick / gsr_render_pick refuse before anything else (and before any HIP call)
+static int check_pick(const GsrCamera *cam, const GsrOptions *opts, float median_T, const int32_t *out_best_id, const float *out_best_w,
+                      const int32_t *out_median_id, const int32_t *out_count)
+{
+    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    if (!out_best_id && !out_best_w && !out_median_id && !out_count) { set_error("null pick outputs: all four"); return GSR_ERR_BAD_ARG; }
+    if (!(median_T > 0.0f && median_T <= 1.0f)) {  // (a NaN fails both compares)
+        set_error("bad median_T %g (0 < median_T <= 1)", (double)median_T); return GSR_ERR_BAD_ARG;
+    }
+    if (opts->output_dtype == 1) { set_error("pick maps are int32 / float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("pick weights are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+int gsr_blend_pick(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
+                   float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id, int32_t *out_count, void *stream)
+{
+    int rc = check_pick(cam, opts, median_T, out_best_id, out_best_w, out_median_id, out_count);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    return launch_blend_pick(*cam, *opts, ws, plan_frame(ws, *opts), median_T, out_best_id, out_best_w, out_median_id, out_count,
+                             static_cast<hipStream_t>(stream));
+}
+
+int gsr_render_pick(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                    size_t workspace_bytes, float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id,
+                    int32_t *out_count, void *stream)
+{
+    int rc = check_pick(cam, opts, median_T, out_best_id, out_best_w, out_median_id, out_count);
+    if (rc) return rc;
+    rc = check_scene(scene);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    GsrOptions o = *opts;
+    o.colour_stage = 0;  // as in gsr_render_features: no SH row is read, the records keep their "unevaluated" marks
+    const FramePlan plan = plan_frame(ws, o);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
+    if (rc) return rc;
+    rc = bin_sort_impl(&o, ws, plan, s);
+    if (rc) return rc;
+    return launch_blend_pick(*cam, o, ws, plan, median_T, out_best_id, out_best_w, out_median_id, out_count, s);
+}
+
 // How many views go through one launch sequence: as many slices as the workspace holds, at most MAX_VIEWS, GsrOptions.batch_views
 // (when set) and the views there are.  0: the workspace does not hold one view.
 static int views_per_launch(const GsrScene *scene, const GsrCamera *cam0, const GsrOptions *opts, int64_t max_pairs, size_t workspace_bytes, int32_t n_cams)

@@ -243,6 +243,10 @@ int launch_blend_channels(const GsrCamera &cam, const GsrOptions &opts, const Wo
 // The transpose of launch_blend_channels in the channels (blend_channels_backward.hip): grad_features[i] += sum_p w_i(p) grad_map[p]
 int launch_blend_channels_backward(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
                                    const float *grad_map, int channels, float *grad_features, int64_t stride, hipStream_t s);
+// Stage 3 for ids (blend_pick.hip): per pixel the gaussian of largest weight (+ that weight), the first one after which T < median_T,
+// and (out_count != nullptr: the COUNT kernel) how many had w > 0.  Any output may be null; single views only
+int launch_blend_pick(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, float median_T,
+                      int32_t *out_best_id, float *out_best_w, int32_t *out_median_id, int32_t *out_count, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

@@ -8,7 +8,7 @@ per-pixel work happens in libgsr.so through the C ABI (include/gsr.h).
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Mapping, Optional
+from typing import Dict, Mapping, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -333,6 +333,25 @@ def file_order_gradient(buf: torch.Tensor, order_t: Optional[torch.Tensor]) -> t
     if order_t is None:
         return buf
     return torch.empty_like(buf).index_copy_(0, order_t, buf)
+
+
+def file_order_ids(ids: torch.Tensor, order_t: Optional[torch.Tensor]) -> torch.Tensor:
+    """A map of gaussian ids in the scene's order (indices into its resident arrays, -1 = none) -> the same map with ids of the
+    file the scene was loaded from: id j becomes order_t[j], -1 stays -1.  order_t=None: the scene kept the file's order and `ids`
+    itself is returned.  Works on CPU and GPU tensors."""
+    if order_t is None:
+        return ids
+    file_ids = order_t.to(ids.dtype)[ids.clamp(min=0).long()]
+    return torch.where(ids < 0, ids, file_ids)
+
+
+class PickMaps(NamedTuple):
+    """Rasterizer.render_pick: per pixel the gaussian of largest blend weight and that weight, the gaussian after which T first
+    falls below median_T, and (count=True) how many gaussians contributed.  Ids are int32, -1 = none."""
+    best_id: torch.Tensor
+    best_w: torch.Tensor
+    median_id: torch.Tensor
+    count: Optional[torch.Tensor]
 
 
 class _RenderFeatures(torch.autograd.Function):
@@ -731,6 +750,72 @@ class Rasterizer:
             return img, maps[0][..., 0].contiguous(), maps[0][..., 1].contiguous()
 
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "frame")
+
+    # -- per-pixel gaussian ids ---------------------------------------------------------------------------------------------------
+    def _enqueue_pick(self, cam: GsrCamera, opts: GsrOptions, median_T: float, count: bool):
+        """One preprocess, one bin / sort and one gsr_blend_pick (gsr_render_pick) on the current stream, unchecked like enqueue().
+        Returns (best_id, best_w, median_id, count or None) with the ids as the kernel wrote them (the scene's order)."""
+        ws = self._workspace(cam.width, cam.height)
+        _, shape = self._out_shape(cam, opts)
+        dev = self.scene.device
+        # strips may include rows below the frame's last pixel row: they read "nothing drawn"
+        best_id = torch.full(shape, -1, dtype=torch.int32, device=dev)
+        best_w = torch.zeros(shape, dtype=torch.float32, device=dev)
+        median_id = torch.full(shape, -1, dtype=torch.int32, device=dev)
+        cnt = torch.zeros(shape, dtype=torch.int32, device=dev) if count else None
+        if best_id.numel() == 0:  # a shard that owns no tile row
+            self.unchecked.wrote(0)
+            return best_id, best_w, median_id, cnt
+        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
+            opts = GsrOptions.from_buffer_copy(opts)
+            opts.keep_flags = 1
+        sc = self.scene.c_struct()
+        check(lib.gsr_render_pick(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), float(median_T),
+                                  best_id.data_ptr(), best_w.data_ptr(), median_id.data_ptr(), cnt.data_ptr() if count else None,
+                                  _stream_ptr(dev)))
+        self.unchecked.wrote(1)
+        return best_id, best_w, median_id, cnt
+
+    def render_pick(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, median_T: float = 0.5, count: bool = False,
+                    scene_order: bool = False) -> PickMaps:
+        """Per pixel, over the colour frame's depth-ordered lists and with its weights w_i = alpha_i T_i (gsr_render_pick):
+        best_id = the gaussian of largest weight and best_w that weight (-1 / 0 where nothing was drawn; at exactly equal weights the
+        earlier gaussian in draw order), median_id = the first gaussian in draw order after which T < median_T (0.5: the median-depth
+        surface; 1.0: the first hit; -1 where T never gets there), and with count=True how many gaussians had w > 0 (the walk then
+        runs to T == 0 like the feature blend; without it it stops as soon as neither id can change).  int32 / float32 [H, W] maps
+        (layouts as render()).  Ids index the file the scene was loaded from (scene_order=True: the scene's resident arrays, as the
+        kernel wrote them).  One preprocess and one bin / sort per call; checked and re-rendered on overflow like render()."""
+        if not 0.0 < float(median_T) <= 1.0:
+            raise ValueError(f"median_T must lie in (0, 1], got {median_T}")
+
+        def attempt(o):
+            return self._enqueue_pick(cam, o, median_T, count)
+
+        best_id, best_w, median_id, cnt = _render_checked([self], [None], opts or make_options(), attempt, 8, "pick map")
+        if not scene_order:
+            best_id, median_id = file_order_ids(best_id, self.scene.order_t), file_order_ids(median_id, self.scene.order_t)
+        return PickMaps(best_id, best_w, median_id, cnt)
+
+    def render_median_depth(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, median_T: float = 0.5) -> torch.Tensor:
+        """[H, W] float32: the camera-space depth z_cam of render_pick's median_id — the depth at which the transmittance falls below
+        median_T, which floaters in front of a surface do not pull forward the way they pull render_depth's sum_i w_i z_i — and 0
+        where no gaussian takes T there."""
+        ids = self.render_pick(cam, opts, median_T, scene_order=True).median_id
+        z = self._depth_features(cam)[:, 0]
+        if self.scene.n == 0:
+            return torch.zeros(ids.shape, dtype=torch.float32, device=self.scene.device)
+        return torch.where(ids >= 0, z[ids.clamp(min=0).long()], torch.zeros((), dtype=torch.float32, device=self.scene.device))
+
+    def pick(self, cam: GsrCamera, x: int, y: int, opts: Optional[GsrOptions] = None):
+        """(best_id, median_id) of pixel (x, y) as Python ints, in file order (-1: nothing there): click-to-select.  A convenience over
+        render_pick (median_T = 0.5) for the whole-frame image layout."""
+        opts = opts or make_options()
+        if opts.output_layout != 0:
+            raise ValueError("pick() addresses pixels of the image layout (output_layout = 0)")
+        if not (0 <= int(x) < cam.width and 0 <= int(y) < cam.height):
+            raise ValueError(f"pixel ({x}, {y}) lies outside the {cam.width}x{cam.height} frame")
+        m = self.render_pick(cam, opts)
+        return int(m.best_id[int(y), int(x)]), int(m.median_id[int(y), int(x)])
 
     def _batch_out(self, cams, opts: GsrOptions, out: Optional[torch.Tensor]):
         """(out, frame_stride in elements) of a batch: whole frames [B,H,W,3], or with a tile-row shard (output_layout = 2) the
