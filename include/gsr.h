@@ -29,7 +29,8 @@ extern "C" {
                             depth, alpha and caller-supplied channels composited with the colour frame's weights; gsr_blend_channels /
                             gsr_render_channels + GSR_MAX_FEATURE_CHANNELS — any number of channels, rows at a caller's stride, many channels per walk of the lists; gsr_blend_channels_backward /
                             gsr_render_channels_backward — the transpose of gsr_blend_channels in the channels: the gradient of a map with respect to the per-gaussian rows; gsr_blend_pick /
-                            gsr_render_pick — per-pixel ids: the gaussian of largest weight, the one at which T crosses a threshold, the contributor count): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            gsr_render_pick — per-pixel ids: the gaussian of largest weight, the one at which T crosses a threshold, the contributor count; gsr_blend_topk /
+                            gsr_render_topk + GSR_MAX_TOPK — per-pixel contributor lists: the k heaviest or the k nearest gaussians of a pixel with their weights): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -362,6 +363,45 @@ int gsr_blend_pick(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int6
 int gsr_render_pick(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id,
                     int32_t *out_count, void *stream);
+
+/* Stage 3 for per-pixel contributor LISTS — of every pixel p the k gaussians that make it, ids and weights (no reference
+ * counterpart).  k is 1 .. GSR_MAX_TOPK, `select` one of GSR_TOPK_HEAVIEST / GSR_TOPK_NEAREST.
+ * Lists, weights and T.  The lists are the depth-ordered lists of gsr_blend_features, the weights are w_i = alpha_i T_i, bit for bit
+ * that kernel's, and so is T.  out_ids[p * k + j] and out_weights[p * k + j] hold slot j = 0 .. k-1 of pixel p, p laid out per
+ * opts->output_layout: [H,W,k], [W,H,k] or the strip [rows * 16, W, k]; the k values of a pixel are contiguous and the stride is
+ * exactly k.
+ *   GSR_TOPK_HEAVIEST: the slots are sorted by weight, descending; only w > 0 enters.  At EXACTLY equal weights the earlier gaussian
+ *     in draw order comes first — so if the k-th and a later one tie, the earlier keeps the slot (gsr_blend_pick's strict compare
+ *     for best_id, generalised: k = 1 is best_id / best_w).
+ *   GSR_TOPK_NEAREST: the slots are in draw order: the first k gaussians with w > 0 (k = 1 is gsr_blend_pick's median_id at
+ *     median_T = 1).
+ * Unused slots hold id -1 and weight 0; pixels the frame never draws (the last column / row of reference_compat) hold -1 / 0 in
+ * every slot.  Ids are indices into the caller's scene arrays (the order gsr_preprocess was given them in); at exactly equal depth
+ * the draw order is array-index order, as elsewhere (GsrScene).
+ * out_ids or out_weights may be NULL, not both.  out_final_T: [H,W] float32 in the same layout (1 where the frame never draws), or
+ * NULL.
+ * Stop rule.  With out_final_T the walk is gsr_blend_features': a quadrant stops once T <= early_out_T for its pixels, because T
+ * itself is an output, and wave_entries / fetched_entries are that kernel's.  Without it a quadrant also stops once none of its lists
+ * can change: HEAVIEST — T <= the weight in slot k-1 (a later w' = fl(alpha' T') <= T' <= T <= w_k, so the strict `>` fails, and fails
+ * forever because T only shrinks); NEAREST — slot k-1 is filled (or T == 0); undrawn pixels from the start.  All exact at
+ * early_out_T = 0.  early_out_T > 0 is the feature blend's approximation: gaussians behind T <= early_out_T are not seen, and the
+ * lists are the top k of the weights gsr_blend_features composites at that early_out_T, with or without out_final_T.
+ * An alternative stage 3 like gsr_blend_features: needs gsr_preprocess and gsr_bin_sort on the workspace first, may be called any
+ * number of times and mixes freely with gsr_blend, the feature blends and gsr_blend_pick (it reads the records' geometry and opacity
+ * only, never their colour words, and only reads the launch-order hint).  Honoured and ignored options are gsr_blend_features'.
+ * GSR_ERR_BAD_ARG, before any HIP call or look at the workspace, for a null camera or options, out_ids and out_weights both NULL,
+ * k < 1 or > GSR_MAX_TOPK, select not 0 or 1, output_dtype = 1, accum_dtype = 1.  Single views.  gsr_read_stats afterwards describes
+ * this walk (wave_entries, fetched_entries; colour_evals = 0). */
+#define GSR_MAX_TOPK 16
+#define GSR_TOPK_HEAVIEST 0   /* the k largest weights, heaviest first */
+#define GSR_TOPK_NEAREST  1   /* the first k gaussians in draw order with w > 0, nearest first */
+int gsr_blend_topk(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
+                   int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T, void *stream);
+
+/* Stages 1-3 back to back with gsr_blend_topk as stage 3; the preprocess runs as with colour_stage = 0, like gsr_render_features'. */
+int gsr_render_topk(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                    size_t workspace_bytes, int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T,
+                    void *stream);
 
 /* Several views of ONE resident scene (the reference renders one view per process, rasterize.py:315-329; BASELINE configs[3] is a
  * camera set).  cams[n_cams] [host] must share width/height; frame i goes to out_images + i * frame_stride (in elements of the

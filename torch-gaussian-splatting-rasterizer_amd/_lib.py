@@ -29,6 +29,8 @@ GSR_MAX_FRAME_SIDE = 65535 * 16
 GSR_MAX_BATCH_VIEWS = 8
 GSR_BOUNDS_BLOCK = 64
 GSR_MAX_FEATURE_CHANNELS = 1024  # gsr_blend_channels / gsr_render_channels
+GSR_MAX_TOPK = 16                 # gsr_blend_topk / gsr_render_topk
+GSR_TOPK_HEAVIEST, GSR_TOPK_NEAREST = 0, 1
 
 
 class GsrError(RuntimeError):
@@ -130,6 +132,7 @@ EXPORTS = [
     "gsr_blend_features", "gsr_render_features", "gsr_blend_channels", "gsr_render_channels",
     "gsr_blend_channels_backward", "gsr_render_channels_backward",
     "gsr_blend_pick", "gsr_render_pick",
+    "gsr_blend_topk", "gsr_render_topk",
 ]
 
 
@@ -162,6 +165,8 @@ def _load() -> C.CDLL:
     L.gsr_render_channels_backward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, vp, i64, vp]
     L.gsr_blend_pick.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, C.c_float, vp, vp, vp, vp, vp]
     L.gsr_render_pick.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, C.c_float, vp, vp, vp, vp, vp]
+    L.gsr_blend_topk.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, i32, i32, vp, vp, vp, vp]
+    L.gsr_render_topk.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, i32, i32, vp, vp, vp, vp]
     L.gsr_render_forward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
     L.gsr_render_batch.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, vp, sz, vp, i64, vp]
     L.gsr_render_batch_slots.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, C.POINTER(vp), sz,

@@ -601,6 +601,55 @@ int gsr_render_pick(const GsrScene *scene, const GsrCamera *cam, const GsrOption
     return launch_blend_pick(*cam, o, ws, plan, median_T, out_best_id, out_best_w, out_median_id, out_count, s);
 }
 
+// What gsr_blend_topk / gsr_render_topk refuse before anything else (and before any HIP call)
+static int check_topk(const GsrCamera *cam, const GsrOptions *opts, int32_t k, int32_t select, const int32_t *out_ids, const float *out_weights)
+{
+    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    if (!out_ids && !out_weights) { set_error("null top-k outputs: both ids and weights"); return GSR_ERR_BAD_ARG; }
+    if (k < 1 || k > GSR_MAX_TOPK) { set_error("bad k %d (1 .. %d)", k, GSR_MAX_TOPK); return GSR_ERR_BAD_ARG; }
+    if (select != GSR_TOPK_HEAVIEST && select != GSR_TOPK_NEAREST) {
+        set_error("bad select %d (GSR_TOPK_HEAVIEST = 0, GSR_TOPK_NEAREST = 1)", select); return GSR_ERR_BAD_ARG;
+    }
+    if (opts->output_dtype == 1) { set_error("top-k lists are int32 / float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("top-k weights are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+int gsr_blend_topk(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
+                   int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T, void *stream)
+{
+    int rc = check_topk(cam, opts, k, select, out_ids, out_weights);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    return launch_blend_topk(*cam, *opts, ws, plan_frame(ws, *opts), k, select, out_ids, out_weights, out_final_T,
+                             static_cast<hipStream_t>(stream));
+}
+
+int gsr_render_topk(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                    size_t workspace_bytes, int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T,
+                    void *stream)
+{
+    int rc = check_topk(cam, opts, k, select, out_ids, out_weights);
+    if (rc) return rc;
+    rc = check_scene(scene);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    GsrOptions o = *opts;
+    o.colour_stage = 0;  // as in gsr_render_features: no SH row is read, the records keep their "unevaluated" marks
+    const FramePlan plan = plan_frame(ws, o);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
+    if (rc) return rc;
+    rc = bin_sort_impl(&o, ws, plan, s);
+    if (rc) return rc;
+    return launch_blend_topk(*cam, o, ws, plan, k, select, out_ids, out_weights, out_final_T, s);
+}
+
 // How many views go through one launch sequence: as many slices as the workspace holds, at most MAX_VIEWS, GsrOptions.batch_views
 // (when set) and the views there are.  0: the workspace does not hold one view.
 static int views_per_launch(const GsrScene *scene, const GsrCamera *cam0, const GsrOptions *opts, int64_t max_pairs, size_t workspace_bytes, int32_t n_cams)

@@ -247,6 +247,10 @@ int launch_blend_channels_backward(const GsrCamera &cam, const GsrOptions &opts,
 // and (out_count != nullptr: the COUNT kernel) how many had w > 0.  Any output may be null; single views only
 int launch_blend_pick(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, float median_T,
                       int32_t *out_best_id, float *out_best_w, int32_t *out_median_id, int32_t *out_count, hipStream_t s);
+// Stage 3 for contributor lists (blend_topk.hip): per pixel the k heaviest (select 0) or nearest (1) gaussians with w > 0, ids and
+// weights [.., k]; one of the two may be null, out_final_T may be (and then the walk stops once no list can change); single views only
+int launch_blend_topk(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, int k, int select,
+                      int32_t *out_ids, float *out_weights, float *out_final_T, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

@@ -354,6 +354,35 @@ class PickMaps(NamedTuple):
     count: Optional[torch.Tensor]
 
 
+class TopK(NamedTuple):
+    """Rasterizer.render_topk: per pixel the k heaviest (or nearest) gaussians and their blend weights.  ids: int32 [H, W, k], -1 =
+    unused slot; weights: float32 [H, W, k], 0 with -1; final_T: float32 [H, W], or None when it was not asked for."""
+    ids: torch.Tensor
+    weights: torch.Tensor
+    final_T: Optional[torch.Tensor]
+
+
+TOPK_SELECT = {"heaviest": _lib.GSR_TOPK_HEAVIEST, "nearest": _lib.GSR_TOPK_NEAREST}
+
+
+def topk_composite(topk: TopK, features: torch.Tensor) -> torch.Tensor:
+    """[H, W, C] = sum_j weights[..., j] * features[ids[..., j]], slots with id -1 contributing 0: the sparse approximation of
+    render_features(cam, features) from a pixel's k listed gaussians, for any C.  `features`: [n, C] on the lists' device, rows in
+    the order the ids index (the file's, unless the lists were rendered with scene_order=True).  Plain torch: differentiable in
+    `features` through autograd; not a kernel, and not bit for bit any blend's sum.  Memory: one [H, W, C] gather per slot (autograd
+    keeps the k index maps and weight planes, not the gathers)."""
+    ids, weights = topk.ids, topk.weights
+    if features.dim() != 2:
+        raise ValueError(f"features must be [n, C], got {tuple(features.shape)}")
+    out = None
+    for j in range(ids.shape[-1]):  # slot by slot: the largest temporary is [H, W, C], not [H, W, k, C]
+        idj = ids[..., j]
+        wj = torch.where(idj >= 0, weights[..., j], torch.zeros_like(weights[..., j])).to(features.dtype)
+        term = wj.unsqueeze(-1) * features[idj.clamp(min=0).long()]
+        out = term if out is None else out + term
+    return out
+
+
 class _RenderFeatures(torch.autograd.Function):
     """render_features as a differentiable function of the features alone: the map is linear in them, so the backward is the
     transpose under the same camera and options (Rasterizer.feature_gradient); nothing flows to the geometry or the opacities."""
@@ -795,6 +824,51 @@ class Rasterizer:
         if not scene_order:
             best_id, median_id = file_order_ids(best_id, self.scene.order_t), file_order_ids(median_id, self.scene.order_t)
         return PickMaps(best_id, best_w, median_id, cnt)
+
+    # -- per-pixel contributor lists --------------------------------------------------------------------------------------------
+    def _enqueue_topk(self, cam: GsrCamera, opts: GsrOptions, k: int, select: int, return_T: bool):
+        """One preprocess, one bin / sort and one gsr_blend_topk (gsr_render_topk) on the current stream, unchecked like enqueue().
+        Returns (ids, weights, final_T or None) with the ids as the kernel wrote them (the scene's order)."""
+        ws = self._workspace(cam.width, cam.height)
+        _, shape = self._out_shape(cam, opts)
+        dev = self.scene.device
+        # strips may include rows below the frame's last pixel row: they read "nothing drawn"
+        ids = torch.full(tuple(shape) + (k,), -1, dtype=torch.int32, device=dev)
+        weights = torch.zeros(tuple(shape) + (k,), dtype=torch.float32, device=dev)
+        final_T = torch.ones(shape, dtype=torch.float32, device=dev) if return_T else None
+        if ids.numel() == 0:  # a shard that owns no tile row
+            self.unchecked.wrote(0)
+            return ids, weights, final_T
+        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
+            opts = GsrOptions.from_buffer_copy(opts)
+            opts.keep_flags = 1
+        sc = self.scene.c_struct()
+        check(lib.gsr_render_topk(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), k, select,
+                                  ids.data_ptr(), weights.data_ptr(), final_T.data_ptr() if return_T else None, _stream_ptr(dev)))
+        self.unchecked.wrote(1)
+        return ids, weights, final_T
+
+    def render_topk(self, cam: GsrCamera, k: int, opts: Optional[GsrOptions] = None, select: str = "heaviest", return_T: bool = False,
+                    scene_order: bool = False) -> TopK:
+        """Per pixel, over the colour frame's depth-ordered lists and with its weights w_i = alpha_i T_i (gsr_render_topk), k of the
+        gaussians that make it: select="heaviest" — the k largest weights, heaviest first (at exactly equal weights the earlier
+        gaussian in draw order first); select="nearest" — the first k gaussians in draw order with w > 0.  ids int32 [H, W, k] and
+        weights float32 [H, W, k] (layouts as render()), unused slots -1 / 0, 1 <= k <= 16.  return_T=True adds the final
+        transmittance [H, W] and walks the lists like the feature blend; without it a quadrant stops as soon as none of its lists
+        can change.  Ids index the file the scene was loaded from (scene_order=True: the scene's resident arrays, as the kernel
+        wrote them).  One preprocess and one bin / sort per call; checked and re-rendered on overflow like render()."""
+        if isinstance(k, bool) or int(k) != k or not 1 <= int(k) <= _lib.GSR_MAX_TOPK:
+            raise ValueError(f"k must be an integer in 1 .. {_lib.GSR_MAX_TOPK}, got {k}")
+        if select not in TOPK_SELECT:
+            raise ValueError(f"select must be one of {sorted(TOPK_SELECT)}, got {select!r}")
+
+        def attempt(o):
+            return self._enqueue_topk(cam, o, int(k), TOPK_SELECT[select], return_T)
+
+        ids, weights, final_T = _render_checked([self], [None], opts or make_options(), attempt, 8, "top-k lists")
+        if not scene_order:
+            ids = file_order_ids(ids, self.scene.order_t)
+        return TopK(ids, weights, final_T)
 
     def render_median_depth(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, median_T: float = 0.5) -> torch.Tensor:
         """[H, W] float32: the camera-space depth z_cam of render_pick's median_id — the depth at which the transmittance falls below
