@@ -30,7 +30,8 @@ extern "C" {
                             gsr_render_channels + GSR_MAX_FEATURE_CHANNELS — any number of channels, rows at a caller's stride, many channels per walk of the lists; gsr_blend_channels_backward /
                             gsr_render_channels_backward — the transpose of gsr_blend_channels in the channels: the gradient of a map with respect to the per-gaussian rows; gsr_blend_pick /
                             gsr_render_pick — per-pixel ids: the gaussian of largest weight, the one at which T crosses a threshold, the contributor count; gsr_blend_topk /
-                            gsr_render_topk + GSR_MAX_TOPK — per-pixel contributor lists: the k heaviest or the k nearest gaussians of a pixel with their weights): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            gsr_render_topk + GSR_MAX_TOPK — per-pixel contributor lists: the k heaviest or the k nearest gaussians of a pixel with their weights; gsr_blend_slab /
+                            gsr_render_slab — gsr_blend_channels between two per-pixel depth limits: a depth test against a z-buffer, section planes, depth layers): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -402,6 +403,45 @@ int gsr_blend_topk(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int6
 int gsr_render_topk(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T,
                     void *stream);
+
+/* Stage 3 for caller-supplied channels BETWEEN TWO PER-PIXEL DEPTH LIMITS (no reference counterpart): gsr_blend_channels restricted,
+ * pixel by pixel, to a part of the depth range — the splats in front of a mesh z-buffer, behind a section plane, behind the median
+ * surface, one layer of a layered depth image.
+ * Semantics.  depth_near and depth_far are [H,W] float32 planes [device], laid out per opts->output_layout exactly like out_final_T;
+ * either may be NULL: no limit on that side.  Pixel p composites the gaussians with
+ *     depth_near[p] <= z_i   and   z_i < depth_far[p]
+ * (>= on the near side, < on the far side: consecutive slabs [a,b), [b,c) partition the range) and no others:
+ *     out_map[p][c] = sum_i w_i(p) f_i[c],   out_final_T[p] = prod_i (1 - alpha_i(p))   over those gaussians, in draw order,
+ * with T starting at 1 at the near limit: a gaussian in front of it is SKIPPED, not blended — it neither adds to the map nor dims
+ * what lies behind it.  The arithmetic per gaussian is gsr_blend_channels'; with both planes NULL (or -inf / +inf everywhere) the map
+ * and T are that function's bit for bit, and so are wave_entries / fetched_entries.
+ * z_i is CAMERA-SPACE LINEAR DEPTH, the unit of the depth maps (f = z_cam through the feature blends), not NDC / z-buffer depth: the
+ * float the depth sort orders the gaussians by, ((x * w2c[2] + y * w2c[6]) + z * w2c[10]) + w2c[14] evaluated in fp32 in exactly this
+ * order without fused multiply-adds — the same bits as GsrDebugOut.cam_means[3 * i + 2].  A caller with an OpenGL-style depth buffer
+ * linearises it first.
+ * If either limit of a pixel is NaN, or depth_far[p] <= depth_near[p], the pixel draws nothing: its map is 0 and its T is 1.  Pixels
+ * the frame never draws (the last column / row of reference_compat) hold 0 / 1 whatever the limits say.
+ * Stop rule.  The lists are in ascending z (ties in array-index order), so a far limit keeps a prefix: a quadrant stops once every
+ * pixel of it has T <= early_out_T, as in gsr_blend_channels, or — exactly — once the list has reached the largest far limit of its
+ * pixels; the tile stops fetching when its four quadrants have.  Entries in front of the smallest near limit of a quadrant are
+ * staged but never evaluated, and are not counted in wave_entries.
+ * features / channels / feature_stride / out_map / out_final_T: gsr_blend_channels'.  scene may be NULL, as for gsr_blend: the means
+ * are then read through the pointer the last gsr_preprocess on this workspace was given (which must still be valid); a non-NULL
+ * scene must have scene->n == n.  An alternative stage 3 like gsr_blend_channels: needs gsr_preprocess and gsr_bin_sort on the
+ * workspace first, may be called any number of times (one call per layer of a layered depth image) and mixes freely with the other
+ * blends.  Honoured and ignored options are gsr_blend_channels' (draw_limit, early_out_T, the layouts and tile-row shards included).
+ * GSR_ERR_BAD_ARG, before any HIP call or look at the workspace, for gsr_blend_channels' cases: a null camera, null options, null
+ * features, a null out_map, channels < 1 or > GSR_MAX_FEATURE_CHANNELS, feature_stride < channels, output_dtype = 1, accum_dtype = 1.
+ * Single views.  No backward.  gsr_read_stats afterwards describes this walk (wave_entries, fetched_entries; colour_evals = 0). */
+int gsr_blend_slab(const GsrScene *scene /* may be NULL */, int64_t n, const GsrCamera *cam, const GsrOptions *opts,
+                   int64_t max_pairs, void *workspace, size_t workspace_bytes, const float *features, int32_t channels,
+                   int64_t feature_stride, const float *depth_near, const float *depth_far, float *out_map,
+                   float *out_final_T, void *stream);
+
+/* Stages 1-3 back to back with gsr_blend_slab as stage 3; the preprocess runs as with colour_stage = 0, like gsr_render_features'. */
+int gsr_render_slab(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                    size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride,
+                    const float *depth_near, const float *depth_far, float *out_map, float *out_final_T, void *stream);
 
 /* Several views of ONE resident scene (the reference renders one view per process, rasterize.py:315-329; BASELINE configs[3] is a
  * camera set).  cams[n_cams] [host] must share width/height; frame i goes to out_images + i * frame_stride (in elements of the

@@ -133,6 +133,7 @@ EXPORTS = [
     "gsr_blend_channels_backward", "gsr_render_channels_backward",
     "gsr_blend_pick", "gsr_render_pick",
     "gsr_blend_topk", "gsr_render_topk",
+    "gsr_blend_slab", "gsr_render_slab",
 ]
 
 
@@ -167,6 +168,8 @@ def _load() -> C.CDLL:
     L.gsr_render_pick.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, C.c_float, vp, vp, vp, vp, vp]
     L.gsr_blend_topk.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, i32, i32, vp, vp, vp, vp]
     L.gsr_render_topk.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, i32, i32, vp, vp, vp, vp]
+    L.gsr_blend_slab.argtypes = [C.POINTER(GsrScene), i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp, vp, vp]
+    L.gsr_render_slab.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp, vp, vp]
     L.gsr_render_forward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
     L.gsr_render_batch.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, vp, sz, vp, i64, vp]
     L.gsr_render_batch_slots.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, C.POINTER(vp), sz,

@@ -498,6 +498,49 @@ int gsr_render_channels(const GsrScene *scene, const GsrCamera *cam, const GsrOp
     return launch_blend_channels(*cam, o, ws, plan, features, channels, feature_stride, out_map, out_final_T, s);
 }
 
+// What gsr_blend_slab / gsr_render_slab refuse before anything else (and before any HIP call): gsr_blend_channels' cases; the depth
+// planes may be null
+int gsr_blend_slab(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                   size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, const float *depth_near,
+                   const float *depth_far, float *out_map, float *out_final_T, void *stream)
+{
+    int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
+    if (rc) return rc;
+    if (scene) {
+        rc = check_scene(scene);
+        if (rc) return rc;
+        if (scene->n != n) { set_error("scene->n = %lld but n = %lld", (long long)scene->n, (long long)n); return GSR_ERR_BAD_ARG; }
+    }
+    Workspace ws;
+    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    return launch_blend_slab(*cam, *opts, ws, plan_frame(ws, *opts), scene ? scene->means : nullptr, features, channels, feature_stride,
+                             depth_near, depth_far, out_map, out_final_T, static_cast<hipStream_t>(stream));
+}
+
+int gsr_render_slab(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                    size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, const float *depth_near,
+                    const float *depth_far, float *out_map, float *out_final_T, void *stream)
+{
+    int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
+    if (rc) return rc;
+    rc = check_scene(scene);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    GsrOptions o = *opts;
+    o.colour_stage = 0;  // as in gsr_render_features: no SH row is read, the records keep their "unevaluated" marks
+    const FramePlan plan = plan_frame(ws, o);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
+    if (rc) return rc;
+    rc = bin_sort_impl(&o, ws, plan, s);
+    if (rc) return rc;
+    return launch_blend_slab(*cam, o, ws, plan, scene->means, features, channels, feature_stride, depth_near, depth_far, out_map,
+                             out_final_T, s);
+}
+
 // What gsr_blend_channels_backward / gsr_render_channels_backward refuse before anything else (and before any HIP call)
 static int check_channels_backward(const GsrCamera *cam, const GsrOptions *opts, const float *grad_map, int32_t channels,
                                    const float *grad_features, int64_t grad_stride)

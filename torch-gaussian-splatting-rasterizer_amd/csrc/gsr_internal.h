@@ -251,6 +251,12 @@ int launch_blend_pick(const GsrCamera &cam, const GsrOptions &opts, const Worksp
 // weights [.., k]; one of the two may be null, out_final_T may be (and then the walk stops once no list can change); single views only
 int launch_blend_topk(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, int k, int select,
                       int32_t *out_ids, float *out_weights, float *out_final_T, hipStream_t s);
+// Stage 3 for channels between two per-pixel depth limits (blend_slab.hip): launch_blend_channels restricted, per pixel, to the
+// gaussians with near <= z_cam < far; either plane may be null (no limit); means null: the pointer the preprocess left in the
+// control block; single views only
+int launch_blend_slab(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *means,
+                      const float *features, int channels, int64_t stride, const float *depth_near, const float *depth_far,
+                      float *out_map, float *out_T, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

@@ -383,6 +383,19 @@ def topk_composite(topk: TopK, features: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def composite_over(map: torch.Tensor, T: torch.Tensor, background: torch.Tensor) -> torch.Tensor:
+    """map + T[..., None] * background: what a blend leaves of whatever lies behind it.  `map` is [H, W, C] with its final
+    transmittance `T` [H, W] (render(..., return_T=True), render_features, render_slab); `background` is [C] (one colour) or
+    [H, W, C] (a frame: the mesh render behind the splats, the next depth layer).  Plain torch, one multiply-add per element in the
+    map's dtype; differentiable in all three; works on CPU and GPU tensors."""
+    if map.dim() != 3 or tuple(T.shape) != tuple(map.shape[:2]):
+        raise ValueError(f"map must be [H, W, C] and T [H, W], got {tuple(map.shape)} and {tuple(T.shape)}")
+    background = torch.as_tensor(background, dtype=map.dtype, device=map.device)
+    if tuple(background.shape) not in ((map.shape[2],), tuple(map.shape)):
+        raise ValueError(f"background must be [{map.shape[2]}] or {tuple(map.shape)}, got {tuple(background.shape)}")
+    return map + T.to(map.dtype).unsqueeze(-1) * background
+
+
 class _RenderFeatures(torch.autograd.Function):
     """render_features as a differentiable function of the features alone: the map is linear in them, so the backward is the
     transpose under the same camera and options (Rasterizer.feature_gradient); nothing flows to the geometry or the opacities."""
@@ -779,6 +792,88 @@ class Rasterizer:
             return img, maps[0][..., 0].contiguous(), maps[0][..., 1].contiguous()
 
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "frame")
+
+    # -- feature maps between two per-pixel depth limits ----------------------------------------------------------------------------
+    def _depth_limit(self, plane, name: str, shape) -> Optional[torch.Tensor]:
+        """A limit plane of render_slab as gsr_render_slab reads it (None stays None): float32 `shape` on the scene's device."""
+        if plane is None:
+            return None
+        if not isinstance(plane, torch.Tensor) or plane.dtype != torch.float32 or tuple(plane.shape) != tuple(shape):
+            got = f"{plane.dtype} {tuple(plane.shape)}" if isinstance(plane, torch.Tensor) else type(plane).__name__
+            raise ValueError(f"{name} must be a float32 tensor of shape {tuple(shape)} (the layout of the final T), got {got}")
+        if plane.device != self.scene.device:
+            raise ValueError(f"{name} must live on the scene's device ({self.scene.device}), got {plane.device}")
+        return plane.detach().contiguous()
+
+    def _enqueue_slab(self, cam: GsrCamera, opts: GsrOptions, rows: torch.Tensor, near, far, want_T: bool):
+        """One preprocess, one bin / sort and one gsr_blend_slab (gsr_render_slab) on the current stream, unchecked like enqueue().
+        Returns (map, T or None)."""
+        ws = self._workspace(cam.width, cam.height)
+        shape, tshape = self._out_shape(cam, opts)
+        dev, n_ch = self.scene.device, int(rows.shape[1])
+        new = torch.zeros if opts.output_layout == 2 else torch.empty  # strips may include rows below the frame's last pixel row
+        out = new(shape[:2] + (n_ch,), dtype=torch.float32, device=dev)
+        T = torch.ones(tshape, dtype=torch.float32, device=dev) if want_T else None
+        if out.numel() == 0:  # a shard that owns no tile row
+            self.unchecked.wrote(0)
+            return out, T
+        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
+            opts = GsrOptions.from_buffer_copy(opts)
+            opts.keep_flags = 1
+        sc = self.scene.c_struct()
+        check(lib.gsr_render_slab(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), rows.data_ptr(),
+                                  n_ch, int(rows.stride(0)), near.data_ptr() if near is not None else None,
+                                  far.data_ptr() if far is not None else None, out.data_ptr(), T.data_ptr() if want_T else None,
+                                  _stream_ptr(dev)))
+        self.unchecked.wrote(1)
+        return out, T
+
+    def render_slab(self, cam: GsrCamera, features: torch.Tensor, near: Optional[torch.Tensor] = None, far: Optional[torch.Tensor] = None,
+                    opts: Optional[GsrOptions] = None, return_T: bool = True, scene_order: bool = False):
+        """render_features between two per-pixel depth limits (gsr_render_slab): pixel p composites only the gaussians with
+        near[p] <= z_i < far[p], z_i = the gaussian's camera-space linear depth (the unit of render_depth, the bits of
+        preprocess_debug(cam)["cam_means"][:, 2]); T starts at 1 at the near limit — what lies in front of it is skipped, not
+        blended.  near / far: float32 [H, W] on the scene's device in the layout of the final T (layouts as render()), or None for
+        no limit on that side; a pixel with a NaN limit or far <= near draws nothing (map 0, T 1).  features, scene_order and the
+        result are render_features' — (map [H, W, C], T [H, W]), or the map alone with return_T=False; with both limits open the
+        map and T are render_features' bit for bit.  Up to 4 channels take one walk of the lists, up to 8 one, wider maps walks of
+        16.  One preprocess and one bin / sort per call; checked and re-rendered on overflow like render(); sets last_stats.
+        This path has NO BACKWARD: features that require a gradient are refused (detach them, or mask the features and use
+        render_features), and nothing is differentiable in the limits."""
+        if isinstance(features, torch.Tensor) and features.requires_grad and torch.is_grad_enabled():
+            raise ValueError("render_slab has no backward: features that require a gradient are refused (pass features.detach())")
+        opts = opts or make_options()
+        tshape = self._out_shape(cam, opts)[1]
+        near, far = self._depth_limit(near, "near", tshape), self._depth_limit(far, "far", tshape)
+        rows = self._feature_rows(features, scene_order)
+
+        def attempt(o):
+            out, T = self._enqueue_slab(cam, o, rows, near, far, return_T)
+            return (out, T) if return_T else out
+
+        return _render_checked([self], [None], opts, attempt, 8, "slab map")
+
+    def _view_colours(self, cam: GsrCamera) -> torch.Tensor:
+        """[n, 3] float32 in the scene's order: every gaussian's colour seen from this camera (gsr_sh_to_rgb: the values the colour
+        frame blends)."""
+        n, dev = self.scene.n, self.scene.device
+        rgb = torch.zeros((n, 3), dtype=torch.float32, device=dev)
+        if n:
+            sh = self.scene.t["sh"] if not self.scene.sh_half else self.scene.t["sh"].float()
+            check(lib.gsr_sh_to_rgb(n, self.scene.t["means"].data_ptr(), sh.data_ptr(), cam.cam_center, self.scene.sh_degree,
+                                    rgb.data_ptr(), _stream_ptr(dev)))
+        return rgb
+
+    def render_occluded(self, cam: GsrCamera, depth: torch.Tensor, background: Optional[torch.Tensor] = None,
+                        opts: Optional[GsrOptions] = None):
+        """(image [H, W, 3], T [H, W]): the colour frame IN FRONT OF a depth buffer — render_slab with the scene's colours for this
+        camera as features and far = depth, so that pixel p shows the gaussians with z_i < depth[p] (camera-space linear depth; +inf:
+        no occluder, the whole frame) and T[p] is how much of what lies at depth[p] shows through.  With `background` ([3] or
+        [H, W, 3]: the occluder's own render) the image is composite_over(image, T, background)."""
+        img, T = self.render_slab(cam, self._view_colours(cam), far=depth, opts=opts, return_T=True, scene_order=True)
+        if background is not None:
+            img = composite_over(img, T, background)
+        return img, T
 
     # -- per-pixel gaussian ids ---------------------------------------------------------------------------------------------------
     def _enqueue_pick(self, cam: GsrCamera, opts: GsrOptions, median_T: float, count: bool):
