@@ -31,7 +31,8 @@ extern "C" {
                             gsr_render_channels_backward — the transpose of gsr_blend_channels in the channels: the gradient of a map with respect to the per-gaussian rows; gsr_blend_pick /
                             gsr_render_pick — per-pixel ids: the gaussian of largest weight, the one at which T crosses a threshold, the contributor count; gsr_blend_topk /
                             gsr_render_topk + GSR_MAX_TOPK — per-pixel contributor lists: the k heaviest or the k nearest gaussians of a pixel with their weights; gsr_blend_slab /
-                            gsr_render_slab — gsr_blend_channels between two per-pixel depth limits: a depth test against a z-buffer, section planes, depth layers): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            gsr_render_slab — gsr_blend_channels between two per-pixel depth limits: a depth test against a z-buffer, section planes, depth layers; gsr_blend_gaussian_stats /
+                            gsr_render_gaussian_stats — per-gaussian statistics of a view: the sum and the maximum of a gaussian's weights and the number of pixels it reaches, optionally under a pixel mask): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -442,6 +443,39 @@ int gsr_blend_slab(const GsrScene *scene /* may be NULL */, int64_t n, const Gsr
 int gsr_render_slab(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride,
                     const float *depth_near, const float *depth_far, float *out_map, float *out_final_T, void *stream);
+
+/* Stage 3 turned round: per GAUSSIAN i, over the pixels p of this view that count, with the weights w_i(p) = alpha_i T_i the feature
+ * blends composite with — bit for bit, over their lists and with their stop rule (no reference counterpart):
+ *   weight_sum[i] += sum_p w_i(p)                  the summed weight: gsr_blend_channels_backward of a one-channel map of ones;
+ *   weight_max[i]  = max(weight_max[i], max_p w_i(p))   the largest weight the gaussian reaches in any pixel: the score of max-based pruning;
+ *   pixels[i]     += #{p : w_i(p) > 0}             how many pixels it reaches (gsr_blend_pick's out_count rule, transposed): pixels[i] > 0
+ *                                                  over a zeroed array is the EXACT visible set of the view.
+ * Each array has n entries in the order of the caller's scene arrays (the order gsr_preprocess was given them in); any of the three
+ * may be NULL, not all three, and an absent output costs nothing.  All three ACCUMULATE (the caller zeroes them, or keeps going over
+ * views: sum of sums, max of maxima, sum of counts); entries of gaussians that no counted pixel draws are not touched.
+ *   - weight_max and pixels are exact and reproducible to the bit: the maximum is taken over the floats' bit patterns as unsigned
+ *     integers (for non-negative floats that is the float maximum) and neither depends on the order the atomics arrive in.
+ *     weight_max must therefore hold NON-NEGATIVE FINITE floats on entry (zeros, or the result of an earlier call).
+ *   - weight_sum is a float atomic sum: its value depends on the order the adds arrive in, so two calls with the same input can
+ *     differ in the last bits.
+ * pixel_mask: one byte per pixel [device], laid out per opts->output_layout like out_final_T ([H,W], [W,H] or the strip
+ * [rows * 16, W]); non-zero = the pixel counts.  NULL: every drawn pixel counts.  Pixels the forward leaves 0 (the undrawn last
+ * column / row of reference_compat) never count.  The mask selects what is COUNTED, not what is blended: T evolves as in the
+ * unmasked view.  A quadrant of 64 pixels none of which counts is skipped, and a tile of four such quadrants stages nothing.
+ * Honoured and ignored options, the stop rule (a quadrant stops once T <= early_out_T for all its pixels; exact at 0) and what it
+ * leaves alone on the workspace are gsr_blend_channels_backward's: it reads the records' geometry and opacity only, no colour word,
+ * and leaves the launch-order hint alone.  gsr_read_stats afterwards describes this walk (wave_entries, fetched_entries;
+ * colour_evals = 0).
+ * GSR_ERR_BAD_ARG, before any HIP call or look at the workspace, for a null camera or options, all three outputs NULL,
+ * output_dtype = 1, accum_dtype = 1.  Single views. */
+int gsr_blend_gaussian_stats(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, const uint8_t *pixel_mask /* may be NULL */, float *weight_sum,
+                             float *weight_max, uint32_t *pixels, void *stream);
+
+/* gsr_preprocess (as with colour_stage = 0) + gsr_bin_sort + gsr_blend_gaussian_stats */
+int gsr_render_gaussian_stats(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                              size_t workspace_bytes, const uint8_t *pixel_mask /* may be NULL */, float *weight_sum,
+                              float *weight_max, uint32_t *pixels, void *stream);
 
 /* Several views of ONE resident scene (the reference renders one view per process, rasterize.py:315-329; BASELINE configs[3] is a
  * camera set).  cams[n_cams] [host] must share width/height; frame i goes to out_images + i * frame_stride (in elements of the

@@ -134,6 +134,7 @@ EXPORTS = [
     "gsr_blend_pick", "gsr_render_pick",
     "gsr_blend_topk", "gsr_render_topk",
     "gsr_blend_slab", "gsr_render_slab",
+    "gsr_blend_gaussian_stats", "gsr_render_gaussian_stats",
 ]
 
 
@@ -170,6 +171,8 @@ def _load() -> C.CDLL:
     L.gsr_render_topk.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, i32, i32, vp, vp, vp, vp]
     L.gsr_blend_slab.argtypes = [C.POINTER(GsrScene), i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp, vp, vp]
     L.gsr_render_slab.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp, vp, vp]
+    L.gsr_blend_gaussian_stats.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp, vp]
+    L.gsr_render_gaussian_stats.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp, vp]
     L.gsr_render_forward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
     L.gsr_render_batch.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, vp, sz, vp, i64, vp]
     L.gsr_render_batch_slots.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, C.POINTER(vp), sz,

@@ -595,6 +595,53 @@ int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, co
     return launch_blend_channels_backward(*cam, o, ws, plan, grad_map, channels, grad_features, grad_stride, s);
 }
 
+// What gsr_blend_gaussian_stats / gsr_render_gaussian_stats refuse before anything else (and before any HIP call)
+static int check_gaussian_stats(const GsrCamera *cam, const GsrOptions *opts, const float *weight_sum, const float *weight_max,
+                                const uint32_t *pixels)
+{
+    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    if (!weight_sum && !weight_max && !pixels) { set_error("null statistics outputs: all three"); return GSR_ERR_BAD_ARG; }
+    if (opts->output_dtype == 1) { set_error("gaussian statistics are float32 / uint32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("the weights are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+int gsr_blend_gaussian_stats(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, const uint8_t *pixel_mask, float *weight_sum, float *weight_max, uint32_t *pixels,
+                             void *stream)
+{
+    int rc = check_gaussian_stats(cam, opts, weight_sum, weight_max, pixels);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    return launch_blend_gstats(*cam, *opts, ws, plan_frame(ws, *opts), pixel_mask, weight_sum, weight_max, pixels,
+                               static_cast<hipStream_t>(stream));
+}
+
+int gsr_render_gaussian_stats(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                              size_t workspace_bytes, const uint8_t *pixel_mask, float *weight_sum, float *weight_max, uint32_t *pixels,
+                              void *stream)
+{
+    int rc = check_gaussian_stats(cam, opts, weight_sum, weight_max, pixels);
+    if (rc) return rc;
+    rc = check_scene(scene);
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    GsrOptions o = *opts;
+    o.colour_stage = 0;  // as in gsr_render_channels_backward: no SH row is read, the records keep their "unevaluated" marks
+    const FramePlan plan = plan_frame(ws, o);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
+    if (rc) return rc;
+    rc = bin_sort_impl(&o, ws, plan, s);
+    if (rc) return rc;
+    return launch_blend_gstats(*cam, o, ws, plan, pixel_mask, weight_sum, weight_max, pixels, s);
+}
+
 // What gsr_blend_pick / gsr_render_pick refuse before anything else (and before any HIP call)
 static int check_pick(const GsrCamera *cam, const GsrOptions *opts, float median_T, const int32_t *out_best_id, const float *out_best_w,
                       const int32_t *out_median_id, const int32_t *out_count)

@@ -257,6 +257,11 @@ int launch_blend_topk(const GsrCamera &cam, const GsrOptions &opts, const Worksp
 int launch_blend_slab(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *means,
                       const float *features, int channels, int64_t stride, const float *depth_near, const float *depth_far,
                       float *out_map, float *out_T, hipStream_t s);
+// Per-gaussian statistics of the view's weights over the counted pixels (blend_gstats.hip): weight_sum[i] += sum_p w_i(p),
+// weight_max[i] = max(old, max_p w_i(p)), pixels[i] += #{p : w_i(p) > 0}; any of the three may be null, not all; pixel_mask null: every
+// drawn pixel counts; single views only
+int launch_blend_gstats(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const uint8_t *pixel_mask,
+                        float *weight_sum, float *weight_max, uint32_t *pixels, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

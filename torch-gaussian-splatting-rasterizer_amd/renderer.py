@@ -362,6 +362,18 @@ class TopK(NamedTuple):
     final_T: Optional[torch.Tensor]
 
 
+class ViewStats(NamedTuple):
+    """Rasterizer.view_stats: per gaussian, over the counted pixels of a view (or of several), the sum of its blend weights
+    (float32), the largest weight it reaches in any pixel (float32) and the number of pixels it reaches with w > 0 (int32).  [n]
+    tensors; a field that was not asked for is None."""
+    weight_sum: Optional[torch.Tensor]
+    weight_max: Optional[torch.Tensor]
+    pixels: Optional[torch.Tensor]
+
+
+VIEW_STATS = ("sum", "max", "pixels")  # the names `want` takes, in ViewStats' field order
+
+
 TOPK_SELECT = {"heaviest": _lib.GSR_TOPK_HEAVIEST, "nearest": _lib.GSR_TOPK_NEAREST}
 
 
@@ -773,6 +785,109 @@ class Rasterizer:
             return out
         return self.feature_gradient(cam, ones, opts).squeeze(1)
 
+    # -- per-gaussian statistics of a view ---------------------------------------------------------------------------------------
+    def _stats_request(self, cam: GsrCamera, opts: GsrOptions, mask, out, want):
+        """view_stats' argument checks, before any workspace or buffer is made: (wanted flags, mask as gsr_render_gaussian_stats
+        reads it or None)."""
+        if isinstance(want, str) or not all(isinstance(w, str) for w in want):
+            raise ValueError(f"want must be a sequence of names from {VIEW_STATS}, got {want!r}")
+        bad = [w for w in want if w not in VIEW_STATS]
+        if bad or not len(want):
+            raise ValueError(f"want must name at least one of {VIEW_STATS} and nothing else, got {tuple(want)!r}")
+        flags = tuple(name in want for name in VIEW_STATS)
+        dev, n = self.scene.device, self.scene.n
+        tshape = tuple(self._out_shape(cam, opts)[1])
+        if mask is not None:
+            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != tshape:
+                got = f"{mask.dtype} {tuple(mask.shape)}" if isinstance(mask, torch.Tensor) else type(mask).__name__
+                raise ValueError(f"mask must be a bool or uint8 tensor of shape {tshape} (the layout of the final T), got {got}")
+            if mask.device != dev:
+                raise ValueError(f"mask must live on the scene's device ({dev}), got {mask.device}")
+            mask = mask.detach().contiguous()
+            mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask  # one byte per pixel, non-zero = counted
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 3:
+                raise ValueError("out must be a ViewStats (weight_sum, weight_max, pixels)")
+            for name, wanted, t, dtype in zip(VIEW_STATS, flags, out, (torch.float32, torch.float32, torch.int32)):
+                if not wanted:
+                    continue
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != (n,) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
+                    raise ValueError(f"out's {name!r} field must be a contiguous {dtype} tensor of shape [{n}] on the scene's device")
+        return flags, mask
+
+    def view_stats(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, mask: Optional[torch.Tensor] = None,
+                   out: Optional[ViewStats] = None, scene_order: bool = False, want=VIEW_STATS) -> ViewStats:
+        """Per gaussian, over the counted pixels of this view and with the weights w_i = alpha_i T_i render_features composites with
+        (gsr_render_gaussian_stats): weight_sum = sum_p w_i(p) (blend_weights' value), weight_max = max_p w_i(p) — the score of
+        max-based pruning — and pixels = #{p : w_i(p) > 0}; pixels > 0 is the exact visible set of the view.  `want` names the
+        fields to compute ("sum", "max", "pixels"); the others are None and cost nothing.  weight_max and pixels are exact and
+        reproducible to the bit, weight_sum is a float atomic sum (last bits may differ between two calls).
+        mask: [H, W] bool or uint8 on the scene's device in the layout render_features writes (layouts as render()); non-zero = the
+        pixel counts.  It selects what is counted, not what is blended (a lasso or click region: the statistics of what shows
+        there); quadrants and tiles with no counted pixel are skipped.
+        Returned in the order of the file the scene was loaded from (scene_order=True: of the scene's resident arrays).  With `out`
+        — a ViewStats of [n] tensors (float32, float32, int32) in the SCENE's order, only the wanted fields needed — the statistics
+        are ACCUMULATED (sum +=, max = max(old, .), pixels +=; weight_max must hold non-negative finite values) and out's tensors
+        are returned: stages 1-2 are checked and re-run first and only then does the blend add, so that an incomplete walk never
+        reaches `out`.  Checked and re-rendered on overflow like render(); sets last_stats."""
+        opts = opts or make_options()
+        flags, mask = self._stats_request(cam, opts, mask, out, want)
+        dev, n = self.scene.device, self.scene.n
+        dtypes = (torch.float32, torch.float32, torch.int32)
+        given = out is not None
+        bufs = [((out[k] if given else torch.zeros(n, dtype=dtypes[k], device=dev)) if flags[k] else None) for k in range(3)]
+        mptr = mask.data_ptr() if mask is not None else None
+
+        def result():
+            if given or scene_order:
+                return ViewStats(*bufs)
+            return ViewStats(*[None if b is None else file_order_gradient(b, self.scene.order_t) for b in bufs])
+
+        if n == 0 or 0 in self._out_shape(cam, opts)[1]:  # nothing to draw, or a shard that owns no tile row
+            return result()
+        ptrs = [b.data_ptr() if b is not None else None for b in bufs]
+        ws_args = lambda: (self._workspace(cam.width, cam.height).data_ptr(), self._ws.numel())
+
+        def chained(o):  # slice 0 holds unchecked frames: add to their record
+            if self.unchecked.slices and not o.keep_flags:
+                o = GsrOptions.from_buffer_copy(o)
+                o.keep_flags = 1
+            return o
+
+        if not given:
+            def attempt(o):  # a re-run after an overflow starts from zero again
+                wp, wn = ws_args()
+                o, sc = chained(o), self.scene.c_struct()
+                for b in bufs:
+                    if b is not None:
+                        b.zero_()
+                check(lib.gsr_render_gaussian_stats(C.byref(sc), C.byref(cam), C.byref(o), self.max_pairs, wp, wn, mptr, *ptrs, _stream_ptr(dev)))
+                self.unchecked.wrote(1)
+
+            _render_checked([self], [None], opts, attempt, 8, "view statistics")
+            return result()
+
+        # Accumulating: an incomplete walk must not reach `out`, so stages 1-2 are checked (and re-run) first, then the blend adds
+        def attempt_lists(o):
+            wp, wn = ws_args()
+            o, sc = GsrOptions.from_buffer_copy(chained(o)), self.scene.c_struct()
+            o.colour_stage = 0  # as gsr_render_gaussian_stats
+            check(lib.gsr_preprocess(C.byref(sc), C.byref(cam), C.byref(o), wp, wn, None, _stream_ptr(dev)))
+            check(lib.gsr_bin_sort(n, C.byref(cam), C.byref(o), self.max_pairs, wp, wn, _stream_ptr(dev)))
+            self.unchecked.wrote(1)
+            return o
+
+        o = _render_checked([self], [None], opts, attempt_lists, 8, "view statistics")
+        wp, wn = ws_args()
+        check(lib.gsr_blend_gaussian_stats(n, C.byref(cam), C.byref(o), self.max_pairs, wp, wn, mptr, *ptrs, _stream_ptr(dev)))
+        return result()
+
+    def visible_ids(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int64 ids, ascending, in the order of the file the scene was loaded from, of the gaussians that reach at least one counted
+        pixel with w > 0: the view's exact visible set (view_stats' pixels > 0).  The preprocess cull is a superset of it, and a
+        saturated tile hides most of that."""
+        return torch.nonzero(self.view_stats(cam, opts, mask, want=("pixels",)).pixels > 0)[:, 0]
+
     def render_depth(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, normalize: bool = False):
         """(depth [H, W], alpha [H, W]): depth = sum_i w_i z_i with z = the gaussians' camera-space depth, alpha = sum_i w_i (= 1 - final T
         up to rounding).  normalize=True divides depth by alpha where alpha > 0 (the expected depth of what was hit), 0 elsewhere."""
@@ -1074,6 +1189,28 @@ class Rasterizer:
                 back[self.scene.order_t] = v
                 out[k] = back
         return out
+
+
+def accumulate_view_stats(R: "Rasterizer", cams, opts: Optional[GsrOptions] = None, masks=None):
+    """Rasterizer.view_stats over a camera set into one set of buffers: (ViewStats, views) in the order of the file the scene was
+    loaded from — weight_sum summed, weight_max the maximum and pixels summed over the views, and `views` [n] int32 = in how many
+    of the views the gaussian reached a counted pixel.  masks: None, or one mask (or None) per camera."""
+    cams = list(cams)
+    masks = [None] * len(cams) if masks is None else list(masks)
+    if len(masks) != len(cams):
+        raise ValueError(f"masks must hold one entry per camera: {len(masks)} for {len(cams)} cameras")
+    n, dev = R.scene.n, R.scene.device
+    total = ViewStats(torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev),
+                      torch.zeros(n, dtype=torch.int32, device=dev))
+    views = torch.zeros(n, dtype=torch.int32, device=dev)
+    seen = torch.zeros(n, dtype=torch.int32, device=dev)  # this view's pixel counts
+    for cam, mask in zip(cams, masks):
+        seen.zero_()
+        R.view_stats(cam, opts, mask, out=ViewStats(total.weight_sum, total.weight_max, seen))
+        total.pixels.add_(seen)
+        views.add_((seen > 0).to(torch.int32))
+    o_t = R.scene.order_t
+    return ViewStats(*[file_order_gradient(b, o_t) for b in total]), file_order_gradient(views, o_t)
 
 
 class FramesInFlight:
