@@ -88,10 +88,15 @@ def main():
             fr = t.sum(axis=1)
             b = t[:, 2]
             s = stats[(name, build)]
-            print(f"{name:10s} {build:8s} preprocess {np.median(t[:, 0]):.4f}  bin_sort {np.median(t[:, 1]):.4f}  "
+            bs = t[:, 1]
+            print(f"{name:10s} {build:8s} preprocess {np.median(t[:, 0]):.4f}  bin_sort {np.median(bs):.4f} [{bs.min():.4f} .. {bs.max():.4f}]  "
                   f"blend {np.median(b):.4f} [{b.min():.4f} .. {b.max():.4f}] q {np.percentile(b, 25):.4f}-{np.percentile(b, 75):.4f}  "
                   f"frame {np.median(fr):.4f} [{fr.min():.4f} .. {fr.max():.4f}]   == {ref}: {bool(torch.equal(outs[(name, build)], outs[(name, ref)]))}  "
                   f"E {s['n_pairs']} fetched {s['fetched_entries']} evaluated {s['wave_entries']} colour_evals {s['colour_evals']}", flush=True)
+        for build, _ in libs[1:]:  # the same for the stage the depth sort and the binning live in
+            d = np.array(times[(name, build)])[:, 1] - np.array(times[(name, ref)])[:, 1]
+            print(f"{name:10s} bin_sort {build} - {ref}: median {np.median(d):+.4f} ms  [{d.min():+.4f} .. {d.max():+.4f}]  "
+                  f"{int((d < 0).sum())} of {len(d)} rounds faster", flush=True)
         if len(libs) == 2:  # paired differences round by round: the spread of the DIFFERENCE is what a gain is held against
             d = np.array(times[(name, libs[1][0])])[:, 2] - np.array(times[(name, libs[0][0])])[:, 2]
             print(f"{name:10s} blend {libs[1][0]} - {libs[0][0]}: median {np.median(d):+.4f} ms  [{d.min():+.4f} .. {d.max():+.4f}]  "

@@ -51,8 +51,13 @@ size_t carve_workspace(void *base, int64_t n, int width, int height, int64_t max
     ws->rec = static_cast<GaussRec *>(take(sizeof(GaussRec) * nn));
     ws->rect = static_cast<ushort4 *>(take(sizeof(ushort4) * nn));
     for (int b = 0; b < 2; ++b) ws->key[b] = static_cast<uint32_t *>(take(4 * nn));
-    for (int b = 0; b < 2; ++b) ws->val[b] = static_cast<uint32_t *>(take(4 * nn));
-    for (int b = 0; b < 2; ++b) ws->rect8[b] = static_cast<uint32_t *>(take(4 * nn));
+    // val[b] and rect8[b] side by side: together they are pay[b], the depth sort's 8-byte {id, rect8} payload (sort.hip).  Pass 0 reads
+    // val[0] / rect8[0] (what the preprocess wrote) and writes pay[1]; pay[0] is first written by pass 1
+    for (int b = 0; b < 2; ++b) {
+        ws->val[b] = static_cast<uint32_t *>(take(4 * nn));
+        ws->rect8[b] = static_cast<uint32_t *>(take(4 * nn));
+        ws->pay[b] = reinterpret_cast<uint2 *>(ws->val[b]);
+    }
     ws->blk_dead = static_cast<unsigned char *>(take((nn + GSR_BOUNDS_BLOCK - 1) / GSR_BOUNDS_BLOCK));  // (with the per-gaussian arrays: stage 1 carves with max_pairs = 0)
     ws->blk_sum = static_cast<uint32_t *>(
         take(4 * ((std::max(nn, (size_t)ws->tiles_x * ws->tiles_y) + EMIT_THREADS - 1) / EMIT_THREADS + 1)));

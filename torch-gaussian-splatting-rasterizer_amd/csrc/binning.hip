@@ -8,8 +8,9 @@
 // the last) and is dropped by the first pass of the tile sort.
 //
 //   count   one thread per depth-sorted gaussian: tiles of its rect that belong to this shard
-//           (tile rows begin, begin+step, ...) -> per-workgroup sums.  The rect arrives packed in the depth
-//           sort's second payload (coalesced); frames wider than 4096 px gather it by gaussian id instead.
+//           (tile rows begin, begin+step, ...) -> per-workgroup sums.  The rect arrives packed beside the id in the depth
+//           sort's 8-byte payload element {id, rect8} (coalesced: a lane's four gaussians are two 16-B loads; emit reads one
+//           8-B element per gaussian); frames wider than 4096 px sort the ids alone and gather the rect by id instead.
 //   scan    one workgroup: exclusive scan of the workgroup sums; D, overflow flag, slots = min(D, max_pairs)
 //   emit    load-balanced expansion: a workgroup owns 256 consecutive gaussians and the contiguous slot range
 //           their pairs occupy; every thread takes slots j, j+256, ..., finds the owning gaussian by binary
@@ -79,10 +80,23 @@ __device__ __forceinline__ void row_col(uint32_t k, uint32_t w, uint32_t *row, u
     *col = k - r * w;
 }
 
+// The r-th gaussian of the draw order: PACKED: one 8-byte {id, rect8} element of the depth sort's payload; else its id, and the
+// rect gathered by it.  *packed: the rect as it travelled (PACKED only)
 template <bool PACKED, bool COARSE>
-__device__ __forceinline__ ushort4 rect_of(uint32_t r, const uint32_t *sorted_ids, const uint32_t *sorted_rect8, const ushort4 *rect)
+__device__ __forceinline__ ushort4 sorted_of(uint32_t r, const uint32_t *sorted_ids, const uint2 *sorted_pay, const ushort4 *rect, uint32_t *g,
+                                             uint32_t *packed)
 {
-    const ushort4 rc = PACKED ? unpack_rect8(sorted_rect8[r]) : rect[sorted_ids[r]];
+    ushort4 rc;
+    if (PACKED) {
+        const uint2 e = sorted_pay[r];
+        *g = e.x;
+        *packed = e.y;
+        rc = unpack_rect8(e.y);
+    } else {
+        *g = sorted_ids[r];
+        *packed = 0u;
+        rc = rect[*g];
+    }
     return COARSE ? coarse_rect(rc) : rc;
 }
 
@@ -94,13 +108,13 @@ constexpr int COUNT_BLOCKS_PER_WG = EMIT_THREADS / 64;  // emit blocks per count
 static_assert(EMIT_THREADS == 256, "a lane of the count kernel takes EMIT_THREADS / 64 = 4 gaussians: one uint4 of packed rects");
 template <bool PACKED, bool COARSE>
 __global__ __launch_bounds__(EMIT_THREADS) void pair_count_kernel(const uint32_t *__restrict__ id_a, const uint32_t *__restrict__ id_b,
-                                                                  const uint32_t *__restrict__ r8_a, const uint32_t *__restrict__ r8_b,
+                                                                  const uint2 *__restrict__ pay_a, const uint2 *__restrict__ pay_b,
                                                                   const FrameCtrl *ctrl, const ushort4 *__restrict__ rect, RowShard sh,
                                                                   uint32_t *__restrict__ blk_sum, uint2 *__restrict__ ranges,
                                                                   int n_tiles, uint32_t draw_limit, uint2 *__restrict__ cranges, int n_ctiles,
                                                                   FrameCtrl *ctrl_w, uint32_t ent_off, int nblk_n, int grid_wgs, size_t vstride)
 {
-    id_a = view_slice(id_a, vstride); id_b = view_slice(id_b, vstride); r8_a = view_slice(r8_a, vstride); r8_b = view_slice(r8_b, vstride);
+    id_a = view_slice(id_a, vstride); id_b = view_slice(id_b, vstride); pay_a = view_slice(pay_a, vstride); pay_b = view_slice(pay_b, vstride);
     ctrl = view_slice(ctrl, vstride); rect = view_slice(rect, vstride); blk_sum = view_slice(blk_sum, vstride); ranges = view_slice(ranges, vstride);
     cranges = view_slice(cranges, vstride); ctrl_w = view_slice(ctrl_w, vstride);
     const uint32_t n = ctrl->n_visible;
@@ -113,7 +127,8 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_count_kernel(const uint32_t
     }
     for (uint32_t c = t; c < (uint32_t)n_tiles; c += stride) ranges[c] = make_uint2(0u, 0u);  // tile ranges are rebuilt every frame
     const bool odd = ctrl->sort_buf != 0;
-    const uint32_t *sorted_ids = odd ? id_b : id_a, *sorted_rect8 = odd ? r8_b : r8_a;
+    const uint32_t *sorted_ids = odd ? id_b : id_a;  // PACKED: not read
+    const uint2 *sorted_pay = odd ? pay_b : pay_a;   // else: not read
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint32_t lim = n < draw_limit ? n : draw_limit;
     // this wave's emit blocks: the grid is capped (launch_binning) and strides over the blocks the frame HAS — n_visible is only known
@@ -125,16 +140,17 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_count_kernel(const uint32_t
     uint32_t cnt = 0;
     if (r0 < lim) {
         int first;
-        if (PACKED && r0 + 4 <= lim) {  // the packed rects ride through the depth sort: four of them in one 16-B load (r0 is a multiple of 4)
-            const uint4 p4 = *reinterpret_cast<const uint4 *>(sorted_rect8 + r0);
-            const uint32_t p[4] = {p4.x, p4.y, p4.z, p4.w};
+        if (PACKED && r0 + 4 <= lim) {  // the packed rects ride through the depth sort beside the ids: four {id, rect8} in two 16-B loads (r0 is a multiple of 4)
+            const uint4 pa = *reinterpret_cast<const uint4 *>(sorted_pay + r0), pb = *reinterpret_cast<const uint4 *>(sorted_pay + r0 + 2);
+            const uint32_t p[4] = {pa.y, pa.w, pb.y, pb.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const ushort4 rc = unpack_rect8(p[j]);
                 cnt += tiles_of(COARSE ? coarse_rect(rc) : rc, sh, &first);
             }
         } else {
-            for (uint32_t r = r0; r < r0 + 4 && r < lim; ++r) cnt += tiles_of(rect_of<PACKED, COARSE>(r, sorted_ids, sorted_rect8, rect), sh, &first);
+            uint32_t g, packed;
+            for (uint32_t r = r0; r < r0 + 4 && r < lim; ++r) cnt += tiles_of(sorted_of<PACKED, COARSE>(r, sorted_ids, sorted_pay, rect, &g, &packed), sh, &first);
         }
     }
 #pragma unroll
@@ -221,7 +237,7 @@ __global__ __launch_bounds__(1024) void pair_scan_kernel(uint32_t *__restrict__ 
 // chain each — counters, ids and rects, scan, stores — eight to a CU: six rounds of latency, not search or store throughput.)
 template <bool PACKED, bool COARSE, typename KeyT>  // KeyT: uint16_t when the keys fit (FramePlan.key16), else uint32_t
 __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t *__restrict__ id_a, const uint32_t *__restrict__ id_b,
-                                                                 const uint32_t *__restrict__ r8_a, const uint32_t *__restrict__ r8_b,
+                                                                 const uint2 *__restrict__ pay_a, const uint2 *__restrict__ pay_b,
                                                                  const FrameCtrl *ctrl, const ushort4 *__restrict__ rect, RowShard sh,
                                                                  int bits_x, int tiles_y, const GaussRec *__restrict__ rec,
                                                                  const uint32_t *blk_off, uint32_t max_pairs,
@@ -229,7 +245,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
                                                                  uint32_t draw_limit, RowShard tsh, uint32_t *blk_entries /* = blk_off: no __restrict__ on either */,
                                                                  int grid_wgs, size_t vstride)
 {
-    id_a = view_slice(id_a, vstride); id_b = view_slice(id_b, vstride); r8_a = view_slice(r8_a, vstride); r8_b = view_slice(r8_b, vstride);
+    id_a = view_slice(id_a, vstride); id_b = view_slice(id_b, vstride); pay_a = view_slice(pay_a, vstride); pay_b = view_slice(pay_b, vstride);
     ctrl = view_slice(ctrl, vstride); rect = view_slice(rect, vstride); rec = view_slice(rec, vstride); blk_off = view_slice(blk_off, vstride);
     pkey = view_slice(pkey, vstride); pval = view_slice(pval, vstride); blk_entries = view_slice(blk_entries, vstride);
     __shared__ uint32_t scratch[8];
@@ -242,7 +258,8 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
     __shared__ uint32_t s_fine[COARSE ? EMIT_THREADS : 1];  // coarse: the gaussian's packed TILE rect
     const uint32_t n = ctrl->n_visible;
     const bool odd = ctrl->sort_buf != 0;
-    const uint32_t *sorted_ids = odd ? id_b : id_a, *sorted_rect8 = odd ? r8_b : r8_a;
+    const uint32_t *sorted_ids = odd ? id_b : id_a;  // PACKED: not read
+    const uint2 *sorted_pay = odd ? pay_b : pay_a;   // else: not read
     const int tid = threadIdx.x;
     // the grid is capped (launch_binning) and strides over the emit blocks the frame has: sized by the bound n >= V it launched more
     // workgroups that found nothing to do than ones that did (n_visible is only known here)
@@ -256,10 +273,10 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
     int first = 0;
     ushort4 rc = make_ushort4(0, 0, 0, 0);
     if (r < n && r < draw_limit) {
-        g = sorted_ids[r];
-        rc = rect_of<PACKED, COARSE>(r, sorted_ids, sorted_rect8, rect);
+        uint32_t packed;
+        rc = sorted_of<PACKED, COARSE>(r, sorted_ids, sorted_pay, rect, &g, &packed);
         cnt = tiles_of(rc, sh, &first);
-        if (COARSE) s_fine[tid] = sorted_rect8[r];
+        if (COARSE) s_fine[tid] = packed;
     }
     const bool test = cnt > CULL_MIN_TILES;
     // (the record gather of a large rect flies while the workgroup scans its counts: it lands in LDS after the scan's barriers)
@@ -386,10 +403,10 @@ int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan 
     // over the blocks the frame has — V is known on the device only
     const int nblk_count = std::min((nblk_n + COUNT_BLOCKS_PER_WG - 1) / COUNT_BLOCKS_PER_WG, EMIT_GRID_CAP / COUNT_BLOCKS_PER_WG);
     const int nblk_emit = std::min(nblk_n, EMIT_GRID_CAP);
-#define GSR_COUNT(P, C) hipLaunchKernelGGL((pair_count_kernel<P, C>), dim3(nblk_count, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.rect8[0], ws.rect8[1], \
+#define GSR_COUNT(P, C) hipLaunchKernelGGL((pair_count_kernel<P, C>), dim3(nblk_count, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.pay[0], ws.pay[1], \
                                            ws.ctrl, ws.rect, C ? plan.csh : plan.rs, ws.blk_sum, ws.ranges, n_tiles, limit, ws.cranges, n_ctiles, ws.ctrl, \
                                            C ? (uint32_t)(reinterpret_cast<const char *>(ws.blk_sum) - reinterpret_cast<const char *>(ws.ctrl)) : 0u, nblk_n, nblk_count, vs)
-#define GSR_EMIT_T(P, C, T) hipLaunchKernelGGL((pair_emit_kernel<P, C, T>), dim3(nblk_emit, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.rect8[0], ws.rect8[1], \
+#define GSR_EMIT_T(P, C, T) hipLaunchKernelGGL((pair_emit_kernel<P, C, T>), dim3(nblk_emit, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.pay[0], ws.pay[1], \
                                           ws.ctrl, ws.rect, C ? plan.csh : plan.rs, plan.bits_x, plan.grid_y, ws.rec, ws.blk_sum, cap, reinterpret_cast<T *>(ws.pkey[0]), ws.pval[0], limit, \
                                           plan.rs, ws.blk_sum, nblk_emit, vs)
 #define GSR_EMIT(P, C) do { if (plan.key16) GSR_EMIT_T(P, C, uint16_t); else GSR_EMIT_T(P, C, uint32_t); } while (0)

@@ -20,7 +20,7 @@ struct FrameCtrl {
     uint32_t n_pairs;       // E  (pairs that survive footprint culling; written by tile-sort pass 0)
     uint32_t overflow;
     uint32_t max_list_len;
-    uint32_t sort_passes;   // depth-sort plan of this frame (sort.hip): passes it needs (1..4) — the sorted ids end up in val[sort_buf]
+    uint32_t sort_passes;   // depth-sort plan of this frame (sort.hip): passes it needs (1..4) — the sorted ids end up in pay[sort_buf] / val[sort_buf]
     unsigned long long wave_entries;  // (quadrant, entry) pairs evaluated by the blend   } totals of blend_stats[], filled in
     unsigned long long fetched_entries;  // list entries staged by the blend              } by gsr_read_stats
     unsigned long long colour_evals;     // deferred colours evaluated by the blend       }
@@ -41,7 +41,7 @@ struct FrameCtrl {
     float col_cc[3];         // GsrCamera.cam_center
     int32_t col_degree;      // GsrScene.sh_degree
     int32_t col_sh16;        // GsrScene.sh_dtype
-    uint32_t sort_buf;       // which of val[] / rect8[] the last depth-sort pass that RAN wrote: min(sort_passes, passes enqueued) & 1.
+    uint32_t sort_buf;       // which of pay[] (val[] when the rect does not ride along) the last depth-sort pass that RAN wrote: min(sort_passes, passes enqueued) & 1.
                              // A frame short of passes (flagged, to be re-rendered) still hands binning a buffer this frame's sort filled
     uint32_t depth_key_max;  // maximum of the frame's valid depth keys (pass-0 histogram).  Cleared with the frame AND by the pass-0
                              // rowscan once consumed (gsr_bin_sort may be repeated on one gsr_preprocess).
@@ -77,10 +77,14 @@ struct Workspace {
     FrameCtrl *ctrl;
     GaussRec *rec;        // [n]
     ushort4 *rect;        // [n]   tile rect {tx0, ty0, tx1, ty1} (exclusive upper), after footprint refinement
-    uint32_t *rect8[2];   // [n]   the same rect packed x0 | y0<<8 | (x1-1)<<16 | (y1-1)<<24; rides through the depth
-                          //       sort as a second payload when the tile grid fits 8 bits (frames up to 4096 px)
+    uint32_t *rect8[2];   // [n]   the same rect packed x0 | y0<<8 | (x1-1)<<16 | (y1-1)<<24, written per gaussian into rect8[0] when the
+                          //       tile grid fits 8 bits (frames up to 4096 px); depth-sort pass 0 moves it into the payload (pay[])
+                          //       ([1]: a shard rank's run scratch)
     uint32_t *key[2];     // [n]   depth keys (ping-pong)
-    uint32_t *val[2];     // [n]   gaussian ids (ping-pong)
+    uint32_t *val[2];     // [n]   gaussian ids (ping-pong) — the depth sort's payload when the rect does not ride along; val[0] also: a
+                          //       shard rank's compacted ids entering pass 0
+    uint2 *pay[2];        // [n]   {gaussian id, rect8}: the depth sort's payload from pass 0's output on when the rect rides along
+                          //       (ping-pong).  No bytes of its own: pay[b] lies over val[b] and rect8[b], which are side by side
     uint32_t *pair_off;   // [n]   exclusive pair offsets in depth order
     uint32_t *blk_sum;    // [ceil(n/EMIT_THREADS)+1]
     uint32_t *hist;       // [512 * hist_blocks] digit-major: hist[digit][block]
@@ -179,7 +183,7 @@ enum class BlendKernel {
 constexpr int COARSE_ID_BITS = 28;  // coarse pairs: value = gaussian id | (mask of the cell's tiles the gaussian reaches) << 28
 struct FramePlan {
     // stage 1 (preprocess.hip)
-    bool packed_rect;      // the tile rect is written packed into rect8[0] and rides through the depth sort as a second payload; else ushort4 in rect[], gathered by id
+    bool packed_rect;      // the tile rect is written packed into rect8[0] and rides through the depth sort beside the id (one uint2, pay[]); else ushort4 in rect[], gathered by id
     bool compact_input;    // the three-phase shard kernel hands the depth sort compact (key, id, rect) records; else the whole-frame kernel (its K-view form when ws.views > 1) one key per gaussian
     RowShard rs;           // the rank's tile rows
     RowShard cull_rs;      // the rows block-level culling tests a block against
@@ -218,7 +222,7 @@ int launch_rasterize_gaussian(int64_t g, const int64_t *bboxes, float *screen, c
                               const float *rgb, float *opacity_buffer, const float *opacity, int W, int H, hipStream_t s);
 
 // Depth order (sort.hip): stable LSD radix sort of the depth keys; leaves V in FrameCtrl.n_visible and the sorted ids (+ packed
-// rects) in val[p] / rect8[p], p = FrameCtrl.sort_buf (decided on the device from the frame's key range).
+// rects) in pay[p] — val[p] without the rects —, p = FrameCtrl.sort_buf (decided on the device from the frame's key range).
 int launch_depth_sort(const Workspace &ws, const FramePlan &plan, hipStream_t s);
 // gsr_scene_order (sort.hip): Morton-curve permutation of the gaussians, built with the radix passes of the pair sort
 size_t scene_order_bytes(int64_t n);

@@ -66,26 +66,27 @@ __device__ __forceinline__ bool radix_tile_of(uint32_t n, uint32_t tile_size, ui
 // owns digit t in the per-digit steps.  256 threads / 4096 records for the pair sort (8-bit digits and fewer), 512 threads /
 // 8192 records for the depth sort's 9-bit digits: with twice the digit values a 4096-record tile's runs halve (8 records =
 // 32 B per array, measured +35 % per pass); doubling the tile keeps the runs at 16 records and the table reads per record equal.
-// LDS budget: the arrays of a record (key, value, second value) pass through ONE tile-sized buffer one after the other instead of
-// each having its own (three barriers more per tile): 52 KB instead of 116 KB for the depth sort's 512-thread tiles, so that LDS
-// leaves room for three workgroups on a CU instead of one.  Two are resident: the scatter kernel's 117-128 VGPRs allow four waves
+// LDS budget: the arrays of a record (key, payload) pass through ONE tile-sized buffer one after the other instead of
+// each having its own (barriers more per tile; the depth sort's 8-byte {id, rect8} payload in two halves): 52 KB instead of 116 KB
+// for the depth sort's 512-thread tiles, so that LDS leaves room for three workgroups on a CU instead of one.  Two are resident: the scatter kernel's 117-128 VGPRs allow four waves
 // per SIMD, which is two 512-thread workgroups (sort.hip; the compiler's occupancy figure, tools/kernel_resources.sh) — the passes
 // are bound by the latency of a tile's dependent phases (load, rank, layout, reorder, store), not by any pipe, and with one
 // workgroup per CU a 410-tile pass ran as two rounds of 256 + 154.
-template <int THREADS, int ITEMS, bool HAS_V2>
+template <int THREADS, int ITEMS, bool PAY8>
 struct RadixTileSmem {
     static constexpr int TILE = THREADS * ITEMS, WAVES = THREADS / 64, DIGITS = THREADS;
     static_assert(THREADS == 256 || THREADS == 512, "digit d is owned by thread d");
     static constexpr int BUF_WORDS = TILE > WAVES * DIGITS * 2 ? TILE : WAVES * DIGITS * 2;  // the peer masks (8 B per wave and digit) live here too
     uint32_t wave_cnt[WAVES][DIGITS];  // per-wave digit counts, then per-wave exclusive bases
     uint32_t tile_start[DIGITS];       // start of digit d inside the reordered tile
-    uint32_t buf[BUF_WORDS];           // peer masks while ranking, then one array of the tile at a time in digit order
+    alignas(8) uint32_t buf[BUF_WORDS]; // peer masks while ranking, then one array of the tile at a time in digit order (PAY8: as many
+                                        // 8-byte payload elements as fit, radix_pay_stage)
     uint32_t scratch[2 * WAVES];
     uint32_t n_valid;
 };
 
-template <int THREADS, int ITEMS, bool HAS_V2>
-__device__ __forceinline__ void radix_clear(RadixTileSmem<THREADS, ITEMS, HAS_V2> &sm)
+template <int THREADS, int ITEMS, bool PAY8>
+__device__ __forceinline__ void radix_clear(RadixTileSmem<THREADS, ITEMS, PAY8> &sm)
 {
     constexpr int WAVES = THREADS / 64;
     uint32_t *wc = &sm.wave_cnt[0][0];
@@ -104,8 +105,8 @@ __device__ __forceinline__ void radix_clear(RadixTileSmem<THREADS, ITEMS, HAS_V2
 // eight ballots per round with a per-lane 64-bit select after each, measured 8 us of the scatter kernel's 17 us per
 // workgroup: ~50 VALU instructions per round.)  The lowest lane of each group then advances the wave's running count of
 // that digit and hands the old value to its peers.  dig(r) returns the digit of this thread's r-th record or RADIX_NO_DIGIT.
-template <int THREADS, int ITEMS, bool HAS_V2, typename DigitOf>
-__device__ __forceinline__ void radix_rank(RadixTileSmem<THREADS, ITEMS, HAS_V2> &sm, DigitOf dig, uint32_t (&rank)[ITEMS])
+template <int THREADS, int ITEMS, bool PAY8, typename DigitOf>
+__device__ __forceinline__ void radix_rank(RadixTileSmem<THREADS, ITEMS, PAY8> &sm, DigitOf dig, uint32_t (&rank)[ITEMS])
 {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     unsigned long long *pm = reinterpret_cast<unsigned long long *>(sm.buf) + wave * THREADS;  // the tile buffer is not live until the reorder
@@ -147,8 +148,8 @@ __device__ __forceinline__ void radix_rank(RadixTileSmem<THREADS, ITEMS, HAS_V2>
 // After radix_rank + a barrier.  Thread t owns digit t: turns the per-wave counts into per-wave exclusive bases, fills
 // tile_start[], leaves the tile's record count in sm.n_valid.  Contains two barriers; the caller adds one before using
 // the tables.
-template <int THREADS, int ITEMS, bool HAS_V2>
-__device__ __forceinline__ void radix_tile_layout(RadixTileSmem<THREADS, ITEMS, HAS_V2> &sm)
+template <int THREADS, int ITEMS, bool PAY8>
+__device__ __forceinline__ void radix_tile_layout(RadixTileSmem<THREADS, ITEMS, PAY8> &sm)
 {
     constexpr int WAVES = THREADS / 64;
     const int d = threadIdx.x;
@@ -165,8 +166,8 @@ __device__ __forceinline__ void radix_tile_layout(RadixTileSmem<THREADS, ITEMS, 
 
 // After radix_tile_layout + a barrier: rank[r] (rank among the wave's earlier records of the same digit) -> the record's position
 // in the reordered tile (stable), RADIX_NO_DIGIT stays.  In place.
-template <int THREADS, int ITEMS, bool HAS_V2, typename DigitOf>
-__device__ __forceinline__ void radix_positions(const RadixTileSmem<THREADS, ITEMS, HAS_V2> &sm, DigitOf dig, uint32_t (&rank)[ITEMS])
+template <int THREADS, int ITEMS, bool PAY8, typename DigitOf>
+__device__ __forceinline__ void radix_positions(const RadixTileSmem<THREADS, ITEMS, PAY8> &sm, DigitOf dig, uint32_t (&rank)[ITEMS])
 {
     const int wave = threadIdx.x >> 6;
 #pragma unroll
@@ -179,12 +180,34 @@ __device__ __forceinline__ void radix_positions(const RadixTileSmem<THREADS, ITE
 }
 
 // One array of the tile -> the tile buffer, in digit order.  The caller brackets it with barriers.
-template <int THREADS, int ITEMS, bool HAS_V2>
-__device__ __forceinline__ void radix_stage(RadixTileSmem<THREADS, ITEMS, HAS_V2> &sm, const uint32_t (&pos)[ITEMS], const uint32_t (&v)[ITEMS])
+template <int THREADS, int ITEMS, bool PAY8>
+__device__ __forceinline__ void radix_stage(RadixTileSmem<THREADS, ITEMS, PAY8> &sm, const uint32_t (&pos)[ITEMS], const uint32_t (&v)[ITEMS])
 {
 #pragma unroll
     for (int r = 0; r < ITEMS; ++r)
         if (pos[r] != RADIX_NO_DIGIT) sm.buf[pos[r]] = v[r];
+}
+
+// PAY8: the 8-byte {id, rect8} elements of chunk c of the reordered tile (positions [c * CHUNK, (c + 1) * CHUNK), CHUNK = what the
+// tile buffer holds of them: half an 8192-record tile, a whole 4096-record one) -> the tile buffer, in digit order.  The caller
+// brackets it with barriers.  (Measured against ONE round over wave_cnt, tile_start and a 46-KB buf together — 66 KB of LDS per
+// workgroup, still two to a CU: bin + sort -7.4 instead of -11.7 us per view, profiles/pay8_build_ab.txt.)
+template <int THREADS, int ITEMS>
+struct RadixPayChunk {
+    using Smem = RadixTileSmem<THREADS, ITEMS, true>;
+    static constexpr int CHUNK = Smem::BUF_WORDS / 2 < Smem::TILE ? Smem::BUF_WORDS / 2 : Smem::TILE;
+    static constexpr int PER = CHUNK / THREADS;  // elements of a chunk a thread writes out
+    static_assert(Smem::TILE % CHUNK == 0 && CHUNK % THREADS == 0, "the tile goes through the buffer in whole chunks");
+};
+template <int THREADS, int ITEMS>
+__device__ __forceinline__ const uint2 *radix_pay_stage(RadixTileSmem<THREADS, ITEMS, true> &sm, int c, const uint32_t (&pos)[ITEMS], const uint2 (&v)[ITEMS])
+{
+    constexpr uint32_t CHUNK = RadixPayChunk<THREADS, ITEMS>::CHUNK;
+    uint2 *buf2 = reinterpret_cast<uint2 *>(sm.buf);
+#pragma unroll
+    for (int r = 0; r < ITEMS; ++r)  // (RADIX_NO_DIGIT lies in no chunk)
+        if (pos[r] / CHUNK == (uint32_t)c) buf2[pos[r] % CHUNK] = v[r];
+    return buf2;
 }
 
 }  // namespace gsr

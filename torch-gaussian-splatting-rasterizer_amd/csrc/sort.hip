@@ -1,8 +1,10 @@
-// sort.hip — stable LSD radix sort of (u32 key, u32 value[, u32 value2]) records, up to 9 bits per pass.
+// sort.hip — stable LSD radix sort of (u32 key, payload) records, up to 9 bits per pass; the payload is a u32 value or the 8-byte
+// {value, second value} element of the depth sort.
 //
 // Used twice per frame (rasterize.py:424-425 is one torch.sort; tile lists have no reference counterpart):
 //   1. depth order:  keys = IEEE bits of z_cam of every gaussian (KEY_INVALID for culled ones, dropped
-//      by pass 0), values = gaussian id (+ its packed tile rect).  Stable from index order => depth ties
+//      by pass 0), payload = {gaussian id, its packed tile rect} as one uint2 from pass 0's output on (frames up to 256 x 256
+//      tiles; wider frames: the id alone, rects are gathered by it).  Stable from index order => depth ties
 //      resolve by gaussian index.
 //   2. tile lists:   keys = (tile row, tile column) of every (gaussian,tile) pair emitted IN DEPTH ORDER, values = gaussian
 //      id.  A stable sort by tile therefore leaves every tile's list depth-ordered.
@@ -12,7 +14,8 @@
 //   hist     one workgroup per tile of 256*ITEMS keys: digit histogram -> hist[digit][tile]
 //   rowscan  one workgroup per digit: exclusive scan of its row in place, row total -> digit_tot[digit]
 //   scatter  one workgroup per tile: per-wave ranking through LDS peer masks -> tile reordered by digit in LDS -> digit
-//            runs written out contiguously (coalesced), position = digit base + scanned hist + rank in run   (radix.h)
+//            runs written out contiguously (coalesced), position = digit base + scanned hist + rank in run   (radix.h);
+//            the keys go through the tile buffer first, then the payload
 // The element count lives in device memory (n_dev): grids are sized by the host-side bound and surplus workgroups fall
 // through.  Which tile a hist / scatter workgroup takes is a matter of speed only (radix_tile_of, radix.h: consecutive tiles per XCD).  16 keys per thread (2048-key tiles measured slower, the fixed per-workgroup costs dominate); the depth sort's
 // 9-bit passes run 512 threads on 8192 keys, the pair sort's <= 8-bit passes 256 threads on 4096 (radix.h says why).
@@ -24,7 +27,8 @@
 // evenly over as few passes of <= 9 bits as possible.  A scene whose depths span 0.2 .. 83 (B <= 27) sorts in 9 + 9 + 9;
 // the launch sequence is fixed at four passes (the host cannot know B without a sync) and the kernels of an unused pass
 // return at once.  Consumers find the sorted buffer from the plan (FrameCtrl.sort_buf).
-// Roofline: HBM.  Per pass per element: 4 B (hist) + 8..12 B read + 8..12 B written.
+// Roofline: HBM.  Per pass per element: 4 B (hist) + 8..12 B read + 8..12 B written (depth sort: key 4 B + payload 8 B, as one 4-B and
+// one 8-B stream; pass 0 reads key and rect8 per gaussian, 8 N).
 #include <algorithm>
 #include "gsr_internal.h"
 #include "radix.h"
@@ -158,19 +162,27 @@ __global__ __launch_bounds__(256) void radix_rowscan_kernel(uint32_t *__restrict
 // Register budget: two 512-thread workgroups per CU (128 VGPRs; one before: 119 KB of LDS) — depth-sort scatters 54 / 32 us ->
 // 49 / 28 us on the bench frame.  The 256-thread pair sort stays at four per CU: pressed into 96 VGPRs for a fifth it spills
 // and takes 53 instead of 37 us.
-template <int THREADS, bool DROP, int ITEMS, bool HAS_V2, bool INDEX_VALS, typename KeyT = uint32_t>
+//
+// Payload.  PAY8 = false: one uint32_t per record (vals_in -> vals_out; INDEX_VALS: the record's index, nothing to load).
+// PAY8 = true (the depth sort of frames up to 256 x 256 tiles): the record's {gaussian id, packed tile rect} travel as ONE uint2 —
+// the pass's output is pay_out whatever its input; the FIRST pass (DROP: the depth sort's pass 0 is its only dropping pass) puts the
+// element together from the id (vals_in, or the index) and the N-indexed rect8 the preprocess wrote (vals2_in), every later pass
+// reads pay_in.  Staged through the tile buffer as 8-byte elements (ds_write_b64 / ds_read_b64, global_store_dwordx2; radix.h,
+// radix_pay_stage): digit runs of 16 records are 128 B, a whole line, instead of two half lines.  The 32-KB buffer holds half an
+// 8192-record tile of them, so such a tile's payload goes in two halves by position in the reordered tile (a 4096-record tile's in one).
+template <int THREADS, bool DROP, int ITEMS, bool PAY8, bool INDEX_VALS, typename KeyT = uint32_t>
 __global__ __launch_bounds__(THREADS, 4) void radix_scatter_kernel(
     const KeyT *__restrict__ keys_in, const uint32_t *__restrict__ vals_in, const uint32_t *__restrict__ vals2_in,
-    KeyT *__restrict__ keys_out, uint32_t *__restrict__ vals_out, uint32_t *__restrict__ vals2_out, const uint32_t *n_dev,
-    uint32_t n_bound, PassSpec ps, const FrameCtrl *ctrl, const uint32_t *__restrict__ hist, int hist_blocks, uint32_t *n_out,
-    size_t vstride)
+    const uint2 *__restrict__ pay_in, KeyT *__restrict__ keys_out, uint32_t *__restrict__ vals_out, uint2 *__restrict__ pay_out,
+    const uint32_t *n_dev, uint32_t n_bound, PassSpec ps, const FrameCtrl *ctrl, const uint32_t *__restrict__ hist, int hist_blocks,
+    uint32_t *n_out, size_t vstride)
 {
-    using Smem = RadixTileSmem<THREADS, ITEMS, HAS_V2>;
+    using Smem = RadixTileSmem<THREADS, ITEMS, PAY8>;
     constexpr int TILE = Smem::TILE;
     __shared__ Smem sm;
     __shared__ uint32_t digit_base[THREADS];  // global position of this tile's run of digit d
     keys_in = view_slice(keys_in, vstride); vals_in = view_slice(vals_in, vstride); vals2_in = view_slice(vals2_in, vstride);
-    keys_out = view_slice(keys_out, vstride); vals_out = view_slice(vals_out, vstride); vals2_out = view_slice(vals2_out, vstride);
+    pay_in = view_slice(pay_in, vstride); keys_out = view_slice(keys_out, vstride); vals_out = view_slice(vals_out, vstride); pay_out = view_slice(pay_out, vstride);
     n_dev = view_slice(n_dev, vstride); ctrl = view_slice(ctrl, vstride); hist = view_slice(hist, vstride); n_out = view_slice(n_out, vstride);
 
     int shift;
@@ -222,12 +234,33 @@ __global__ __launch_bounds__(THREADS, 4) void radix_scatter_kernel(
     __syncthreads();
 
     radix_positions(sm, dig, rank);  // rank[] is now the position inside the reordered tile
+    // the payload's loads fly while the keys go out
     uint32_t val[ITEMS];
-    if (INDEX_VALS) {  // the payload is the element's index: nothing to load
+    uint2 pay[PAY8 ? ITEMS : 1];
+    if constexpr (PAY8 && !DROP) {
+        if (full) {
 #pragma unroll
-        for (int r = 0; r < ITEMS; ++r) val[r] = base + wave * (64 * ITEMS) + r * 64 + lane;
+            for (int r = 0; r < ITEMS; ++r) pay[r] = pay_in[base + wave * (64 * ITEMS) + r * 64 + lane];
+        } else {
+#pragma unroll
+            for (int r = 0; r < ITEMS; ++r) {
+                const uint32_t idx = base + wave * (64 * ITEMS) + r * 64 + lane;
+                pay[r] = idx < n ? pay_in[idx] : make_uint2(0u, 0u);
+            }
+        }
     } else {
-        load(vals_in, val, 0u);
+        if (INDEX_VALS) {  // the payload is the element's index: nothing to load
+#pragma unroll
+            for (int r = 0; r < ITEMS; ++r) val[r] = base + wave * (64 * ITEMS) + r * 64 + lane;
+        } else {
+            load(vals_in, val, 0u);
+        }
+        if constexpr (PAY8) {
+            uint32_t v2[ITEMS];
+            load(vals2_in, v2, 0u);
+#pragma unroll
+            for (int r = 0; r < ITEMS; ++r) pay[r] = make_uint2(val[r], v2[r]);
+        }
     }
     // keys through the tile buffer; every output slot's global position is fixed on the way and kept for the payloads
     radix_stage(sm, rank, key);
@@ -247,29 +280,33 @@ __global__ __launch_bounds__(THREADS, 4) void radix_scatter_kernel(
         }
     }
     __syncthreads();
-    radix_stage(sm, rank, val);
-    if constexpr (HAS_V2) load(vals2_in, val, 0u);  // val is staged: its registers take the second payload
-    __syncthreads();
+    if constexpr (PAY8) {
+        using Chunk = RadixPayChunk<THREADS, ITEMS>;
 #pragma unroll
-    for (int k = 0; k < ITEMS; ++k) {
-        const uint32_t i = (uint32_t)tid + (uint32_t)k * THREADS;
-        if (i < nvalid) vals_out[gpos[k]] = sm.buf[i];
-    }
-    if constexpr (HAS_V2) {
-        __syncthreads();
+        for (int c = 0; c < TILE / Chunk::CHUNK; ++c) {
+            if (c > 0) __syncthreads();
+            const uint2 *buf2 = radix_pay_stage(sm, c, rank, pay);
+            __syncthreads();
+#pragma unroll
+            for (int k = c * Chunk::PER; k < (c + 1) * Chunk::PER; ++k) {
+                const uint32_t i = (uint32_t)tid + (uint32_t)k * THREADS;
+                if (i < nvalid) pay_out[gpos[k]] = buf2[i - (uint32_t)(c * Chunk::CHUNK)];
+            }
+        }
+    } else {
         radix_stage(sm, rank, val);
         __syncthreads();
 #pragma unroll
         for (int k = 0; k < ITEMS; ++k) {
             const uint32_t i = (uint32_t)tid + (uint32_t)k * THREADS;
-            if (i < nvalid) vals2_out[gpos[k]] = sm.buf[i];
+            if (i < nvalid) vals_out[gpos[k]] = sm.buf[i];
         }
     }
 }
 
 // One pass = hist + rowscan + scatter.  `first` = pass 0 of a sort (may drop, may synthesise the index payload).
-template <int THREADS, int ITEMS, bool HAS_V2, typename KeyT = uint32_t>
-static void launch_pass(const KeyT *kin, const uint32_t *vin, const uint32_t *v2in, KeyT *kout, uint32_t *vout, uint32_t *v2out,
+template <int THREADS, int ITEMS, bool PAY8, typename KeyT = uint32_t>
+static void launch_pass(const KeyT *kin, const uint32_t *vin, const uint32_t *v2in, const uint2 *pin, KeyT *kout, uint32_t *vout, uint2 *pout,
                         const uint32_t *cnt_dev, int64_t n_bound, const PassSpec &ps, bool drop, bool ident, uint32_t *n_out,
                         const Workspace &ws, hipStream_t s)
 {
@@ -281,8 +318,8 @@ static void launch_pass(const KeyT *kin, const uint32_t *vin, const uint32_t *v2
     const unsigned nv = (unsigned)ws.views;  // gridDim.y: one slice of the workspace per view (gsr_internal.h, view_slice)
     const size_t vs = ws.view_stride;
 #define GSR_SCATTER(DROP, IDENT)                                                                                                   \
-    hipLaunchKernelGGL((radix_scatter_kernel<THREADS, DROP, ITEMS, HAS_V2, IDENT, KeyT>), dim3(nblk, nv), dim3(THREADS), 0, s, kin, vin, v2in,   \
-                       kout, vout, v2out, cnt_dev, nb, ps, ws.ctrl, ws.hist, ws.hist_blocks, n_out, vs)
+    hipLaunchKernelGGL((radix_scatter_kernel<THREADS, DROP, ITEMS, PAY8, IDENT, KeyT>), dim3(nblk, nv), dim3(THREADS), 0, s, kin, vin, v2in,   \
+                       pin, kout, vout, pout, cnt_dev, nb, ps, ws.ctrl, ws.hist, ws.hist_blocks, n_out, vs)
     if (drop) hipLaunchKernelGGL((radix_hist_kernel<THREADS, true, ITEMS, KeyT>), dim3(nblk, nv), dim3(THREADS), 0, s, kin, cnt_dev, nb, ps, ws.ctrl, ws.hist, ws.hist_blocks, vs);
     else hipLaunchKernelGGL((radix_hist_kernel<THREADS, false, ITEMS, KeyT>), dim3(nblk, nv), dim3(THREADS), 0, s, kin, cnt_dev, nb, ps, ws.ctrl, ws.hist, ws.hist_blocks, vs);
     hipLaunchKernelGGL(radix_rowscan_kernel<TILE>, dim3(THREADS, nv), dim3(256), 0, s, ws.hist, ws.hist_blocks, cnt_dev, nb, ps, ws.ctrl, vs);
@@ -293,7 +330,8 @@ static void launch_pass(const KeyT *kin, const uint32_t *vin, const uint32_t *v2
 
 // Depth order of the gaussians (rasterize.py:424-425).  plan.depth_passes radix passes are enqueued: four unless the caller bounds
 // them (GsrOptions.depth_sort_passes), 3 run on ordinary scenes (header); a frame that needs more than were enqueued is flagged.
-// Afterwards FrameCtrl.n_visible = V and the sorted ids / packed rects are in val[p] / rect8[p], p = FrameCtrl.sort_buf.
+// Afterwards FrameCtrl.n_visible = V and the sorted {id, packed rect} elements are in pay[p] (the ids alone in val[p] when the rect does
+// not ride along), p = FrameCtrl.sort_buf.
 template <int ITEMS>
 static int depth_sort_passes(const Workspace &ws, const FramePlan &plan, hipStream_t s)
 {
@@ -309,11 +347,11 @@ static int depth_sort_passes(const Workspace &ws, const FramePlan &plan, hipStre
         const PassSpec ps = {0, 0u, DEPTH_KEY_BASE, KEY_INVALID, p, enq};
         const int in = p & 1, out = in ^ 1;
         const bool first = p == 0;
-        if (plan.packed_rect)
-            launch_pass<DEPTH_SORT_THREADS, ITEMS, true>(ws.key[in], ws.val[in], ws.rect8[in], ws.key[out], ws.val[out], ws.rect8[out], cnt_dev, ws.n, ps,
+        if (plan.packed_rect)  // pass 0 (in = 0) reads val[0] / rect8[0], which pay[0] lies over: its output is pay[1]
+            launch_pass<DEPTH_SORT_THREADS, ITEMS, true>(ws.key[in], ws.val[0], ws.rect8[0], ws.pay[in], ws.key[out], nullptr, ws.pay[out], cnt_dev, ws.n, ps,
                                                      first, first && !compact_input, first ? &ws.ctrl->n_visible : nullptr, ws, s);
         else
-            launch_pass<DEPTH_SORT_THREADS, ITEMS, false>(ws.key[in], ws.val[in], nullptr, ws.key[out], ws.val[out], nullptr, cnt_dev, ws.n, ps,
+            launch_pass<DEPTH_SORT_THREADS, ITEMS, false>(ws.key[in], ws.val[in], nullptr, nullptr, ws.key[out], ws.val[out], nullptr, cnt_dev, ws.n, ps,
                                                       first, first && !compact_input, first ? &ws.ctrl->n_visible : nullptr, ws, s);
         cnt_dev = &ws.ctrl->n_visible;  // later passes only see the survivors
     }
@@ -344,11 +382,11 @@ int launch_pair_sort(const Workspace &ws, const FramePlan &plan, const uint32_t 
         const PassSpec ps = {shift, (1u << std::min(bits_pp, key_bits - shift)) - 1u, 0u, plan.drop_from, -1, 0};
         const bool first = p == 0;
         if (plan.key16)  // the keys lie in the first half of each pkey buffer, two bytes each (binning.hip writes them so)
-            launch_pass<PAIR_SORT_THREADS, PAIR_SORT_ITEMS, false, uint16_t>(reinterpret_cast<const uint16_t *>(ws.pkey[cur]), ws.pval[cur], nullptr,
+            launch_pass<PAIR_SORT_THREADS, PAIR_SORT_ITEMS, false, uint16_t>(reinterpret_cast<const uint16_t *>(ws.pkey[cur]), ws.pval[cur], nullptr, nullptr,
                                                                             reinterpret_cast<uint16_t *>(ws.pkey[cur ^ 1]), ws.pval[cur ^ 1], nullptr, cnt_dev,
                                                                             ws.max_pairs, ps, first, false, first ? n_out : nullptr, ws, s);
         else
-            launch_pass<PAIR_SORT_THREADS, PAIR_SORT_ITEMS, false>(ws.pkey[cur], ws.pval[cur], nullptr, ws.pkey[cur ^ 1], ws.pval[cur ^ 1], nullptr, cnt_dev,
+            launch_pass<PAIR_SORT_THREADS, PAIR_SORT_ITEMS, false>(ws.pkey[cur], ws.pval[cur], nullptr, nullptr, ws.pkey[cur ^ 1], ws.pval[cur ^ 1], nullptr, cnt_dev,
                                                  ws.max_pairs, ps, first, false, first ? n_out : nullptr, ws, s);
         if (first && n_out) cnt_dev = n_out;
         cur ^= 1;
@@ -427,7 +465,7 @@ int launch_scene_order(int64_t n, const float *means, uint32_t *perm_out, void *
         int cur = 0;
         for (int sh = 0; sh < bits; sh += 8) {
             const PassSpec ps = {sh, (1u << std::min(8, bits - sh)) - 1u, 0u, KEY_INVALID, -1, 0};
-            launch_pass<PAIR_SORT_THREADS, PAIR_SORT_ITEMS, false>(key[cur], val[cur], nullptr, key[cur ^ 1], val[cur ^ 1], nullptr, nullptr, n, ps,
+            launch_pass<PAIR_SORT_THREADS, PAIR_SORT_ITEMS, false>(key[cur], val[cur], nullptr, nullptr, key[cur ^ 1], val[cur ^ 1], nullptr, nullptr, n, ps,
                                                                   false, sh == 0, nullptr, ws, s);
             cur ^= 1;
         }
