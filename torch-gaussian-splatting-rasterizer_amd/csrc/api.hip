@@ -418,36 +418,63 @@ static int check_features(const GsrCamera *cam, const GsrOptions *opts, const fl
     return GSR_OK;
 }
 
+// What every gsr_blend_X / gsr_render_X pair does behind its own argument checks: check_scene (when a scene is given), the frame's
+// checks, the plan, and launch(cam, opts, ws, plan, s) on the lists — those already in the workspace (scene == nullptr: n
+// gaussians), or the ones made here from the scene: stages 1 and 2 with colour_stage = 0 (nobody here needs a colour: the
+// preprocess reads no SH row, the records keep their "unevaluated" marks).
+extern "C++" {  // (templates cannot have C linkage)
+template <class Launch>
+static int run_on_lists(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs,
+                        void *workspace, size_t workspace_bytes, void *stream, Launch launch)
+{
+    int rc = scene ? check_scene(scene) : GSR_OK;
+    if (rc) return rc;
+    Workspace ws;
+    rc = check_frame(scene ? scene->n : n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    GsrOptions o = *opts;
+    if (scene) o.colour_stage = 0;
+    const FramePlan plan = plan_frame(ws, o);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (scene) {
+        rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
+        if (rc) return rc;
+        rc = bin_sort_impl(&o, ws, plan, s);
+        if (rc) return rc;
+    }
+    return launch(*cam, o, ws, plan, s);
+}
+
+// gsr_render_X: the scene is not optional ("null scene" is check_scene's to say)
+template <class Launch>
+static int render_on_lists(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                           size_t workspace_bytes, void *stream, Launch launch)
+{
+    if (!scene) return check_scene(scene);
+    return run_on_lists(scene, 0, cam, opts, max_pairs, workspace, workspace_bytes, stream, launch);
+}
+}  // extern "C++"
+
 int gsr_blend_features(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
                        const float *features, float *out_map, float *out_final_T, void *stream)
 {
-    int rc = check_features(cam, opts, features, out_map);
+    const int rc = check_features(cam, opts, features, out_map);
     if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    return launch_blend_features(*cam, *opts, ws, plan_frame(ws, *opts), features, out_map, out_final_T, static_cast<hipStream_t>(stream));
+    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_features(c, o, ws, plan, features, out_map, out_final_T, s);
+        });
 }
 
 int gsr_render_features(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                         size_t workspace_bytes, const float *features, float *out_map, float *out_final_T, void *stream)
 {
-    int rc = check_features(cam, opts, features, out_map);
+    const int rc = check_features(cam, opts, features, out_map);
     if (rc) return rc;
-    rc = check_scene(scene);
-    if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    GsrOptions o = *opts;
-    o.colour_stage = 0;  // nobody here needs a colour: the preprocess reads no SH row, the records keep their "unevaluated" marks
-    const FramePlan plan = plan_frame(ws, o);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
-    if (rc) return rc;
-    rc = bin_sort_impl(&o, ws, plan, s);
-    if (rc) return rc;
-    return launch_blend_features(*cam, o, ws, plan, features, out_map, out_final_T, s);
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_features(c, o, ws, plan, features, out_map, out_final_T, s);
+        });
 }
 
 // What gsr_blend_channels / gsr_render_channels refuse before anything else (and before any HIP call)
@@ -472,39 +499,28 @@ static int check_channels(const GsrCamera *cam, const GsrOptions *opts, const fl
 int gsr_blend_channels(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
                        const float *features, int32_t channels, int64_t feature_stride, float *out_map, float *out_final_T, void *stream)
 {
-    int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
+    const int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
     if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    return launch_blend_channels(*cam, *opts, ws, plan_frame(ws, *opts), features, channels, feature_stride, out_map, out_final_T,
-                                 static_cast<hipStream_t>(stream));
+    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_channels(c, o, ws, plan, features, channels, feature_stride, out_map, out_final_T, s);
+        });
 }
 
 int gsr_render_channels(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                         size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, float *out_map,
                         float *out_final_T, void *stream)
 {
-    int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
+    const int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
     if (rc) return rc;
-    rc = check_scene(scene);
-    if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    GsrOptions o = *opts;
-    o.colour_stage = 0;  // as in gsr_render_features: no SH row is read, the records keep their "unevaluated" marks
-    const FramePlan plan = plan_frame(ws, o);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
-    if (rc) return rc;
-    rc = bin_sort_impl(&o, ws, plan, s);
-    if (rc) return rc;
-    return launch_blend_channels(*cam, o, ws, plan, features, channels, feature_stride, out_map, out_final_T, s);
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_channels(c, o, ws, plan, features, channels, feature_stride, out_map, out_final_T, s);
+        });
 }
 
-// What gsr_blend_slab / gsr_render_slab refuse before anything else (and before any HIP call): gsr_blend_channels' cases; the depth
-// planes may be null
+// gsr_blend_slab / gsr_render_slab refuse gsr_blend_channels' cases; the depth planes may be null.  gsr_blend_slab may name the scene
+// whose means it reads; it preprocesses nothing
 int gsr_blend_slab(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                    size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, const float *depth_near,
                    const float *depth_far, float *out_map, float *out_final_T, void *stream)
@@ -516,34 +532,24 @@ int gsr_blend_slab(const GsrScene *scene, int64_t n, const GsrCamera *cam, const
         if (rc) return rc;
         if (scene->n != n) { set_error("scene->n = %lld but n = %lld", (long long)scene->n, (long long)n); return GSR_ERR_BAD_ARG; }
     }
-    Workspace ws;
-    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    return launch_blend_slab(*cam, *opts, ws, plan_frame(ws, *opts), scene ? scene->means : nullptr, features, channels, feature_stride,
-                             depth_near, depth_far, out_map, out_final_T, static_cast<hipStream_t>(stream));
+    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_slab(c, o, ws, plan, scene ? scene->means : nullptr, features, channels, feature_stride, depth_near,
+                                     depth_far, out_map, out_final_T, s);
+        });
 }
 
 int gsr_render_slab(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, const float *depth_near,
                     const float *depth_far, float *out_map, float *out_final_T, void *stream)
 {
-    int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
+    const int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
     if (rc) return rc;
-    rc = check_scene(scene);
-    if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    GsrOptions o = *opts;
-    o.colour_stage = 0;  // as in gsr_render_features: no SH row is read, the records keep their "unevaluated" marks
-    const FramePlan plan = plan_frame(ws, o);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
-    if (rc) return rc;
-    rc = bin_sort_impl(&o, ws, plan, s);
-    if (rc) return rc;
-    return launch_blend_slab(*cam, o, ws, plan, scene->means, features, channels, feature_stride, depth_near, depth_far, out_map,
-                             out_final_T, s);
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_slab(c, o, ws, plan, scene->means, features, channels, feature_stride, depth_near, depth_far, out_map,
+                                     out_final_T, s);
+        });
 }
 
 // What gsr_blend_channels_backward / gsr_render_channels_backward refuse before anything else (and before any HIP call)
@@ -569,35 +575,24 @@ int gsr_blend_channels_backward(int64_t n, const GsrCamera *cam, const GsrOption
                                 size_t workspace_bytes, const float *grad_map, int32_t channels, float *grad_features, int64_t grad_stride,
                                 void *stream)
 {
-    int rc = check_channels_backward(cam, opts, grad_map, channels, grad_features, grad_stride);
+    const int rc = check_channels_backward(cam, opts, grad_map, channels, grad_features, grad_stride);
     if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    return launch_blend_channels_backward(*cam, *opts, ws, plan_frame(ws, *opts), grad_map, channels, grad_features, grad_stride,
-                                          static_cast<hipStream_t>(stream));
+    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_channels_backward(c, o, ws, plan, grad_map, channels, grad_features, grad_stride, s);
+        });
 }
 
 int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                                  size_t workspace_bytes, const float *grad_map, int32_t channels, float *grad_features,
                                  int64_t grad_stride, void *stream)
 {
-    int rc = check_channels_backward(cam, opts, grad_map, channels, grad_features, grad_stride);
+    const int rc = check_channels_backward(cam, opts, grad_map, channels, grad_features, grad_stride);
     if (rc) return rc;
-    rc = check_scene(scene);
-    if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    GsrOptions o = *opts;
-    o.colour_stage = 0;  // as in gsr_render_channels: the lists and records of the forward it transposes
-    const FramePlan plan = plan_frame(ws, o);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
-    if (rc) return rc;
-    rc = bin_sort_impl(&o, ws, plan, s);
-    if (rc) return rc;
-    return launch_blend_channels_backward(*cam, o, ws, plan, grad_map, channels, grad_features, grad_stride, s);
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_channels_backward(c, o, ws, plan, grad_map, channels, grad_features, grad_stride, s);
+        });
 }
 
 // What gsr_blend_gaussian_stats / gsr_render_gaussian_stats refuse before anything else (and before any HIP call)
@@ -616,35 +611,24 @@ int gsr_blend_gaussian_stats(int64_t n, const GsrCamera *cam, const GsrOptions *
                              size_t workspace_bytes, const uint8_t *pixel_mask, float *weight_sum, float *weight_max, uint32_t *pixels,
                              void *stream)
 {
-    int rc = check_gaussian_stats(cam, opts, weight_sum, weight_max, pixels);
+    const int rc = check_gaussian_stats(cam, opts, weight_sum, weight_max, pixels);
     if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    return launch_blend_gstats(*cam, *opts, ws, plan_frame(ws, *opts), pixel_mask, weight_sum, weight_max, pixels,
-                               static_cast<hipStream_t>(stream));
+    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_gstats(c, o, ws, plan, pixel_mask, weight_sum, weight_max, pixels, s);
+        });
 }
 
 int gsr_render_gaussian_stats(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                               size_t workspace_bytes, const uint8_t *pixel_mask, float *weight_sum, float *weight_max, uint32_t *pixels,
                               void *stream)
 {
-    int rc = check_gaussian_stats(cam, opts, weight_sum, weight_max, pixels);
+    const int rc = check_gaussian_stats(cam, opts, weight_sum, weight_max, pixels);
     if (rc) return rc;
-    rc = check_scene(scene);
-    if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    GsrOptions o = *opts;
-    o.colour_stage = 0;  // as in gsr_render_channels_backward: no SH row is read, the records keep their "unevaluated" marks
-    const FramePlan plan = plan_frame(ws, o);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
-    if (rc) return rc;
-    rc = bin_sort_impl(&o, ws, plan, s);
-    if (rc) return rc;
-    return launch_blend_gstats(*cam, o, ws, plan, pixel_mask, weight_sum, weight_max, pixels, s);
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_gstats(c, o, ws, plan, pixel_mask, weight_sum, weight_max, pixels, s);
+        });
 }
 
 // What gsr_blend_pick / gsr_render_pick refuse before anything else (and before any HIP call)
@@ -665,35 +649,24 @@ static int check_pick(const GsrCamera *cam, const GsrOptions *opts, float median
 int gsr_blend_pick(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
                    float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id, int32_t *out_count, void *stream)
 {
-    int rc = check_pick(cam, opts, median_T, out_best_id, out_best_w, out_median_id, out_count);
+    const int rc = check_pick(cam, opts, median_T, out_best_id, out_best_w, out_median_id, out_count);
     if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    return launch_blend_pick(*cam, *opts, ws, plan_frame(ws, *opts), median_T, out_best_id, out_best_w, out_median_id, out_count,
-                             static_cast<hipStream_t>(stream));
+    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_pick(c, o, ws, plan, median_T, out_best_id, out_best_w, out_median_id, out_count, s);
+        });
 }
 
 int gsr_render_pick(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id,
                     int32_t *out_count, void *stream)
 {
-    int rc = check_pick(cam, opts, median_T, out_best_id, out_best_w, out_median_id, out_count);
+    const int rc = check_pick(cam, opts, median_T, out_best_id, out_best_w, out_median_id, out_count);
     if (rc) return rc;
-    rc = check_scene(scene);
-    if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    GsrOptions o = *opts;
-    o.colour_stage = 0;  // as in gsr_render_features: no SH row is read, the records keep their "unevaluated" marks
-    const FramePlan plan = plan_frame(ws, o);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
-    if (rc) return rc;
-    rc = bin_sort_impl(&o, ws, plan, s);
-    if (rc) return rc;
-    return launch_blend_pick(*cam, o, ws, plan, median_T, out_best_id, out_best_w, out_median_id, out_count, s);
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_pick(c, o, ws, plan, median_T, out_best_id, out_best_w, out_median_id, out_count, s);
+        });
 }
 
 // What gsr_blend_topk / gsr_render_topk refuse before anything else (and before any HIP call)
@@ -714,35 +687,24 @@ static int check_topk(const GsrCamera *cam, const GsrOptions *opts, int32_t k, i
 int gsr_blend_topk(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
                    int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T, void *stream)
 {
-    int rc = check_topk(cam, opts, k, select, out_ids, out_weights);
+    const int rc = check_topk(cam, opts, k, select, out_ids, out_weights);
     if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    return launch_blend_topk(*cam, *opts, ws, plan_frame(ws, *opts), k, select, out_ids, out_weights, out_final_T,
-                             static_cast<hipStream_t>(stream));
+    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_topk(c, o, ws, plan, k, select, out_ids, out_weights, out_final_T, s);
+        });
 }
 
 int gsr_render_topk(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T,
                     void *stream)
 {
-    int rc = check_topk(cam, opts, k, select, out_ids, out_weights);
+    const int rc = check_topk(cam, opts, k, select, out_ids, out_weights);
     if (rc) return rc;
-    rc = check_scene(scene);
-    if (rc) return rc;
-    Workspace ws;
-    rc = check_frame(scene->n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
-    if (rc) return rc;
-    GsrOptions o = *opts;
-    o.colour_stage = 0;  // as in gsr_render_features: no SH row is read, the records keep their "unevaluated" marks
-    const FramePlan plan = plan_frame(ws, o);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = launch_preprocess(*scene, cam, o, ws, plan, nullptr, reset_words_of(&o, false), s);
-    if (rc) return rc;
-    rc = bin_sort_impl(&o, ws, plan, s);
-    if (rc) return rc;
-    return launch_blend_topk(*cam, o, ws, plan, k, select, out_ids, out_weights, out_final_T, s);
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_topk(c, o, ws, plan, k, select, out_ids, out_weights, out_final_T, s);
+        });
 }
 
 // How many views go through one launch sequence: as many slices as the workspace holds, at most MAX_VIEWS, GsrOptions.batch_views

@@ -3,9 +3,8 @@
 //
 // out[p][c] = sum_i w_i(p) f_i[c] is linear in f, so its gradient needs the weights and nothing else: they are produced front to back,
 // by the forward's walk of the forward's lists, with the forward's stop rule.  No per-pixel state is kept from the forward, nothing
-// flows through alpha or T, and no map is written.  The workgroup is blend_channels_kernel's (blend_common.h): 256 threads per 16x16
-// tile, wave = 8x8 quadrant, lane = pixel, the same lists, footprint ballots, launch order and stat words; the weight of a
-// (pixel, survivor) is blend_channels_one's first 14 issues in its order, so the weights are the forward's bit for bit.
+// flows through alpha or T, and no map is written.  The workgroup, the survivor walk (one per trip) and the weight are
+// blend_weight_walk.h's, the forward's: the weights are the forward's bit for bit.  (The batch head is spelled out: see the loop.)
 //
 // What differs:
 //   per lane      CH registers with the pixel's upstream gradient, loaded once (zero outside the frame and in Q1's undrawn last
@@ -27,9 +26,7 @@
 //   ring [1024] + wc [8] + done: tile_list_next's
 // = 10240 + 1024 * CH + 4132 B: 22.0 KB at CH = 8 (7 workgroups per CU), 30.0 KB at CH = 16 (5).
 // Float atomic sums depend on the order the adds arrive in: two runs of the same input may differ in the last bits.
-#include "gsr_internal.h"
-#include "blend_args.h"
-#include "blend_common.h"
+#include "blend_weight_walk.h"
 
 namespace gsr {
 
@@ -44,15 +41,6 @@ struct ChannelGradArgs {
 };
 
 constexpr uint32_t ENTRY_TOUCHED = 1u << 31;  // ids are below 2^28 (LIST_ID_MASK)
-
-// x + (x moved across lanes by the DPP control CTRL); lanes without a source lane add 0 (bound_ctrl): one v_add_f32_dpp.
-// (No contraction: fused with the product that made x, the add would need the moved value in a register of its own.)
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x)
-{
-#pragma clang fp contract(off)
-    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
 
 // The sums of four values over the wave's 64 lanes, left in lane 63 (the other lanes hold partial sums nobody reads): row_shr
 // 1 / 2 / 4 / 8 leave each row's sum in its lane 15, row_bcast:15 adds it into the next row — lane 31 = rows 0 + 1, lane 63 = rows
@@ -73,18 +61,10 @@ __device__ __forceinline__ void wave_sum4(float (&v)[4])
     for (int c = 0; c < 4; ++c) v[c] = dpp_add<0x143>(v[c]);
 }
 
-// One (pixel, survivor): blend_channels_one's weight, then the wave's sums of w * g_c into row k of sG.
+// One survivor's weights w: the wave's sums of w * g_c into row k of sG.
 template <int CH>
-__device__ __forceinline__ void blend_channels_backward_one(const float2 gm, const float4 c, const float L, float fpx, float fpy, float &T,
-                                                            const float (&g)[CH], int nch, int lane, float *row, uint32_t *touched)
+__device__ __forceinline__ void blend_channels_backward_add(float w, const float (&g)[CH], int nch, int lane, float *row, uint32_t *touched)
 {
-    const float dx = gm.x - fpx, dy = gm.y - fpy;
-    const float p = fmaf(dx, fmaf(c.y, dy, c.x * dx), fmaf(c.z * dy, dy, L));  // log2 domain, opacity folded in
-    float alpha = fminf(__builtin_amdgcn_exp2f(p), GSR_MAX_ALPHA);
-    const bool valid = (alpha > GSR_MIN_ALPHA) & (p <= L);
-    alpha = valid ? alpha : 0.0f;
-    const float w = alpha * T;
-    T = fmaf(-T, alpha, T);
     if (__ballot(w != 0.0f) == 0) return;  // uniform: nothing to add for any pixel of the quadrant
 #pragma unroll
     for (int q = 0; q < CH / 4; ++q) {
@@ -132,19 +112,9 @@ __global__ __launch_bounds__(256, ChannelGradWaves<CH>::value) void blend_channe
     for (int c = 0; c < CH; ++c) g[c] = 0.0f;
     if (t.px < a.W && t.py < a.H && t.px < a.xlim && t.py < a.ylim) {
         const float *gp = ch.grad_map + frame_pixel(a, t.ty, t.px, t.py) * (size_t)ch.channels;
+        const ChannelRow<Q> row = load_channel_row<Q>(gp, nch, ch.vec_map);
 #pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            if (ch.vec_map && 4 * q + 4 <= nch) {
-                typedef float V4 __attribute__((ext_vector_type(4)));
-                const V4 v = ((const __attribute__((address_space(1))) V4 *)gp)[q];
-                g[4 * q] = v.x; g[4 * q + 1] = v.y; g[4 * q + 2] = v.z; g[4 * q + 3] = v.w;
-            } else {
-                if (4 * q + 0 < nch) g[4 * q + 0] = ldg(gp, 4 * q + 0);
-                if (4 * q + 1 < nch) g[4 * q + 1] = ldg(gp, 4 * q + 1);
-                if (4 * q + 2 < nch) g[4 * q + 2] = ldg(gp, 4 * q + 2);
-                if (4 * q + 3 < nch) g[4 * q + 3] = ldg(gp, 4 * q + 3);
-            }
-        }
+        for (int q = 0; q < Q; ++q) { g[4 * q] = row.v[q].x; g[4 * q + 1] = row.v[q].y; g[4 * q + 2] = row.v[q].z; g[4 * q + 3] = row.v[q].w; }
     }
 #pragma unroll
     for (int j = 0; j < CH; ++j) sG[j * 256 + tid] = 0.0f;  // published by the loop's top barrier
@@ -154,7 +124,25 @@ __global__ __launch_bounds__(256, ChannelGradWaves<CH>::value) void blend_channe
     bool wave_done = false;
     uint32_t fetched = 0;  // workgroup-uniform
     TileList<256> list = batches_begin<256, false>(a, t, tid, lds);
+    struct Entry { float2 g; float4 c; float L; int k; };
+    auto read = [&](int k) __attribute__((always_inline)) {
+        const Entry en = {*reinterpret_cast<const float2 *>(&s0[k]), s1[k], sL[k], k};
+        keep_b128(en.c);
+        return en;
+    };
+    auto eval = [&](const Entry &en) __attribute__((always_inline)) {
+        // the row's index goes through a vector register the compiler cannot see through: for an address it knows to be
+        // wave-uniform it wraps every LDS add into a loop that first sums the values of the active lanes
+        int at = en.k * CH;
+        asm volatile("" : "+v"(at));
+        const float w = blend_weight(en.g, en.c, en.L, fpx, fpy, T);
+        blend_channels_backward_add<CH>(w, g, nch, lane, &sG[at], &sId[en.k]);
+    };
     for (;;) {
+        // next_batch_planes (blend_weight_walk.h), spelled out: through the shared function the 16-channel kernel's median on the
+        // bench frame came out 0.03 % above the parent's slowest run of five (the function's extra lane-mask bookkeeping per batch,
+        // 23 scalar instructions); with its own head the kernel lies inside the parent's range at 8, 16 and 32 channels
+        // 
         __syncthreads();  // previous batch consumed AND flushed (and s_done initialised); a refilled ring published
         if (s_done == 4) break;  // uniform: every wave saturated
         uint32_t id = 0;
@@ -174,21 +162,9 @@ __global__ __launch_bounds__(256, ChannelGradWaves<CH>::value) void blend_channe
             for (int chunk = 0; chunk < nb; chunk += 64) {
                 const int e = chunk + lane;
                 const bool hit = e < nb && footprint_hits_rect(s0[e], s1[e], qx0, qx1, qy0, qy1);
-                unsigned long long m = __ballot(hit);
+                const unsigned long long m = __ballot(hit);
                 evaluated += (uint32_t)__popcll(m);
-                while (m) {
-                    const int k = chunk + (__ffsll((long long)m) - 1);
-                    m &= m - 1;
-                    const float2 gm = *reinterpret_cast<const float2 *>(&s0[k]);  // wave-uniform address: LDS broadcast
-                    const float4 c = s1[k];
-                    const float L = sL[k];
-                    asm volatile("" ::"v"(c.w));  // keep the read a ds_read_b128
-                    // the row's index goes through a vector register the compiler cannot see through: for an address it knows
-                    // to be wave-uniform it wraps every LDS add into a loop that first sums the values of the active lanes
-                    int at = k * CH;
-                    asm volatile("" : "+v"(at));
-                    blend_channels_backward_one<CH>(gm, c, L, fpx, fpy, T, g, nch, lane, &sG[at], &sId[k]);
-                }
+                walk_survivors_single(m, chunk, read, eval);
                 if (__all(T <= a.early_T)) {  // the forward's stop rule, where the forward evaluates it
                     wave_done = true;
                     wave_finished(lds, lane);
@@ -220,34 +196,29 @@ static void launch_width(int slots, const BlendArgs &a, const ChannelGradArgs &c
     hipLaunchKernelGGL(blend_channels_backward_kernel<CH>, dim3((unsigned)slots), dim3(256), 0, s, a, ch);
 }
 
-// launch_blend_channels' widths and its grouping of the channels into walks
-constexpr int CH_NARROW = 8, CH_WIDE = 16;
-
+// for_channel_groups with the gradient map in the place of the forward's map (vec_map is the forward's vec_out)
 int launch_blend_channels_backward(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
                                    const float *grad_map, int channels, float *grad_features, int64_t stride, hipStream_t s)
 {
-    if (ws.views > 1) { set_error("feature gradients: single views only"); return GSR_ERR_BAD_ARG; }
-    BlendArgs a = blend_args_common(cam, opts, ws, plan, nullptr, nullptr);  // no map is written; tile_work stays null
-    if (a.rows <= 0 || a.tiles_x <= 0) return GSR_OK;
-    const int slots = launch_tile_order(ws, plan, true, s);
-    for (int c0 = 0; c0 < channels;) {
-        const int rest = channels - c0;
-        const int width = rest > CH_NARROW ? CH_WIDE : CH_NARROW;
+    BlendArgs a;  // no map is written
+    int slots;
+    const int rc = weight_walk_begin("feature gradients", cam, opts, ws, plan, nullptr, nullptr, s, &a, &slots);
+    if (rc || !slots) return rc;
+    return for_channel_groups(grad_features, stride, grad_map, channels, 8, [&](const ChannelArgs &g, int width) -> int {
         ChannelGradArgs ch;
-        ch.grad_map = grad_map + c0;
-        ch.grad_features = grad_features + c0;
+        ch.grad_map = grad_map + g.c0;
+        ch.grad_features = grad_features + g.c0;
         ch.stride = stride;
         ch.channels = channels;
-        ch.nch = rest < width ? rest : width;
+        ch.nch = g.nch;
         ch.pad_shift = 0;
         while ((1 << ch.pad_shift) < ch.nch) ++ch.pad_shift;
-        ch.vec_map = reinterpret_cast<uintptr_t>(ch.grad_map) % 16 == 0 && channels % 4 == 0;  // the forward's vec_out
-        if (width == CH_WIDE) launch_width<CH_WIDE>(slots, a, ch, s);
-        else launch_width<CH_NARROW>(slots, a, ch, s);
+        ch.vec_map = g.vec_out;
+        if (width == 16) launch_width<16>(slots, a, ch, s);
+        else launch_width<8>(slots, a, ch, s);
         GSR_HIP(hipGetLastError());
-        c0 += ch.nch;
-    }
-    return GSR_OK;
+        return GSR_OK;
+    });
 }
 
 }  // namespace gsr

@@ -3,9 +3,8 @@
 // with the forward's weights w_i = alpha_i T_i.  The sum is what blend_channels_backward.hip gives for a one-channel map of ones;
 // the maximum and the count are no sum_p w G[p] and need this kernel.
 //
-// The workgroup is blend_channels_backward_kernel's (blend_common.h): 256 threads per 16x16 tile, wave = 8x8 quadrant, lane = pixel,
-// the same lists, staging, footprint ballots, stop rule, launch order and stat words; the weight of a (pixel, survivor) is
-// blend_channels_backward_one's first 14 issues in its order, so w and T are the forward's bit for bit.
+// The workgroup, the batch loop, the survivor walk (one per trip) and the weight are blend_weight_walk.h's, with
+// blend_channels_backward_kernel's staging, stop rule and flush after a batch: w and T are the forward's bit for bit.
 //
 // What differs:
 //   per lane      no gradient registers: one predicate `counted` — false outside the frame, in Q1's undrawn last column / row (where
@@ -34,9 +33,7 @@
 // = 8192 + 1024 + 1024 + 4096 + 4132 B = 18.0 KB: LDS allows 8 workgroups per CU, and so do the registers (launch bound 8).
 // Max and pixels do not depend on the order the atomics arrive in: two runs give the same bits.  The float sums may differ in
 // their last bits.
-#include "gsr_internal.h"
-#include "blend_args.h"
-#include "blend_common.h"
+#include "blend_weight_walk.h"
 
 namespace gsr {
 
@@ -49,14 +46,7 @@ struct GaussStatsArgs {
 
 constexpr int WANT_SUM = 1, WANT_MAX = 2, WANT_PIXELS = 4;
 
-// x + / max (x moved across lanes by the DPP control CTRL); lanes without a source lane take 0 (bound_ctrl), the identity of both for
-// x >= +0: one v_add_f32_dpp / v_max_u32_dpp.
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float x)
-{
-#pragma clang fp contract(off)
-    return x + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xF, 0xF, true));
-}
+// dpp_add's counterpart for the maximum; lanes without a source lane take 0 (bound_ctrl), the identity of both for x >= +0
 // (the maximum of the BIT PATTERNS, v_max_u32: for floats >= +0 that is the float maximum, and fmaxf would first quiet each operand
 // with a v_max_f32 x, x of its own — three issues a step instead of one)
 template <int CTRL>
@@ -77,18 +67,10 @@ __device__ __forceinline__ void wave_sum_max(float &s, uint32_t &m)
 #undef GSR_STEP
 }
 
-// One (pixel, survivor): blend_channels_backward_one's weight, then the wave's three statistics into the entry's row.
+// One survivor's weights w: the wave's three statistics into the entry's row.
 template <int WANT>
-__device__ __forceinline__ void gstats_one(const float2 gm, const float4 c, const float L, float fpx, float fpy, float &T, bool counted,
-                                           int lane, uint32_t *row)
+__device__ __forceinline__ void gstats_add(float w, bool counted, int lane, uint32_t *row)
 {
-    const float dx = gm.x - fpx, dy = gm.y - fpy;
-    const float p = fmaf(dx, fmaf(c.y, dy, c.x * dx), fmaf(c.z * dy, dy, L));  // log2 domain, opacity folded in
-    float alpha = fminf(__builtin_amdgcn_exp2f(p), GSR_MAX_ALPHA);
-    const bool valid = (alpha > GSR_MIN_ALPHA) & (p <= L);
-    alpha = valid ? alpha : 0.0f;
-    const float w = alpha * T;
-    T = fmaf(-T, alpha, T);
     const float wc = counted ? w : 0.0f;
     const unsigned long long b = __ballot(wc != 0.0f);
     if (b == 0) return;  // uniform: nothing to record for any pixel of the quadrant
@@ -139,41 +121,33 @@ __global__ __launch_bounds__(256, 8) void blend_gstats_kernel(BlendArgs args, co
         wave_done = true;
         wave_finished(lds, lane);
     }
-    for (;;) {
-        __syncthreads();  // previous batch consumed AND flushed; a refilled ring and the finished waves' count published
-        if (s_done == 4) break;  // uniform: every wave saturated (or has nothing to count)
-        uint32_t id = 0;
-        const int nb = tile_list_next<256>(a, list, s_ring, s_wc, &id);
-        if (nb < 0) continue;
-        if (nb == 0) break;
-        fetched += (uint32_t)nb;
-        if (tid < nb) {
-            const GaussRec *r = a.rec + id;
-            srec[0][tid] = r->q0;
-            srec[1][tid] = r->q1;
-            sL[tid] = ldg(&r->q2.x, 0);
-            sId[tid] = id;
-        }
-        __syncthreads();
+    struct Entry { float2 g; float4 c; float L; int k; };
+    auto stage = [&](uint32_t id, const GaussRec *r) __attribute__((always_inline)) {
+        sL[tid] = ldg(&r->q2.x, 0);
+        sId[tid] = id;
+    };
+    auto read = [&](int k) __attribute__((always_inline)) {
+        const Entry en = {*reinterpret_cast<const float2 *>(&s0[k]), s1[k], sL[k], k};
+        keep_b128(en.c);
+        return en;
+    };
+    auto eval = [&](const Entry &en) __attribute__((always_inline)) {
+        // the row's index goes through a vector register the compiler cannot see through: for an address it knows to be
+        // wave-uniform it wraps every LDS atomic into a loop that first reduces the values of the active lanes
+        int at = en.k;
+        asm volatile("" : "+v"(at));
+        const float w = blend_weight(en.g, en.c, en.L, fpx, fpy, T);
+        gstats_add<WANT>(w, counted, lane, reinterpret_cast<uint32_t *>(&sS[at]));
+    };
+    // (the loop's top barrier: previous batch consumed AND flushed; the finished waves' count published)
+    while (const int nb = next_batch_planes<256>(a, list, tid, lds, fetched, stage)) {
         if (!wave_done) {
             for (int chunk = 0; chunk < nb; chunk += 64) {
                 const int e = chunk + lane;
                 const bool hit = e < nb && footprint_hits_rect(s0[e], s1[e], qx0, qx1, qy0, qy1);
-                unsigned long long m = __ballot(hit);
+                const unsigned long long m = __ballot(hit);
                 evaluated += (uint32_t)__popcll(m);
-                while (m) {
-                    const int k = chunk + (__ffsll((long long)m) - 1);
-                    m &= m - 1;
-                    const float2 gm = *reinterpret_cast<const float2 *>(&s0[k]);  // wave-uniform address: LDS broadcast
-                    const float4 c = s1[k];
-                    const float L = sL[k];
-                    asm volatile("" ::"v"(c.w));  // keep the read a ds_read_b128
-                    // the row's index goes through a vector register the compiler cannot see through: for an address it knows
-                    // to be wave-uniform it wraps every LDS atomic into a loop that first reduces the values of the active lanes
-                    int at = k;
-                    asm volatile("" : "+v"(at));
-                    gstats_one<WANT>(gm, c, L, fpx, fpy, T, counted, lane, reinterpret_cast<uint32_t *>(&sS[at]));
-                }
+                walk_survivors_single(m, chunk, read, eval);
                 if (__all(T <= a.early_T)) {  // the forward's stop rule, where the forward evaluates it
                     wave_done = true;
                     wave_finished(lds, lane);
@@ -207,10 +181,10 @@ static void launch_want(int slots, const BlendArgs &a, const GaussStatsArgs &gs,
 int launch_blend_gstats(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const uint8_t *pixel_mask,
                         float *weight_sum, float *weight_max, uint32_t *pixels, hipStream_t s)
 {
-    if (ws.views > 1) { set_error("gaussian statistics: single views only"); return GSR_ERR_BAD_ARG; }
-    const BlendArgs a = blend_args_common(cam, opts, ws, plan, nullptr, nullptr);  // no map is written; tile_work stays null
-    if (a.rows <= 0 || a.tiles_x <= 0) return GSR_OK;
-    const int slots = launch_tile_order(ws, plan, true, s);
+    BlendArgs a;  // no map is written
+    int slots;
+    const int rc = weight_walk_begin("gaussian statistics", cam, opts, ws, plan, nullptr, nullptr, s, &a, &slots);
+    if (rc || !slots) return rc;
     const GaussStatsArgs gs = {pixel_mask, weight_sum, reinterpret_cast<uint32_t *>(weight_max), pixels};
     switch ((weight_sum ? WANT_SUM : 0) | (weight_max ? WANT_MAX : 0) | (pixels ? WANT_PIXELS : 0)) {
     case 1: launch_want<1>(slots, a, gs, s); break;

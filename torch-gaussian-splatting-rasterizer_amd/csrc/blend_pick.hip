@@ -5,9 +5,8 @@
 //   - and how many contributed: count = #{i : w_i(p) > 0}   (COUNT instantiation only).
 // A per-pixel gather: no atomics, nothing per gaussian is written.
 //
-// The workgroup is blend_kernel's (blend_common.h): 256 threads per 16x16 tile, wave = 8x8 quadrant, lane = pixel, the same lists
-// (tile_list_of / tile_list_next), the same footprint test by wave ballot, the same launch order, and per (pixel, survivor)
-// blend_one's arithmetic in blend_one's order up to w = alpha T and its T = T - w: w and T are the feature blend's, bit for bit.
+// The workgroup, the batch loop, the survivor walk and the weight w = alpha T with its T are blend_weight_walk.h's: w and T are the
+// feature blend's, bit for bit.
 // In the place of the colour sums a survivor costs one compare and two selects for the maximum, one compare-and-select for the
 // median and (COUNT) one compare-and-add.
 //
@@ -32,9 +31,7 @@
 //   ring [1024] + wc [8] + done: tile_list_next's
 // = 8192 + 2048 + 4132 B = 14.4 KB: LDS allows 11 workgroups per CU, the 8 waves per SIMD of 64 VGPRs allow 8.
 // The record's colour words are neither read nor written and tile_work is only read, as in blend_features.hip.
-#include "gsr_internal.h"
-#include "blend_args.h"
-#include "blend_common.h"
+#include "blend_weight_walk.h"
 
 namespace gsr {
 
@@ -45,27 +42,6 @@ struct PickArgs {
     int32_t *count;      // COUNT only
     float median_T;      // in (0, 1]
 };
-
-// blend_one up to w and its T update, with the pick accumulators in the place of the colour sums.
-template <bool COUNT>
-__device__ __forceinline__ void pick_one(const float2 g, const float4 c, const float2 o, float median_T, float fpx, float fpy, float &T,
-                                         float &best_w, int &best_id, int &med_id, int &count)
-{
-    const float L = o.x;
-    const int id = __float_as_int(o.y);
-    const float dx = g.x - fpx, dy = g.y - fpy;
-    const float p = fmaf(dx, fmaf(c.y, dy, c.x * dx), fmaf(c.z * dy, dy, L));  // log2 domain, opacity folded in
-    float alpha = fminf(__builtin_amdgcn_exp2f(p), GSR_MAX_ALPHA);
-    const bool valid = (alpha > GSR_MIN_ALPHA) & (p <= L);
-    alpha = valid ? alpha : 0.0f;
-    const float w = alpha * T;
-    const bool better = w > best_w;  // strict: on equal weights the earlier one in draw order stays (and w == 0 never wins)
-    best_w = better ? w : best_w;
-    best_id = better ? id : best_id;
-    T = T - w;
-    med_id = ((med_id < 0) & (T < median_T)) ? id : med_id;  // the first entry AFTER which T < median_T
-    if (COUNT) count += w > 0.0f ? 1 : 0;
-}
 
 template <bool COUNT>
 __global__ __launch_bounds__(256, 8) void blend_pick_kernel(BlendArgs args, const PickArgs pk)
@@ -92,55 +68,33 @@ __global__ __launch_bounds__(256, 8) void blend_pick_kernel(BlendArgs args, cons
     bool wave_done = false;
     uint32_t fetched = 0;  // workgroup-uniform
     TileList<256> list = batches_begin<256, false>(a, t, tid, lds);
-    for (;;) {
-        // next_batch (blend_common.h) with this kernel's planes
-        __syncthreads();  // previous batch fully consumed (and s_done initialised); a refilled ring published
-        if (s_done == 4) break;  // uniform: every wave has finished
-        uint32_t id = 0;
-        const int nb = tile_list_next<256>(a, list, s_ring, s_wc, &id);
-        if (nb < 0) continue;
-        if (nb == 0) break;
-        fetched += (uint32_t)nb;
-        if (tid < nb) {
-            const GaussRec *r = a.rec + id;
-            srec[0][tid] = r->q0;
-            srec[1][tid] = r->q1;
-            sP[tid] = make_float2(ldg(&r->q2.x, 0), __uint_as_float(id));  // the id: the index into the scene arrays
-        }
-        __syncthreads();
+    struct Entry { float2 g; float4 c; float2 o; };
+    auto stage = [&](uint32_t id, const GaussRec *r) __attribute__((always_inline)) {
+        sP[tid] = make_float2(ldg(&r->q2.x, 0), __uint_as_float(id));  // the id: the index into the scene arrays
+    };
+    auto read = [&](int k) __attribute__((always_inline)) {
+        const Entry en = {*reinterpret_cast<const float2 *>(&s0[k]), s1[k], sP[k]};
+        keep_b128(en.c);
+        return en;
+    };
+    // the pick accumulators in the place of blend_one's colour sums
+    auto eval = [&](const Entry &en) __attribute__((always_inline)) {
+        const int id = __float_as_int(en.o.y);
+        const float w = blend_weight(en.g, en.c, en.o.x, fpx, fpy, T);
+        const bool better = w > best_w;  // strict: on equal weights the earlier one in draw order stays (and w == 0 never wins)
+        best_w = better ? w : best_w;
+        best_id = better ? id : best_id;
+        med_id = ((med_id < 0) & (T < median_T)) ? id : med_id;  // the first entry AFTER which T < median_T
+        if (COUNT) count += w > 0.0f ? 1 : 0;
+    };
+    while (const int nb = next_batch_planes<256>(a, list, tid, lds, fetched, stage)) {
         if (wave_done) continue;
         for (int chunk = 0; chunk < nb; chunk += 64) {
             const int e = chunk + lane;
             const bool hit = e < nb && footprint_hits_rect(s0[e], s1[e], qx0, qx1, qy0, qy1);
-            unsigned long long m = __ballot(hit);
+            const unsigned long long m = __ballot(hit);
             evaluated += (uint32_t)__popcll(m);
-            // two survivors per trip so that the second one's LDS reads overlap the first one's arithmetic; an odd one out comes
-            // last, after the loop (blend_channels_kernel's form: as a second arm inside it the two arms' accumulators meet in
-            // register copies every trip)
-            while (m & (m - 1)) {
-                const int k0 = chunk + (__ffsll((long long)m) - 1);
-                m &= m - 1;
-                const int k1 = chunk + (__ffsll((long long)m) - 1);
-                m &= m - 1;
-                const float2 ga = *reinterpret_cast<const float2 *>(&s0[k0]);  // wave-uniform address: LDS broadcast
-                const float4 ca = s1[k0];
-                const float2 oa = sP[k0];
-                asm volatile("" ::"v"(ca.w));  // keep the read a ds_read_b128 (4 LDS cycles); a b96 costs 8
-                const float2 gb = *reinterpret_cast<const float2 *>(&s0[k1]);
-                const float4 cb = s1[k1];
-                const float2 ob = sP[k1];
-                asm volatile("" ::"v"(cb.w));
-                pick_one<COUNT>(ga, ca, oa, median_T, fpx, fpy, T, best_w, best_id, med_id, count);
-                pick_one<COUNT>(gb, cb, ob, median_T, fpx, fpy, T, best_w, best_id, med_id, count);
-            }
-            if (m) {
-                const int k0 = chunk + (__ffsll((long long)m) - 1);
-                const float2 ga = *reinterpret_cast<const float2 *>(&s0[k0]);
-                const float4 ca = s1[k0];
-                const float2 oa = sP[k0];
-                asm volatile("" ::"v"(ca.w));
-                pick_one<COUNT>(ga, ca, oa, median_T, fpx, fpy, T, best_w, best_id, med_id, count);
-            }
+            walk_survivors(m, chunk, read, eval);
             // the rules of the comment at the top (a negative early_T never fires: "blend every entry")
             const bool finished = COUNT ? T <= a.early_T : !drawn | (T <= a.early_T) | ((med_id >= 0) & (T <= best_w));
             if (__all(finished)) {
@@ -164,11 +118,10 @@ __global__ __launch_bounds__(256, 8) void blend_pick_kernel(BlendArgs args, cons
 int launch_blend_pick(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, float median_T,
                       int32_t *out_best_id, float *out_best_w, int32_t *out_median_id, int32_t *out_count, hipStream_t s)
 {
-    if (ws.views > 1) { set_error("pick maps: single views only"); return GSR_ERR_BAD_ARG; }
-    const BlendArgs a = blend_args_common(cam, opts, ws, plan, nullptr, nullptr);  // tile_work stays null: never written here
-    if (a.rows <= 0 || a.tiles_x <= 0) return GSR_OK;
-    // heaviest tiles first, by what the last colour blend on this workspace staged where that is known (a schedule only)
-    const int slots = launch_tile_order(ws, plan, true, s);
+    BlendArgs a;
+    int slots;
+    const int rc = weight_walk_begin("pick maps", cam, opts, ws, plan, nullptr, nullptr, s, &a, &slots);
+    if (rc || !slots) return rc;
     const PickArgs pk = {out_best_id, out_best_w, out_median_id, out_count, median_T};
     if (out_count) hipLaunchKernelGGL(blend_pick_kernel<true>, dim3((unsigned)slots), dim3(256), 0, s, a, pk);
     else hipLaunchKernelGGL(blend_pick_kernel<false>, dim3((unsigned)slots), dim3(256), 0, s, a, pk);

@@ -3,11 +3,9 @@
 // skipped, not blended), and out_final_T[p] the product of (1 - alpha_i) over the same gaussians.  z_i is the gaussian's camera-space
 // depth, the float the depth sort orders the lists by.
 //
-// The kernel is blend_channels_kernel (blend_channels.hip) with one more staged word: the same workgroup (256 threads per 16x16 tile,
-// wave = 8x8 quadrant, lane = pixel), the same lists (tile_list_of / tile_list_next), the same staging of the records and the rows,
-// the same footprint test by wave ballot, the same launch order, and per channel its arithmetic in its order — w = alpha T,
-// C_c = fma(w, f_c, C_c), T = fma(-T, alpha, T).  With open limits every bit of the map and of T is that kernel's, and so are
-// wave_entries / fetched_entries.
+// The kernel is blend_channels_kernel (blend_channels.hip) with one more staged word, built from the same pieces
+// (blend_weight_walk.h): workgroup, batch loop, staging of the rows, survivor walk, weight and channel update.  With open limits
+// every bit of the map and of T is that kernel's, and so are wave_entries / fetched_entries.
 //
 // What is added:
 //   - staging: the staging thread loads its gaussian's mean (12 B) and computes z = ((x V2 + y V6) + z V10) + V14 — the preprocess'
@@ -17,9 +15,10 @@
 //     draw anything (not NaN, near < far) are reduced across the wave once;
 //   - ballot: the lane that tests entry e also requires near_q <= z_e < far_q: an entry outside the quadrant's range is never walked
 //     and not counted in wave_entries;
-//   - walk: a survivor's `valid` gains (z >= near) & (z < far) for the lane's own limits — unless the whole chunk of 64 entries lies
-//     inside every pixel's range (near_hi <= z_first, z_last < far_lo; the list is ascending), when the walk is the channel blend's
-//     as it stands (the bypass; GSR_SLAB_NO_BYPASS builds the kernel without it for the A/B in tools/slab_ab.py);
+//   - walk: a survivor's `valid` gains (z >= near) & (z < far) for the lane's own limits (blend_weight's `admit`) — unless the whole
+//     chunk of 64 entries lies inside every pixel's range (near_hi <= z_first, z_last < far_lo; the list is ascending), when the
+//     walk is the channel blend's as it stands (the bypass; GSR_SLAB_NO_BYPASS builds the kernel without it for the A/B in
+//     tools/slab_ab.py);
 //   - stop: a quadrant has finished once every pixel has T <= early_out_T (pixels that can draw nothing do not count), or once a
 //     staged entry has z_e >= far_q.  The second rule is exact: the list is ascending in the key bits, the key of a visible gaussian
 //     (z >= 0.2) is the bit pattern of z, so every later entry has z >= z_e >= far_q >= far[p] and fails every pixel's test.
@@ -28,10 +27,7 @@
 //
 // LDS per workgroup: blend_channels_kernel's + 1 KB (sZ): 9216 + 1024 * CH + 5156 B.
 #include <type_traits>
-#include "gsr_internal.h"
-#include "blend_args.h"
-#include "blend_common.h"
-#include "blend_channels.h"
+#include "blend_weight_walk.h"
 
 namespace gsr {
 
@@ -55,28 +51,6 @@ __device__ __forceinline__ float slab_depth(const SlabArgs &s, float x, float y,
     float t = opaque_mul(x, s.v2) + opaque_mul(y, s.v6);
     t = t + opaque_mul(z, s.v10);
     return t + s.v14;
-}
-
-// blend_channels_one, and with TEST the lane's own limits in `valid`.
-template <int CH, bool TEST>
-__device__ __forceinline__ void blend_slab_one(const float2 g, const float4 c, const float L, const float z, const float4 (&f)[CH / 4],
-                                               float fpx, float fpy, float near, float far, float &T, float (&acc)[CH])
-{
-    const float dx = g.x - fpx, dy = g.y - fpy;
-    const float p = fmaf(dx, fmaf(c.y, dy, c.x * dx), fmaf(c.z * dy, dy, L));  // log2 domain, opacity folded in
-    float alpha = fminf(__builtin_amdgcn_exp2f(p), GSR_MAX_ALPHA);
-    bool valid = (alpha > GSR_MIN_ALPHA) & (p <= L);
-    if (TEST) valid = valid & (z >= near) & (z < far);  // (a NaN limit fails both)
-    alpha = valid ? alpha : 0.0f;
-    const float w = alpha * T;
-#pragma unroll
-    for (int q = 0; q < CH / 4; ++q) {
-        acc[4 * q + 0] = fmaf(w, f[q].x, acc[4 * q + 0]);
-        acc[4 * q + 1] = fmaf(w, f[q].y, acc[4 * q + 1]);
-        acc[4 * q + 2] = fmaf(w, f[q].z, acc[4 * q + 2]);
-        acc[4 * q + 3] = fmaf(w, f[q].w, acc[4 * q + 3]);
-    }
-    T = fmaf(-T, alpha, T);  // what the channel blend's T - w compiles to
 }
 
 // waves per SIMD the register allocator aims at: what the LDS lets a CU hold
@@ -140,86 +114,43 @@ __global__ __launch_bounds__(256, SlabWaves<CH>::value) void blend_slab_kernel(B
     uint32_t fetched = 0;  // workgroup-uniform
     const int nch = ch.nch;
     TileList<256> list = batches_begin<256, false>(a, t, tid, lds);
-    for (;;) {
-        // next_batch (blend_common.h) with this kernel's planes
-        __syncthreads();  // previous batch fully consumed (and s_done initialised); a refilled ring published
-        if (s_done == 4) break;  // uniform: every wave has finished
-        uint32_t id = 0;
-        const int nb = tile_list_next<256>(a, list, s_ring, s_wc, &id);
-        if (nb < 0) continue;
-        if (nb == 0) break;
-        fetched += (uint32_t)nb;
-        if (tid < nb) {
-            const GaussRec *r = a.rec + id;
-            const float *row = ch.features + (size_t)id * (size_t)ch.stride;
-            const float *m = means + 3 * (size_t)id;
-            srec[0][tid] = r->q0;
-            srec[1][tid] = r->q1;
-            sL[tid] = ldg(&r->q2.x, 0);
-            sZ[tid] = slab_depth(sl, ldg(m, 0), ldg(m, 1), ldg(m, 2));
+    struct Entry { float2 g; float4 c; float L, z; float4 f[Q]; };
+    auto stage = [&](uint32_t id, const GaussRec *r) __attribute__((always_inline)) {
+        const float *m = means + 3 * (size_t)id;
+        sL[tid] = ldg(&r->q2.x, 0);
+        sZ[tid] = slab_depth(sl, ldg(m, 0), ldg(m, 1), ldg(m, 2));
+        const ChannelRow<Q> row = load_channel_row<Q>(ch.features + (size_t)id * (size_t)ch.stride, nch, ch.vec_in);
 #pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);  // absent channels: not loaded
-                if (ch.vec_in && 4 * q + 4 <= nch) {
-                    v = ldg4(row, q);
-                } else {
-                    if (4 * q + 0 < nch) v.x = ldg(row, 4 * q + 0);
-                    if (4 * q + 1 < nch) v.y = ldg(row, 4 * q + 1);
-                    if (4 * q + 2 < nch) v.z = ldg(row, 4 * q + 2);
-                    if (4 * q + 3 < nch) v.w = ldg(row, 4 * q + 3);
-                }
-                sF[q][tid] = v;
-            }
-        }
-        __syncthreads();
+        for (int q = 0; q < Q; ++q) sF[q][tid] = row.v[q];
+    };
+    while (const int nb = next_batch_planes<256>(a, list, tid, lds, fetched, stage)) {
         if (wave_done) continue;
         for (int chunk = 0; chunk < nb; chunk += 64) {
             const int e = chunk + lane;
             const float ze = e < nb ? sZ[e] : -INF;
             const bool hit = e < nb && footprint_hits_rect(s0[e], s1[e], qx0, qx1, qy0, qy1) && near_q <= ze && ze < far_q;
             const bool past = __any(ze >= far_q);  // this entry and every later one lie behind every pixel's far limit
-            unsigned long long m = __ballot(hit);
+            const unsigned long long m = __ballot(hit);
             evaluated += (uint32_t)__popcll(m);
-            // the survivors, two per trip so that the second one's LDS reads overlap the first one's arithmetic, an odd one out last
-            // (blend_channels_kernel's walk); test_c: the lanes compare the entry's depth with their own limits
+            // the channel blend's walk; test_c: the lanes compare the entry's depth with their own limits (a NaN limit fails both)
             auto walk = [&](auto test_c) __attribute__((always_inline)) {
                 constexpr bool TEST = decltype(test_c)::value;
-                while (m & (m - 1)) {
-                    const int k0 = chunk + (__ffsll((long long)m) - 1);
-                    m &= m - 1;
-                    const int k1 = chunk + (__ffsll((long long)m) - 1);
-                    m &= m - 1;
-                    const float2 ga = *reinterpret_cast<const float2 *>(&s0[k0]);  // wave-uniform address: LDS broadcast
-                    const float4 ca = s1[k0];
-                    const float La = sL[k0];
-                    const float za = TEST ? sZ[k0] : 0.0f;
-                    float4 fa[Q];
+                walk_survivors(m, chunk,
+                    [&](int k) __attribute__((always_inline)) {
+                        Entry en;
+                        en.g = *reinterpret_cast<const float2 *>(&s0[k]);
+                        en.c = s1[k];
+                        en.L = sL[k];
+                        en.z = TEST ? sZ[k] : 0.0f;
 #pragma unroll
-                    for (int q = 0; q < Q; ++q) fa[q] = sF[q][k0];
-                    asm volatile("" ::"v"(ca.w));  // keep the read a ds_read_b128 (4 LDS cycles); a b96 costs 8
-                    const float2 gb = *reinterpret_cast<const float2 *>(&s0[k1]);
-                    const float4 cb = s1[k1];
-                    const float Lb = sL[k1];
-                    const float zb = TEST ? sZ[k1] : 0.0f;
-                    float4 fb[Q];
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) fb[q] = sF[q][k1];
-                    asm volatile("" ::"v"(cb.w));
-                    blend_slab_one<CH, TEST>(ga, ca, La, za, fa, fpx, fpy, near, far, T, acc);
-                    blend_slab_one<CH, TEST>(gb, cb, Lb, zb, fb, fpx, fpy, near, far, T, acc);
-                }
-                if (m) {
-                    const int k0 = chunk + (__ffsll((long long)m) - 1);
-                    const float2 ga = *reinterpret_cast<const float2 *>(&s0[k0]);
-                    const float4 ca = s1[k0];
-                    const float La = sL[k0];
-                    const float za = TEST ? sZ[k0] : 0.0f;
-                    float4 fa[Q];
-#pragma unroll
-                    for (int q = 0; q < Q; ++q) fa[q] = sF[q][k0];
-                    asm volatile("" ::"v"(ca.w));
-                    blend_slab_one<CH, TEST>(ga, ca, La, za, fa, fpx, fpy, near, far, T, acc);
-                }
+                        for (int q = 0; q < Q; ++q) en.f[q] = sF[q][k];
+                        keep_b128(en.c);
+                        return en;
+                    },
+                    [&](const Entry &en) __attribute__((always_inline)) {
+                        const bool admit = !TEST || ((en.z >= near) & (en.z < far));
+                        blend_channels_add<Q>(blend_weight(en.g, en.c, en.L, fpx, fpy, T, admit), en.f, acc);
+                    });
             };
             // every pixel of the quadrant admits every entry of the chunk: the first is the nearest, the last the farthest
             if (BYPASS && near_hi <= sZ[chunk] && sZ[min(chunk + 63, nb - 1)] < far_lo) walk(std::false_type{});  // uniform
@@ -236,20 +167,7 @@ __global__ __launch_bounds__(256, SlabWaves<CH>::value) void blend_slab_kernel(B
     if (t.px < a.W && t.py < a.H) {
         const bool drawn = t.px < a.xlim && t.py < a.ylim;  // Q1: last column / row stay zero, T stays 1
         const size_t pix = frame_pixel(a, t.ty, t.px, t.py);
-        float *o = static_cast<float *>(a.out) + pix * (size_t)ch.channels + ch.c0;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const float4 v = make_float4(drawn ? acc[4 * q] : 0.0f, drawn ? acc[4 * q + 1] : 0.0f, drawn ? acc[4 * q + 2] : 0.0f,
-                                         drawn ? acc[4 * q + 3] : 0.0f);
-            if (ch.vec_out && 4 * q + 4 <= nch) {
-                reinterpret_cast<float4 *>(o)[q] = v;
-            } else {
-                if (4 * q + 0 < nch) o[4 * q + 0] = v.x;
-                if (4 * q + 1 < nch) o[4 * q + 1] = v.y;
-                if (4 * q + 2 < nch) o[4 * q + 2] = v.z;
-                if (4 * q + 3 < nch) o[4 * q + 3] = v.w;
-            }
-        }
+        store_channel_pixel<Q>(static_cast<float *>(a.out) + pix * (size_t)ch.channels + ch.c0, acc, nch, ch.vec_out, drawn);
         if (a.out_T) a.out_T[pix] = drawn ? T : 1.0f;
     }
 }
@@ -260,38 +178,24 @@ static void launch_width(int slots, const BlendArgs &a, const ChannelArgs &ch, c
     hipLaunchKernelGGL(blend_slab_kernel<CH>, dim3((unsigned)slots), dim3(256), 0, s, a, ch, sl);
 }
 
-// The instantiated widths: a map of up to 4 channels takes one walk of 4, up to 8 one of 8, a wider one walks of 16 with the rest
-// in the narrowest width that holds it (launch_blend_channels' rule with one more width below it).
+// The instantiated widths: for_channel_groups' with 4 as the narrowest — a map of up to 4 channels takes one walk of 4.
 int launch_blend_slab(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *means,
                       const float *features, int channels, int64_t stride, const float *depth_near, const float *depth_far,
                       float *out_map, float *out_T, hipStream_t s)
 {
-    if (ws.views > 1) { set_error("feature maps: single views only"); return GSR_ERR_BAD_ARG; }
-    BlendArgs a = blend_args_common(cam, opts, ws, plan, out_map, out_T);  // tile_work stays null: never written here
-    if (a.rows <= 0 || a.tiles_x <= 0) return GSR_OK;
+    BlendArgs a;
+    int slots;
+    const int rc = weight_walk_begin("feature maps", cam, opts, ws, plan, out_map, out_T, s, &a, &slots);
+    if (rc || !slots) return rc;
     const SlabArgs sl = {depth_near, depth_far, means, cam.w2c[2], cam.w2c[6], cam.w2c[10], cam.w2c[14]};
-    // heaviest tiles first, by what the last colour blend on this workspace staged where that is known (a schedule only)
-    const int slots = launch_tile_order(ws, plan, true, s);
-    for (int c0 = 0; c0 < channels;) {
-        const int rest = channels - c0;
-        const int width = rest > 8 ? 16 : rest > 4 ? 8 : 4;
-        ChannelArgs ch;
-        ch.features = features + c0;
-        ch.stride = stride;
-        ch.channels = channels;
-        ch.c0 = c0;
-        ch.nch = rest < width ? rest : width;
-        // 16-byte accesses where every row / pixel of this group starts on a 16-byte boundary
-        ch.vec_in = reinterpret_cast<uintptr_t>(ch.features) % 16 == 0 && stride % 4 == 0;
-        ch.vec_out = reinterpret_cast<uintptr_t>(out_map + c0) % 16 == 0 && channels % 4 == 0;
+    return for_channel_groups(features, stride, out_map, channels, 4, [&](const ChannelArgs &ch, int width) -> int {
         if (width == 16) launch_width<16>(slots, a, ch, sl, s);
         else if (width == 8) launch_width<8>(slots, a, ch, sl, s);
         else launch_width<4>(slots, a, ch, sl, s);
         GSR_HIP(hipGetLastError());
         a.out_T = nullptr;  // every group ends with the same T: the first one's store is enough
-        c0 += ch.nch;
-    }
-    return GSR_OK;
+        return GSR_OK;
+    });
 }
 
 }  // namespace gsr

@@ -6,9 +6,8 @@
 // ids and weights, k <= GSR_MAX_TOPK, unused slots -1 / 0.  A per-pixel gather like the pick maps: no atomics, nothing per gaussian
 // is written.
 //
-// The workgroup is blend_pick_kernel's (blend_pick.hip): 256 threads per 16x16 tile, wave = 8x8 quadrant, lane = pixel, the same
-// lists, staging ({q0, q1, {log2 opacity, id}}), footprint ballot, launch order and two survivors per trip, and per (pixel,
-// survivor) blend_one's arithmetic in blend_one's order up to w = alpha T and T = T - w: w and T are the feature blend's, bit for bit.
+// The workgroup, the survivor walk and the weight w = alpha T with its T are blend_weight_walk.h's, the staging
+// ({q0, q1, {log2 opacity, id}}) blend_pick_kernel's: w and T are the feature blend's, bit for bit.
 // In the place of the argmax each lane keeps K weights and K ids in registers; K is instantiated at 4, 8 and 16, a request for k runs
 // the smallest K >= k and stores k slots.
 //
@@ -47,9 +46,7 @@
 // SIMD (64 VGPRs) at K = 4, 6 (80) at K = 8, 4 (128) at K = 16; no instantiation uses scratch (tools/kernel_resources.sh
 // blend_topk.hip; the table is in DESIGN.md §5.16).
 // The record's colour words are neither read nor written and tile_work is only read, as in blend_pick.hip.
-#include "gsr_internal.h"
-#include "blend_args.h"
-#include "blend_common.h"
+#include "blend_weight_walk.h"
 
 namespace gsr {
 
@@ -60,22 +57,6 @@ struct TopkArgs {
     int k;             // 1 .. K slots are stored
     int vec;           // k % 4 == 0 and both planes 16-byte aligned: 16-byte stores
 };
-
-// blend_one up to w and its T update (pick_one's lines, in pick_one's order); the weight goes to the caller's lists.
-__device__ __forceinline__ float topk_weight(const float2 g, const float4 c, const float L, float fpx, float fpy, float &T)
-{
-    const float dx = g.x - fpx, dy = g.y - fpy;
-    const float p = fmaf(dx, fmaf(c.y, dy, c.x * dx), fmaf(c.z * dy, dy, L));  // log2 domain, opacity folded in
-    float alpha = fminf(__builtin_amdgcn_exp2f(p), GSR_MAX_ALPHA);
-    const bool valid = (alpha > GSR_MIN_ALPHA) & (p <= L);
-    alpha = valid ? alpha : 0.0f;
-    const float w = alpha * T;
-    // blend_one's T - w.  Every blend kernel of the library compiles that into this fma (the contraction next_batch's comment in
-    // blend_common.h speaks of); here the insertion's branch stands between the product and the difference, the compiler
-    // contracted some of them and not others, and T was no longer the feature blend's: spelled out
-    T = fmaf(-T, alpha, T);
-    return w;
-}
 
 // Both lists S slots to the left (S a power of two; what comes in at the far end is never stored)
 template <int K, int S>
@@ -161,8 +142,27 @@ __global__ __launch_bounds__(256, topk_min_waves(K)) void blend_topk_kernel(Blen
     bool wave_done = false;
     uint32_t fetched = 0;  // workgroup-uniform
     TileList<256> list = batches_begin<256, false>(a, t, tid, lds);
+    struct Entry { float2 g; float4 c; float2 o; };
+    auto read = [&](int k) __attribute__((always_inline)) {
+        const Entry en = {*reinterpret_cast<const float2 *>(&s0[k]), s1[k], sP[k]};
+        keep_b128(en.c);
+        return en;
+    };
+    auto eval = [&](const Entry &en) __attribute__((always_inline)) {
+        const float w = blend_weight(en.g, en.c, en.o.x, fpx, fpy, T);
+        topk_take<K, NEAREST>(wk, ik, filled, k, w, __float_as_int(en.o.y));
+    };
+    // a trip's two: both weights (and T) first, in draw order, then the two go to the lists in that order
+    auto eval2 = [&](const Entry &ea, const Entry &eb) __attribute__((always_inline)) {
+        const float wa = blend_weight(ea.g, ea.c, ea.o.x, fpx, fpy, T);
+        const float wb = blend_weight(eb.g, eb.c, eb.o.x, fpx, fpy, T);
+        topk_take<K, NEAREST>(wk, ik, filled, k, wa, __float_as_int(ea.o.y));
+        topk_take<K, NEAREST>(wk, ik, filled, k, wb, __float_as_int(eb.o.y));
+    };
     for (;;) {
-        // next_batch (blend_common.h) with this kernel's planes
+        // next_batch_planes (blend_weight_walk.h), spelled out: through the shared function the loop keeps more lane masks in
+        // scalar registers, the K = 4 kernels run out of the 80 their eight waves per SIMD leave them and park six of them in a
+        // vector register of their own, 43 VGPRs against 42
         __syncthreads();  // previous batch fully consumed (and s_done initialised); a refilled ring published
         if (s_done == 4) break;  // uniform: every wave has finished
         uint32_t id = 0;
@@ -181,37 +181,9 @@ __global__ __launch_bounds__(256, topk_min_waves(K)) void blend_topk_kernel(Blen
         for (int chunk = 0; chunk < nb; chunk += 64) {
             const int e = chunk + lane;
             const bool hit = e < nb && footprint_hits_rect(s0[e], s1[e], qx0, qx1, qy0, qy1);
-            unsigned long long m = __ballot(hit);
+            const unsigned long long m = __ballot(hit);
             evaluated += (uint32_t)__popcll(m);
-            // two survivors per trip so that the second one's LDS reads overlap the first one's arithmetic; both weights (and T)
-            // first, in draw order, then the two go to the lists in that order
-            while (m & (m - 1)) {
-                const int k0 = chunk + (__ffsll((long long)m) - 1);
-                m &= m - 1;
-                const int k1 = chunk + (__ffsll((long long)m) - 1);
-                m &= m - 1;
-                const float2 ga = *reinterpret_cast<const float2 *>(&s0[k0]);  // wave-uniform address: LDS broadcast
-                const float4 ca = s1[k0];
-                const float2 oa = sP[k0];
-                asm volatile("" ::"v"(ca.w));  // keep the read a ds_read_b128 (4 LDS cycles); a b96 costs 8
-                const float2 gb = *reinterpret_cast<const float2 *>(&s0[k1]);
-                const float4 cb = s1[k1];
-                const float2 ob = sP[k1];
-                asm volatile("" ::"v"(cb.w));
-                const float wa = topk_weight(ga, ca, oa.x, fpx, fpy, T);
-                const float wb = topk_weight(gb, cb, ob.x, fpx, fpy, T);
-                topk_take<K, NEAREST>(wk, ik, filled, k, wa, __float_as_int(oa.y));
-                topk_take<K, NEAREST>(wk, ik, filled, k, wb, __float_as_int(ob.y));
-            }
-            if (m) {
-                const int k0 = chunk + (__ffsll((long long)m) - 1);
-                const float2 ga = *reinterpret_cast<const float2 *>(&s0[k0]);
-                const float4 ca = s1[k0];
-                const float2 oa = sP[k0];
-                asm volatile("" ::"v"(ca.w));
-                const float wa = topk_weight(ga, ca, oa.x, fpx, fpy, T);
-                topk_take<K, NEAREST>(wk, ik, filled, k, wa, __float_as_int(oa.y));
-            }
+            walk_survivors(m, chunk, read, eval, eval2);
             // the rules of the comment at the top (a negative early_T never fires: "blend every entry")
             const bool settled = !drawn | (NEAREST ? (filled >= k) | (T <= 0.0f) : T <= wk[K - 1]);
             if (__all(T <= a.early_T) || (lists_only && __all(settled))) {
@@ -265,11 +237,10 @@ static void launch_topk_k(bool nearest, int slots, const BlendArgs &a, const Top
 int launch_blend_topk(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, int k, int select,
                       int32_t *out_ids, float *out_weights, float *out_final_T, hipStream_t s)
 {
-    if (ws.views > 1) { set_error("top-k lists: single views only"); return GSR_ERR_BAD_ARG; }
-    const BlendArgs a = blend_args_common(cam, opts, ws, plan, nullptr, nullptr);  // tile_work stays null: never written here
-    if (a.rows <= 0 || a.tiles_x <= 0) return GSR_OK;
-    // heaviest tiles first, by what the last colour blend on this workspace staged where that is known (a schedule only)
-    const int slots = launch_tile_order(ws, plan, true, s);
+    BlendArgs a;
+    int slots;
+    const int rc = weight_walk_begin("top-k lists", cam, opts, ws, plan, nullptr, nullptr, s, &a, &slots);
+    if (rc || !slots) return rc;
     const bool aligned = ((reinterpret_cast<uintptr_t>(out_ids) | reinterpret_cast<uintptr_t>(out_weights)) & 15u) == 0;
     const TopkArgs tk = {out_ids, out_weights, out_final_T, k, (k % 4 == 0 && aligned) ? 1 : 0};
     const bool nearest = select == GSR_TOPK_NEAREST;
