@@ -1,0 +1,231 @@
+"""GPU: what the host side of every public single-view call of Rasterizer asks of libgsr — which entries, in which order, with which
+options — read off a recording proxy around renderer.lib that forwards every call to the real library.
+
+Three things per call, none of them a number the code under test produces:
+  a. the entry sequence, written out below (CALLS);
+  b. chaining: after an enqueue() that no stats() has read, every options struct the call passes before its first gsr_read_stats
+     has keep_flags = 1 (0 with nothing unchecked), and a shard without tile rows calls no render, list or blend entry at all;
+  c. the retry: on a rasterizer whose pair buffer (max_pairs = 64) is too small for the scene the attempt runs twice, max_pairs
+     grows and the result is the roomy rasterizer's — bit for bit, except the float atomic sums (the gradient, weight_sum), which
+     are held to the bar test_gpu_channels_backward applies between two runs of one gradient; a caller's `out` ends as what it
+     held before plus ONE view's contribution: the overflowed first attempt added nothing.
+
+Scene: test_gpu_pick's 40 x 24 deep-tile scene (1000 gaussians, two tile rows).
+"""
+import pytest
+import torch
+
+from test_gpu_channels_backward import _bar
+from test_gpu_pick import _deep_tile_scene
+
+pytestmark = pytest.mark.gpu
+
+STATS = ("gsr_read_stats",)
+LISTS = ("gsr_preprocess", "gsr_bin_sort")
+Z = ("gsr_project_to_camera_space",)
+# call -> (entries before the checked attempt, entries of one attempt (gsr_read_stats follows each), entries after the last check)
+CALLS = {
+    "render": ((), ("gsr_render_forward",), ()),
+    "features2": ((), ("gsr_render_features",), ()),
+    "features5": ((), ("gsr_render_channels",), ()),
+    "depth": (Z, ("gsr_render_features",), ()),
+    "rgbd": (Z, LISTS + ("gsr_blend", "gsr_blend_features"), ()),
+    "slab": ((), ("gsr_render_slab",), ()),
+    "occluded": (("gsr_sh_to_rgb",), ("gsr_render_slab",), ()),
+    "pick": ((), ("gsr_render_pick",), ()),
+    "median_depth": ((), ("gsr_render_pick",), Z),
+    "topk": ((), ("gsr_render_topk",), ()),
+    "gradient": ((), ("gsr_render_channels_backward",), ()),
+    "weights": ((), ("gsr_render_channels_backward",), ()),
+    "view_stats": ((), ("gsr_render_gaussian_stats",), ()),
+    "gradient_out": ((), LISTS, ("gsr_blend_channels_backward",)),
+    "weights_out": ((), LISTS, ("gsr_blend_channels_backward",)),
+    "view_stats_out": ((), LISTS, ("gsr_blend_gaussian_stats",)),
+}
+ATOMIC = {"gradient": (0,), "weights": (0,), "view_stats": (0,)}  # outputs that are float atomic sums, by position in the result
+
+
+class _Recorder:
+    """renderer.lib with a note of every call: (entry name, the fields of the GsrOptions it was passed by reference, or None)."""
+
+    def __init__(self, real, options_type):
+        self._real, self._options_type, self.calls = real, options_type, []
+
+    def __getattr__(self, name):
+        fn = getattr(self._real, name)
+
+        def call(*args):
+            opts = [a._obj for a in args if isinstance(getattr(a, "_obj", None), self._options_type)]
+            self.calls.append((name, {k: getattr(opts[0], k) for k, _ in self._options_type._fields_} if opts else None))
+            return fn(*args)
+
+        return call
+
+    def names(self):
+        return tuple(name for name, _ in self.calls)
+
+    def options_before_the_first_check(self):
+        names = self.names()
+        head = self.calls[:names.index("gsr_read_stats")] if "gsr_read_stats" in names else self.calls
+        return [o for _, o in head if o is not None]
+
+
+@pytest.fixture(scope="module")
+def S():
+    from gsr_amd import renderer
+
+    class NS:
+        pass
+
+    s = NS()
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    packed, args = _deep_tile_scene()
+    s.renderer, s.cam = renderer, renderer.make_camera(*args)
+    s.scene = renderer.GaussianScene.from_packed(packed)
+    s.R = renderer.Rasterizer(s.scene)
+    s.R.render(s.cam)
+    gen = torch.Generator().manual_seed(23)
+    s.F = torch.randn((s.scene.n, 5), generator=gen).cuda()
+    s.G = torch.randn((s.cam.height, s.cam.width, 5), generator=gen).cuda()
+    s.roomy = {}
+    return s
+
+
+@pytest.fixture
+def rec(S, monkeypatch):
+    r = _Recorder(S.renderer.lib, S.renderer.GsrOptions)
+    monkeypatch.setattr(S.renderer, "lib", r)
+    return r
+
+
+def _rows(S, o):
+    """Pixel rows of the maps a call with options `o` lays out (a strip: its tile rows)."""
+    return S.renderer.shard_rows(S.cam.height, o.tile_row_begin, o.tile_row_step, o.tile_row_block) * 16 if o.output_layout == 2 else S.cam.height
+
+
+def _flat(res):
+    return [t for t in (res if isinstance(res, tuple) else (res,)) if t is not None]
+
+
+def _run(S, R, name, o, outs=None):
+    """One public call by its CALLS name -> the list of tensors it returns.  `outs`: the buffers of an accumulating call."""
+    cam, rows, VS = S.cam, _rows(S, o), S.renderer.ViewStats
+    plane = lambda v: torch.full((rows, cam.width), v, dtype=torch.float32, device="cuda")
+    if name.endswith("_out") and outs is None:
+        outs = _zero_outs(S, name)
+    call = {
+        "render": lambda: R.render(cam, o, return_T=True),
+        "features2": lambda: R.render_features(cam, S.F[:, :2], o, return_T=True),
+        "features5": lambda: R.render_features(cam, S.F, o, return_T=True),
+        "depth": lambda: R.render_depth(cam, o),
+        "rgbd": lambda: R.render_rgbd(cam, o),
+        "slab": lambda: R.render_slab(cam, S.F, plane(1.2), plane(2.6), o),
+        "occluded": lambda: R.render_occluded(cam, plane(2.2), opts=o),
+        "pick": lambda: R.render_pick(cam, o, count=True),
+        "median_depth": lambda: R.render_median_depth(cam, o),
+        "topk": lambda: R.render_topk(cam, 4, o, return_T=True),
+        "gradient": lambda: R.feature_gradient(cam, S.G[:rows], o, scene_order=True),
+        "weights": lambda: R.blend_weights(cam, o),
+        "view_stats": lambda: R.view_stats(cam, o, scene_order=True),
+        "gradient_out": lambda: R.feature_gradient(cam, S.G[:rows], o, out=outs[0]),
+        "weights_out": lambda: R.blend_weights(cam, o, out=outs[0]),
+        "view_stats_out": lambda: R.view_stats(cam, o, out=VS(*outs)),
+    }[name]
+    return _flat(call())
+
+
+def _zero_outs(S, name):
+    n = S.scene.n
+    if name == "gradient_out":
+        return [torch.zeros((n, 5), device="cuda")]
+    if name == "weights_out":
+        return [torch.zeros(n, device="cuda")]
+    return [torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda")]
+
+
+def _sequence(name, attempts):
+    pre, attempt, post = CALLS[name]
+    return pre + (attempt + STATS) * attempts + post
+
+
+def _check_closing_blend(rec, name):
+    """An accumulating call's blend runs once, after the last check, with colour_stage = 0 and the depth-sort bound its lists got."""
+    (blend, bo), (sort, so) = rec.calls[-1], rec.calls[-3]
+    assert blend == CALLS[name][2][0] and sort == "gsr_bin_sort", rec.names()
+    assert bo["colour_stage"] == 0 and bo["depth_sort_passes"] == so["depth_sort_passes"], (name, bo, so)
+
+
+@pytest.mark.parametrize("name", list(CALLS))
+def test_entries_and_chaining(S, rec, name):
+    R, mk = S.R, S.renderer.make_options
+    assert R.unchecked.slices == 0
+    # a. nothing unchecked: the sequence, and no struct asks to keep a record.  The accumulating calls get colour_stage = 1 from the
+    #    caller, which their lists and their blend must not run with.
+    _run(S, R, name, mk(colour_stage=1) if name.endswith("_out") else mk())
+    assert rec.names() == _sequence(name, 1), name
+    assert rec.options_before_the_first_check() and all(o["keep_flags"] == 0 for o in rec.options_before_the_first_check()), name
+    assert R.sort_passes > 0 and all(o["depth_sort_passes"] == R.sort_passes for o in rec.options_before_the_first_check()), name
+    if name.endswith("_out"):
+        _check_closing_blend(rec, name)
+    # b. one frame enqueued and not read: the call adds to its record
+    R.enqueue(S.cam)
+    assert R.unchecked.slices == 1
+    del rec.calls[:]
+    _run(S, R, name, mk())
+    assert rec.names() == _sequence(name, 1), name
+    assert rec.options_before_the_first_check() and all(o["keep_flags"] == 1 for o in rec.options_before_the_first_check()), name
+    assert R.unchecked.slices == 0
+    # a shard without tile rows (two tile rows, the third of three shards): no render, list or blend entry is called
+    del rec.calls[:]
+    outs = [torch.full_like(t, 3) for t in _zero_outs(S, name)] if name.endswith("_out") else None
+    res = _run(S, R, name, mk(tile_row_begin=2, tile_row_step=3, output_layout=2), outs)
+    assert not [c for c in rec.names() if c.startswith(("gsr_render_", "gsr_blend")) or c in LISTS], (name, rec.names())
+    if outs is not None:
+        assert all(bool((t == 3).all()) for t in outs)
+    else:
+        assert all(not t.any() if name in ATOMIC else t.numel() == 0 for t in res), name  # per-gaussian results: zeros; maps: no rows
+    R.stats()
+
+
+def _roomy(S, name):
+    """What the roomy rasterizer returns for the call (scene order), computed once."""
+    base = name[:-4] if name.endswith("_out") else name
+    if base not in S.roomy:
+        S.roomy[base] = _run(S, S.R, base, S.renderer.make_options())
+    return S.roomy[base]
+
+
+@pytest.mark.parametrize("name", list(CALLS))
+def test_an_overflowed_attempt_is_run_again_and_leaves_no_trace(S, rec, name):
+    ref = _roomy(S, name)
+    del rec.calls[:]
+    small = S.renderer.Rasterizer(S.scene, max_pairs=64)
+    if not name.endswith("_out"):
+        got = _run(S, small, name, S.renderer.make_options())
+        assert rec.names() == _sequence(name, 2), (name, rec.names())
+        assert small.max_pairs > 64
+        assert len(got) == len(ref)
+        for k, (g, r) in enumerate(zip(got, ref)):
+            if k in ATOMIC.get(name, ()):
+                _bar(f"{name}[{k}] after a retry", g.cpu().numpy(), r.cpu().numpy())
+            else:
+                assert g.dtype == r.dtype and torch.equal(g, r), (name, k)
+        return
+    # accumulating: `before` + one view.  Sums start from the view's own value (so the bar is taken at twice it), the maximum from
+    # the median of the view's positive maxima (gaussians on either side of it), the pixel counts from 7.
+    if name == "weights_out":  # blend_weights without `out` answers in file order, `out` is in the scene's
+        o_t = S.scene.order_t
+        ref = ref if o_t is None else [ref[0].index_select(0, o_t)]
+    outs = [ref[0].clone()]
+    if name == "view_stats_out":
+        mid = float(ref[1][ref[1] > 0].median())
+        outs += [torch.full_like(ref[1], mid), torch.full_like(ref[2], 7)]
+    got = _run(S, small, name, S.renderer.make_options(), outs)
+    assert rec.names() == _sequence(name, 2), (name, rec.names())
+    assert small.max_pairs > 64
+    _check_closing_blend(rec, name)
+    assert all(g is o for g, o in zip(got, outs))
+    _bar(f"{name} sum after a retry", outs[0].cpu().numpy(), 2.0 * ref[0].double().cpu().numpy())
+    if name == "view_stats_out":
+        assert bool((ref[1] > mid).any()) and bool(((ref[1] > 0) & (ref[1] < mid)).any())
+        assert torch.equal(outs[1], torch.clamp(ref[1], min=mid)) and torch.equal(outs[2], ref[2] + 7)

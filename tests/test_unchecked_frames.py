@@ -51,3 +51,25 @@ def test_an_empty_shard_leaves_the_frames_before_it_to_be_read():
     assert u.empty and u.read() == 0                             # and nothing more: the shard's own counters are zeros
     u.wrote(1)
     assert not u.empty and list(u.to_reset(1)) == [] and u.read() == 1
+
+
+def test_a_single_view_chains_onto_unchecked_frames_with_a_copy_of_the_options():
+    """Rasterizer._chained, the one statement of the rule every single-view call follows: the caller's options as they are while
+    slice 0 holds nothing unchecked or the flag is set already, else a copy with keep_flags = 1 — never a write to the caller's."""
+    from gsr_amd.renderer import Rasterizer, UncheckedFrames, make_options
+
+    R = Rasterizer.__new__(Rasterizer)
+    R.unchecked = UncheckedFrames()
+    plain, kept = make_options(depth_sort_passes=3), make_options(keep_flags=True)
+    assert R._chained(plain) is plain and R._chained(kept) is kept      # nothing unchecked
+    R.unchecked.wrote(0)                                                # an empty shard leaves nothing to chain onto
+    assert R._chained(plain) is plain
+    R.unchecked.wrote(1)
+    o = R._chained(plain)
+    assert o is not plain and o.keep_flags == 1 and plain.keep_flags == 0
+    assert bytes(o) != bytes(plain)
+    o.keep_flags = 0
+    assert bytes(o) == bytes(plain)                                      # every other field is the caller's
+    assert R._chained(kept) is kept                                      # the flag is set already
+    R.unchecked.read()
+    assert R._chained(plain) is plain                                    # stats() has read the record

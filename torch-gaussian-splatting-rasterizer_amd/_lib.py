@@ -155,33 +155,27 @@ def _load() -> C.CDLL:
     L.gsr_default_options.restype = None
     L.gsr_camera_setup.argtypes = [dp, dp, C.c_double, C.c_double, i64, i64, i32, i32, C.POINTER(GsrCamera)]
     L.gsr_workspace_bytes.argtypes = [i64, i32, i32, i64, C.POINTER(sz)]
-    L.gsr_preprocess.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), vp, sz,
-                                 C.POINTER(GsrDebugOut), vp]
-    L.gsr_bin_sort.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp]
-    L.gsr_blend.argtypes = [C.POINTER(GsrScene), i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
-    L.gsr_blend_features.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp]
-    L.gsr_render_features.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp]
-    L.gsr_blend_channels.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp]
-    L.gsr_render_channels.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp]
-    L.gsr_blend_channels_backward.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, vp, i64, vp]
-    L.gsr_render_channels_backward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, vp, i64, vp]
-    L.gsr_blend_pick.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, C.c_float, vp, vp, vp, vp, vp]
-    L.gsr_render_pick.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, C.c_float, vp, vp, vp, vp, vp]
-    L.gsr_blend_topk.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, i32, i32, vp, vp, vp, vp]
-    L.gsr_render_topk.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, i32, i32, vp, vp, vp, vp]
-    L.gsr_blend_slab.argtypes = [C.POINTER(GsrScene), i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp, vp, vp]
-    L.gsr_render_slab.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, i32, i64, vp, vp, vp, vp, vp]
-    L.gsr_blend_gaussian_stats.argtypes = [i64, C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp, vp]
-    L.gsr_render_gaussian_stats.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp, vp, vp]
-    L.gsr_render_forward.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), i64, vp, sz, vp, vp, vp]
-    L.gsr_render_batch.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, vp, sz, vp, i64, vp]
-    L.gsr_render_batch_slots.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), i32, C.POINTER(GsrOptions), i64, C.POINTER(vp), sz,
-                                         C.POINTER(vp), i32, vp, i64]
+    scene_p, cam_p, opts_p = C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions)
+    lists = [i64, cam_p, opts_p, i64, vp, sz]        # gsr_bin_sort / gsr_blend_*: n, camera, options, max_pairs, workspace, its bytes
+    view = [scene_p, cam_p, opts_p, i64, vp, sz]     # gsr_render_*: the scene in n's place
+    L.gsr_preprocess.argtypes = [scene_p, cam_p, opts_p, vp, sz, C.POINTER(GsrDebugOut), vp]
+    L.gsr_bin_sort.argtypes = lists + [vp]
+    L.gsr_blend.argtypes = [scene_p] + lists + [vp, vp, vp]
+    L.gsr_render_forward.argtypes = view + [vp, vp, vp]
+    L.gsr_blend_slab.argtypes = [scene_p] + lists + [vp, i32, i64, vp, vp, vp, vp, vp]
+    L.gsr_render_slab.argtypes = view + [vp, i32, i64, vp, vp, vp, vp, vp]
+    for name, tail in (("features", [vp, vp, vp, vp]), ("channels", [vp, i32, i64, vp, vp, vp]),
+                       ("channels_backward", [vp, i32, vp, i64, vp]), ("pick", [C.c_float, vp, vp, vp, vp, vp]),
+                       ("topk", [i32, i32, vp, vp, vp, vp]), ("gaussian_stats", [vp, vp, vp, vp, vp])):
+        getattr(L, "gsr_blend_" + name).argtypes = lists + tail   # the blend alone, over lists already made ...
+        getattr(L, "gsr_render_" + name).argtypes = view + tail   # ... and stages 1-3 in one call: the same tail
+    L.gsr_render_batch.argtypes = [scene_p, cam_p, i32, opts_p, i64, vp, sz, vp, i64, vp]
+    L.gsr_render_batch_slots.argtypes = [scene_p, cam_p, i32, opts_p, i64, C.POINTER(vp), sz, C.POINTER(vp), i32, vp, i64]
     L.gsr_read_stats.argtypes = [vp, sz, C.POINTER(GsrStats), vp]
     L.gsr_scene_order_bytes.argtypes = [i64, C.POINTER(sz)]
     L.gsr_scene_order.argtypes = [i64, vp, vp, vp, sz, vp]
     L.gsr_scene_bounds.argtypes = [i64, vp, vp, vp, vp]
-    L.gsr_block_visibility.argtypes = [C.POINTER(GsrScene), C.POINTER(GsrCamera), C.POINTER(GsrOptions), vp, vp]
+    L.gsr_block_visibility.argtypes = [scene_p, cam_p, opts_p, vp, vp]
     L.gsr_sh_to_rgb.argtypes = [i64, vp, vp, C.POINTER(C.c_float), i32, vp, vp]
     L.gsr_cov3d.argtypes = [i64, vp, vp, vp, vp]
     f16 = C.POINTER(C.c_float)

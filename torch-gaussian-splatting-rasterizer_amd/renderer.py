@@ -498,6 +498,66 @@ class Rasterizer:
         o.depth_sort_passes = self.sort_passes
         return o
 
+    # -- the host skeleton of every single-view call ---------------------------
+    def _new(self, opts: GsrOptions, shape, dtype=torch.float32, fill=None) -> torch.Tensor:
+        """An output of a single-view call.  fill=None: a map the blend stores whole, except that strips (output_layout == 2) may
+        hold rows below the frame's last pixel row, which are kept defined (0).  Else the value that reads "nothing drawn" (0; -1 for
+        an id; 1 for T), everywhere."""
+        if fill is None:
+            return (torch.zeros if opts.output_layout == 2 else torch.empty)(shape, dtype=dtype, device=self.scene.device)
+        return torch.full(shape, fill, dtype=dtype, device=self.scene.device)
+
+    def _chained(self, opts: GsrOptions) -> GsrOptions:
+        """Slice 0 holds unchecked frames: a single view adds to their record (keep_flags; a copy, the caller's struct is never
+        written).  enqueue_batch has a rule of its own (to_reset), FramesInFlight.render_batch clears the flag on purpose."""
+        if not self.unchecked.slices or opts.keep_flags:
+            return opts
+        o = GsrOptions.from_buffer_copy(opts)
+        o.keep_flags = 1
+        return o
+
+    def _enqueue_view(self, cam: GsrCamera, opts: GsrOptions, entry, result: Optional[torch.Tensor], *args) -> Optional[GsrOptions]:
+        """One gsr_render_* entry (all share the prefix scene, cam, opts, max_pairs, workspace; `args` lie between it and the stream)
+        into slice 0 on the current stream, unchecked like enqueue().  The workspace comes first: one of a new size resets
+        `unchecked`.  A `result` without elements is a shard that owns no tile row (more ranks than tile rows): nothing is called
+        and None returned; else the options the entry ran with."""
+        ws = self._workspace(cam.width, cam.height)
+        if result is not None and result.numel() == 0:
+            self.unchecked.wrote(0)
+            return None
+        opts, sc = self._chained(opts), self.scene.c_struct()
+        check(entry(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), *args, _stream_ptr(self.scene.device)))
+        self.unchecked.wrote(1)
+        return opts
+
+    def _stages_1_2(self, sc, cam, opts, max_pairs, ws, ws_bytes, stream) -> int:
+        """gsr_preprocess then gsr_bin_sort, with the parameters and the status of a gsr_render_* entry."""
+        return lib.gsr_preprocess(sc, cam, opts, ws, ws_bytes, None, stream) or \
+            lib.gsr_bin_sort(self.scene.n, cam, opts, max_pairs, ws, ws_bytes, stream)
+
+    def _enqueue_lists(self, cam: GsrCamera, opts: GsrOptions, result: Optional[torch.Tensor] = None) -> Optional[GsrOptions]:
+        """Stages 1-2 alone, as _enqueue_view enqueues a whole view: the tile lists the gsr_blend_* entries walk (_blend_lists) with
+        the options returned here."""
+        return self._enqueue_view(cam, opts, self._stages_1_2, result)
+
+    def _blend_lists(self, cam: GsrCamera, opts: GsrOptions, entry, *args) -> None:
+        """One gsr_blend_* entry (prefix n, cam, opts, max_pairs, workspace) over the lists in slice 0.  The workspace is asked for
+        again: _render_checked may have grown max_pairs since the caller last saw it."""
+        ws = self._workspace(cam.width, cam.height)
+        check(entry(self.scene.n, C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), *args, _stream_ptr(self.scene.device)))
+
+    def _checked_lists(self, cam: GsrCamera, opts: GsrOptions, what: str) -> GsrOptions:
+        """The first phase of a call that ACCUMULATES into the caller's buffers.  An incomplete walk must never reach them — what it
+        added could not be taken back — so stages 1-2 are enqueued, checked and re-run until they are complete (_render_checked), with
+        colour_stage = 0 as the gsr_render_* entries of these blends set it; only then does the caller's gsr_blend_* add, once, with
+        the options returned here."""
+        def attempt(o):
+            o = GsrOptions.from_buffer_copy(o)
+            o.colour_stage = 0
+            return self._enqueue_lists(cam, o)
+
+        return _render_checked([self], [None], opts, attempt, 8, what)
+
     # -- one frame ------------------------------------------------------------------------------
     def enqueue(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None,
                 final_T: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -505,26 +565,13 @@ class Rasterizer:
         caller's bounds (max_pairs; opts.depth_sort_passes if set).  The frames enqueued since the last stats() are chained
         with GsrOptions.keep_flags, so the next stats() / render() reports a bound exceeded by ANY of them, not only the last."""
         opts = opts or make_options()
-        ws = self._workspace(cam.width, cam.height)
         shape, _ = self._out_shape(cam, opts)
         dtype = torch.bfloat16 if opts.output_dtype == 1 else torch.float32
         if out is None:
-            # strips may include rows below the frame's last pixel row: keep them defined
-            out = torch.zeros(shape, dtype=dtype, device=self.scene.device) if opts.output_layout == 2 else \
-                torch.empty(shape, dtype=dtype, device=self.scene.device)
+            out = self._new(opts, shape, dtype)
         elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or not out.is_cuda:
             raise ValueError(f"out must be a contiguous {dtype} CUDA tensor of shape {shape}")
-        if out.numel() == 0:  # a shard that owns no tile row (more ranks than tile rows): nothing to render
-            self.unchecked.wrote(0)
-            return out
-        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
-            opts = GsrOptions.from_buffer_copy(opts)
-            opts.keep_flags = 1
-        sc = self.scene.c_struct()
-        tptr = final_T.data_ptr() if final_T is not None else None
-        check(lib.gsr_render_forward(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(),
-                                     out.data_ptr(), tptr, _stream_ptr(self.scene.device)))
-        self.unchecked.wrote(1)
+        self._enqueue_view(cam, opts, lib.gsr_render_forward, out, out.data_ptr(), final_T.data_ptr() if final_T is not None else None)
         return out
 
     def stats(self) -> Dict[str, int]:
@@ -562,24 +609,28 @@ class Rasterizer:
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "frame")
 
     # -- feature, depth and alpha maps -----------------------------------------------------------------
-    def _feature_groups(self, features: torch.Tensor, scene_order: bool):
-        """[n, C] caller values -> ceil(C / 3) contiguous [n, 3] float32 arrays in the scene's order (the last zero-padded)."""
+    def _check_features(self, features: torch.Tensor, max_channels: Optional[int] = None) -> None:
         _require_cuda(features, "features")
         if features.dim() != 2 or features.shape[0] != self.scene.n or features.shape[1] < 1 or features.dtype != torch.float32:
             raise ValueError(f"features must be a float32 tensor of shape [{self.scene.n}, C >= 1], got {features.dtype} {tuple(features.shape)}")
         if features.device != self.scene.device:
             raise ValueError("features must live on the scene's device")
+        if max_channels is not None and features.shape[1] > max_channels:
+            raise ValueError(f"at most {max_channels} channels per call, got {features.shape[1]}")
+
+    def _feature_triple(self, features: torch.Tensor, scene_order: bool) -> torch.Tensor:
+        """[n, C <= 3] caller values -> one contiguous [n, 3] float32 array in the scene's order, zero-padded: what the three-channel
+        blend reads (wider maps go through _feature_rows and gsr_render_channels, WIDE_BLEND_ABOVE)."""
+        self._check_features(features)
+        n, n_ch = self.scene.n, int(features.shape[1])
+        assert n_ch <= 3
+        if n == 0:  # an empty tensor has no address; libgsr refuses a null array
+            return torch.zeros((1, 3), dtype=torch.float32, device=self.scene.device)
         if not scene_order and self.scene.order_t is not None:
             features = features.index_select(0, self.scene.order_t)
-        groups = []
-        for c0 in range(0, features.shape[1], 3):
-            g = features[:, c0:c0 + 3]
-            if g.shape[1] < 3:
-                g = torch.cat([g, torch.zeros((self.scene.n, 3 - g.shape[1]), dtype=torch.float32, device=self.scene.device)], 1)
-            if self.scene.n == 0:  # an empty tensor has no address; libgsr refuses a null array
-                g = torch.zeros((1, 3), dtype=torch.float32, device=self.scene.device)
-            groups.append(g.contiguous())
-        return groups
+        if n_ch < 3:
+            features = torch.cat([features, torch.zeros((n, 3 - n_ch), dtype=torch.float32, device=self.scene.device)], 1)
+        return features.contiguous()
 
     def _depth_features(self, cam: GsrCamera) -> torch.Tensor:
         """[n, 3] = (z_cam, 1, 0) in the scene's order; z_cam = column 2 of gsr_project_to_camera_space for the camera's w2c."""
@@ -592,53 +643,35 @@ class Rasterizer:
             f[:, 1] = 1.0
         return f
 
-    def _enqueue_maps(self, cam: GsrCamera, opts: GsrOptions, groups, want_T: bool, with_image: bool):
-        """One preprocess and one bin / sort, then (with_image) the colour blend and one feature blend per group of three channels,
-        on the current stream, unchecked like enqueue().  Returns (image or None, [maps], T or None)."""
-        ws = self._workspace(cam.width, cam.height)
+    def _enqueue_maps(self, cam: GsrCamera, opts: GsrOptions, triple: torch.Tensor, want_T: bool):
+        """One preprocess, one bin / sort and the three-channel feature blend (gsr_render_features) on the current stream, unchecked
+        like enqueue().  Returns (map, T or None)."""
         shape, tshape = self._out_shape(cam, opts)
-        dev = self.scene.device
-        new = torch.zeros if opts.output_layout == 2 else torch.empty  # strips may include rows below the frame's last pixel row
-        maps = [new(shape, dtype=torch.float32, device=dev) for _ in groups]
-        T = torch.ones(tshape, dtype=torch.float32, device=dev) if want_T else None
-        img = new(shape, dtype=torch.bfloat16 if opts.output_dtype == 1 else torch.float32, device=dev) if with_image else None
-        if maps[0].numel() == 0:  # a shard that owns no tile row
-            self.unchecked.wrote(0)
-            return img, maps, T
-        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
-            opts = GsrOptions.from_buffer_copy(opts)
-            opts.keep_flags = 1
-        sc, sp = self.scene.c_struct(), _stream_ptr(dev)
-        n, mp, wp, wn = self.scene.n, self.max_pairs, ws.data_ptr(), ws.numel()
-        tptr = T.data_ptr() if want_T else None
-        rest = groups
-        if with_image:
-            fo = GsrOptions.from_buffer_copy(opts)  # the maps are float32 whatever the frame is stored as
+        out = self._new(opts, shape)
+        T = self._new(opts, tshape, fill=1) if want_T else None
+        self._enqueue_view(cam, opts, lib.gsr_render_features, out, triple.data_ptr(), out.data_ptr(), T.data_ptr() if want_T else None)
+        return out, T
+
+    def _enqueue_rgbd(self, cam: GsrCamera, opts: GsrOptions, triple: torch.Tensor):
+        """One preprocess and one bin / sort, then the colour blend with the caller's options (the frame may be bf16) and one feature
+        blend over the same lists, on the current stream, unchecked like enqueue().  Returns (image, map)."""
+        shape, _ = self._out_shape(cam, opts)
+        img = self._new(opts, shape, torch.bfloat16 if opts.output_dtype == 1 else torch.float32)
+        out = self._new(opts, shape)
+        opts = self._enqueue_lists(cam, opts, out)
+        if opts is not None:
+            sc = self.scene.c_struct()
+            fo = GsrOptions.from_buffer_copy(opts)  # the map is float32 whatever the frame is stored as
             fo.output_dtype = 0
-            check(lib.gsr_preprocess(C.byref(sc), C.byref(cam), C.byref(opts), wp, wn, None, sp))
-            check(lib.gsr_bin_sort(n, C.byref(cam), C.byref(opts), mp, wp, wn, sp))
-            check(lib.gsr_blend(C.byref(sc), n, C.byref(cam), C.byref(opts), mp, wp, wn, img.data_ptr(), None, sp))
-            opts = fo
-        else:
-            check(lib.gsr_render_features(C.byref(sc), C.byref(cam), C.byref(opts), mp, wp, wn, groups[0].data_ptr(), maps[0].data_ptr(), tptr, sp))
-            rest, tptr = groups[1:], None
-        for g, m in zip(rest, maps[len(maps) - len(rest):]):
-            check(lib.gsr_blend_features(n, C.byref(cam), C.byref(opts), mp, wp, wn, g.data_ptr(), m.data_ptr(), tptr, sp))
-            tptr = None  # every group ends with the same T: one store is enough
-        self.unchecked.wrote(1)
-        return img, maps, T
+            self._blend_lists(cam, opts, lambda *a: lib.gsr_blend(C.byref(sc), *a), img.data_ptr(), None)
+            self._blend_lists(cam, fo, lib.gsr_blend_features, triple.data_ptr(), out.data_ptr(), None)
+        return img, out
 
     def _feature_rows(self, features: torch.Tensor, scene_order: bool) -> torch.Tensor:
         """[n, C] caller values -> a float32 tensor in the scene's order that gsr_render_channels reads where it lies: rows of unit
         element stride, stride(0) >= C apart.  The caller's own tensor (a column window of a wider one included) whenever it already
         is in the scene's order and laid out so; else ONE copy (the gather through scene.order_t, or .contiguous())."""
-        _require_cuda(features, "features")
-        if features.dim() != 2 or features.shape[0] != self.scene.n or features.shape[1] < 1 or features.dtype != torch.float32:
-            raise ValueError(f"features must be a float32 tensor of shape [{self.scene.n}, C >= 1], got {features.dtype} {tuple(features.shape)}")
-        if features.device != self.scene.device:
-            raise ValueError("features must live on the scene's device")
-        if features.shape[1] > _lib.GSR_MAX_FEATURE_CHANNELS:
-            raise ValueError(f"at most {_lib.GSR_MAX_FEATURE_CHANNELS} channels per call, got {features.shape[1]}")
+        self._check_features(features, _lib.GSR_MAX_FEATURE_CHANNELS)
         if self.scene.n == 0:  # an empty tensor has no address; libgsr refuses a null array
             return torch.zeros((1, features.shape[1]), dtype=torch.float32, device=self.scene.device)
         if not scene_order and self.scene.order_t is not None:
@@ -647,25 +680,19 @@ class Rasterizer:
             return features
         return features.contiguous()
 
-    def _enqueue_channels(self, cam: GsrCamera, opts: GsrOptions, rows: torch.Tensor, want_T: bool):
+    def _enqueue_channels(self, cam: GsrCamera, opts: GsrOptions, rows: torch.Tensor, want_T: bool, limits=None):
         """One preprocess, one bin / sort and one gsr_blend_channels (gsr_render_channels) on the current stream, unchecked like
-        enqueue(): the [.., C] map is written in place, no group copies.  Returns (map, T or None)."""
-        ws = self._workspace(cam.width, cam.height)
+        enqueue(): the [.., C] map is written in place, no group copies.  With limits = (near, far), planes or None, gsr_blend_slab
+        (gsr_render_slab) instead.  Returns (map, T or None)."""
         shape, tshape = self._out_shape(cam, opts)
-        dev, n_ch = self.scene.device, int(rows.shape[1])
-        new = torch.zeros if opts.output_layout == 2 else torch.empty  # strips may include rows below the frame's last pixel row
-        out = new(shape[:2] + (n_ch,), dtype=torch.float32, device=dev)
-        T = torch.ones(tshape, dtype=torch.float32, device=dev) if want_T else None
-        if out.numel() == 0:  # a shard that owns no tile row
-            self.unchecked.wrote(0)
-            return out, T
-        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
-            opts = GsrOptions.from_buffer_copy(opts)
-            opts.keep_flags = 1
-        sc = self.scene.c_struct()
-        check(lib.gsr_render_channels(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), rows.data_ptr(),
-                                      n_ch, int(rows.stride(0)), out.data_ptr(), T.data_ptr() if want_T else None, _stream_ptr(dev)))
-        self.unchecked.wrote(1)
+        n_ch = int(rows.shape[1])
+        out = self._new(opts, shape[:2] + (n_ch,))
+        T = self._new(opts, tshape, fill=1) if want_T else None
+        entry, planes = lib.gsr_render_channels, ()
+        if limits is not None:
+            entry, planes = lib.gsr_render_slab, tuple(p.data_ptr() if p is not None else None for p in limits)
+        self._enqueue_view(cam, opts, entry, out, rows.data_ptr(), n_ch, int(rows.stride(0)), *planes, out.data_ptr(),
+                           T.data_ptr() if want_T else None)
         return out, T
 
     def render_features(self, cam: GsrCamera, features: torch.Tensor, opts: Optional[GsrOptions] = None, return_T: bool = False,
@@ -694,13 +721,12 @@ class Rasterizer:
                 return (out, T) if return_T else out
 
             return _render_checked([self], [None], opts or make_options(), attempt_wide, 8, "feature map")
-        groups = self._feature_groups(features, scene_order)
+        triple = self._feature_triple(features, scene_order)
         n_ch = int(features.shape[1])
 
         def attempt(o):
-            _, maps, T = self._enqueue_maps(cam, o, groups, return_T, False)
-            out = maps[0] if len(maps) == 1 else torch.cat(maps, -1)
-            out = out if out.shape[-1] == n_ch else out[..., :n_ch].contiguous()
+            out, T = self._enqueue_maps(cam, o, triple, return_T)
+            out = out if n_ch == 3 else out[..., :n_ch].contiguous()
             return (out, T) if return_T else out
 
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "feature map")
@@ -729,46 +755,21 @@ class Rasterizer:
             if tuple(out.shape) != (n, n_ch) or out.dtype != torch.float32 or out.device != dev or (
                     n and (out.stride(1) != 1 or out.stride(0) < n_ch)):
                 raise ValueError(f"out must be a float32 tensor of shape [{n}, {n_ch}] on the scene's device with unit element stride")
-        if n == 0 or gm.numel() == 0:  # nothing to draw, or a shard that owns no tile row: the gradient is zero
+        # nothing to draw, or a shard that owns no tile row: the gradient is zero.  Here and in view_stats no workspace is made for
+        # that and the shard leaves no mark in `unchecked`, unlike the map calls (_enqueue_view).
+        if n == 0 or gm.numel() == 0:
             return out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
-        ws_args = lambda: (self._workspace(cam.width, cam.height).data_ptr(), self._ws.numel())
-        sp = _stream_ptr(dev)
-
-        def chained(o):  # slice 0 holds unchecked frames: add to their record
-            if self.unchecked.slices and not o.keep_flags:
-                o = GsrOptions.from_buffer_copy(o)
-                o.keep_flags = 1
-            return o
-
         if out is None:
             buf = torch.empty((n, n_ch), dtype=torch.float32, device=dev)
 
             def attempt(o):  # a re-run after an overflow starts from zero again
-                o, sc = chained(o), self.scene.c_struct()
-                wp, wn = ws_args()
                 buf.zero_()
-                check(lib.gsr_render_channels_backward(C.byref(sc), C.byref(cam), C.byref(o), self.max_pairs, wp, wn, gm.data_ptr(), n_ch,
-                                                       buf.data_ptr(), n_ch, sp))
-                self.unchecked.wrote(1)
-                return buf
+                self._enqueue_view(cam, o, lib.gsr_render_channels_backward, buf, gm.data_ptr(), n_ch, buf.data_ptr(), n_ch)
 
             _render_checked([self], [None], opts, attempt, 8, "feature gradient")
             return buf if scene_order else file_order_gradient(buf, self.scene.order_t)
-
-        # Accumulating: an incomplete walk must not reach `out`, so stages 1-2 are checked (and re-run) first, then the blend adds
-        def attempt_lists(o):
-            o, sc = GsrOptions.from_buffer_copy(chained(o)), self.scene.c_struct()
-            o.colour_stage = 0  # as gsr_render_channels_backward
-            wp, wn = ws_args()
-            check(lib.gsr_preprocess(C.byref(sc), C.byref(cam), C.byref(o), wp, wn, None, sp))
-            check(lib.gsr_bin_sort(n, C.byref(cam), C.byref(o), self.max_pairs, wp, wn, sp))
-            self.unchecked.wrote(1)
-            return o
-
-        o = _render_checked([self], [None], opts, attempt_lists, 8, "feature gradient")
-        wp, wn = ws_args()
-        check(lib.gsr_blend_channels_backward(n, C.byref(cam), C.byref(o), self.max_pairs, wp, wn, gm.data_ptr(), n_ch, out.data_ptr(),
-                                              int(out.stride(0)), sp))
+        o = self._checked_lists(cam, opts, "feature gradient")
+        self._blend_lists(cam, o, lib.gsr_blend_channels_backward, gm.data_ptr(), n_ch, out.data_ptr(), int(out.stride(0)))
         return out
 
     def blend_weights(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -845,41 +846,18 @@ class Rasterizer:
 
         if n == 0 or 0 in self._out_shape(cam, opts)[1]:  # nothing to draw, or a shard that owns no tile row
             return result()
-        ptrs = [b.data_ptr() if b is not None else None for b in bufs]
-        ws_args = lambda: (self._workspace(cam.width, cam.height).data_ptr(), self._ws.numel())
-
-        def chained(o):  # slice 0 holds unchecked frames: add to their record
-            if self.unchecked.slices and not o.keep_flags:
-                o = GsrOptions.from_buffer_copy(o)
-                o.keep_flags = 1
-            return o
-
+        ptrs = [mptr] + [b.data_ptr() if b is not None else None for b in bufs]
         if not given:
             def attempt(o):  # a re-run after an overflow starts from zero again
-                wp, wn = ws_args()
-                o, sc = chained(o), self.scene.c_struct()
                 for b in bufs:
                     if b is not None:
                         b.zero_()
-                check(lib.gsr_render_gaussian_stats(C.byref(sc), C.byref(cam), C.byref(o), self.max_pairs, wp, wn, mptr, *ptrs, _stream_ptr(dev)))
-                self.unchecked.wrote(1)
+                self._enqueue_view(cam, o, lib.gsr_render_gaussian_stats, None, *ptrs)
 
             _render_checked([self], [None], opts, attempt, 8, "view statistics")
             return result()
-
-        # Accumulating: an incomplete walk must not reach `out`, so stages 1-2 are checked (and re-run) first, then the blend adds
-        def attempt_lists(o):
-            wp, wn = ws_args()
-            o, sc = GsrOptions.from_buffer_copy(chained(o)), self.scene.c_struct()
-            o.colour_stage = 0  # as gsr_render_gaussian_stats
-            check(lib.gsr_preprocess(C.byref(sc), C.byref(cam), C.byref(o), wp, wn, None, _stream_ptr(dev)))
-            check(lib.gsr_bin_sort(n, C.byref(cam), C.byref(o), self.max_pairs, wp, wn, _stream_ptr(dev)))
-            self.unchecked.wrote(1)
-            return o
-
-        o = _render_checked([self], [None], opts, attempt_lists, 8, "view statistics")
-        wp, wn = ws_args()
-        check(lib.gsr_blend_gaussian_stats(n, C.byref(cam), C.byref(o), self.max_pairs, wp, wn, mptr, *ptrs, _stream_ptr(dev)))
+        o = self._checked_lists(cam, opts, "view statistics")
+        self._blend_lists(cam, o, lib.gsr_blend_gaussian_stats, *ptrs)
         return result()
 
     def visible_ids(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -900,11 +878,11 @@ class Rasterizer:
     def render_rgbd(self, cam: GsrCamera, opts: Optional[GsrOptions] = None):
         """(image, depth, alpha): render()'s frame, bit for bit, and render_depth()'s maps from ONE preprocess and ONE bin / sort — the
         colour blend and the feature blend run on the same lists."""
-        groups = self._feature_groups(self._depth_features(cam), True)
+        triple = self._feature_triple(self._depth_features(cam), True)
 
         def attempt(o):
-            img, maps, _ = self._enqueue_maps(cam, o, groups, False, True)
-            return img, maps[0][..., 0].contiguous(), maps[0][..., 1].contiguous()
+            img, m = self._enqueue_rgbd(cam, o, triple)
+            return img, m[..., 0].contiguous(), m[..., 1].contiguous()
 
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "frame")
 
@@ -919,29 +897,6 @@ class Rasterizer:
         if plane.device != self.scene.device:
             raise ValueError(f"{name} must live on the scene's device ({self.scene.device}), got {plane.device}")
         return plane.detach().contiguous()
-
-    def _enqueue_slab(self, cam: GsrCamera, opts: GsrOptions, rows: torch.Tensor, near, far, want_T: bool):
-        """One preprocess, one bin / sort and one gsr_blend_slab (gsr_render_slab) on the current stream, unchecked like enqueue().
-        Returns (map, T or None)."""
-        ws = self._workspace(cam.width, cam.height)
-        shape, tshape = self._out_shape(cam, opts)
-        dev, n_ch = self.scene.device, int(rows.shape[1])
-        new = torch.zeros if opts.output_layout == 2 else torch.empty  # strips may include rows below the frame's last pixel row
-        out = new(shape[:2] + (n_ch,), dtype=torch.float32, device=dev)
-        T = torch.ones(tshape, dtype=torch.float32, device=dev) if want_T else None
-        if out.numel() == 0:  # a shard that owns no tile row
-            self.unchecked.wrote(0)
-            return out, T
-        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
-            opts = GsrOptions.from_buffer_copy(opts)
-            opts.keep_flags = 1
-        sc = self.scene.c_struct()
-        check(lib.gsr_render_slab(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), rows.data_ptr(),
-                                  n_ch, int(rows.stride(0)), near.data_ptr() if near is not None else None,
-                                  far.data_ptr() if far is not None else None, out.data_ptr(), T.data_ptr() if want_T else None,
-                                  _stream_ptr(dev)))
-        self.unchecked.wrote(1)
-        return out, T
 
     def render_slab(self, cam: GsrCamera, features: torch.Tensor, near: Optional[torch.Tensor] = None, far: Optional[torch.Tensor] = None,
                     opts: Optional[GsrOptions] = None, return_T: bool = True, scene_order: bool = False):
@@ -963,7 +918,7 @@ class Rasterizer:
         rows = self._feature_rows(features, scene_order)
 
         def attempt(o):
-            out, T = self._enqueue_slab(cam, o, rows, near, far, return_T)
+            out, T = self._enqueue_channels(cam, o, rows, return_T, (near, far))
             return (out, T) if return_T else out
 
         return _render_checked([self], [None], opts, attempt, 8, "slab map")
@@ -994,25 +949,11 @@ class Rasterizer:
     def _enqueue_pick(self, cam: GsrCamera, opts: GsrOptions, median_T: float, count: bool):
         """One preprocess, one bin / sort and one gsr_blend_pick (gsr_render_pick) on the current stream, unchecked like enqueue().
         Returns (best_id, best_w, median_id, count or None) with the ids as the kernel wrote them (the scene's order)."""
-        ws = self._workspace(cam.width, cam.height)
         _, shape = self._out_shape(cam, opts)
-        dev = self.scene.device
-        # strips may include rows below the frame's last pixel row: they read "nothing drawn"
-        best_id = torch.full(shape, -1, dtype=torch.int32, device=dev)
-        best_w = torch.zeros(shape, dtype=torch.float32, device=dev)
-        median_id = torch.full(shape, -1, dtype=torch.int32, device=dev)
-        cnt = torch.zeros(shape, dtype=torch.int32, device=dev) if count else None
-        if best_id.numel() == 0:  # a shard that owns no tile row
-            self.unchecked.wrote(0)
-            return best_id, best_w, median_id, cnt
-        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
-            opts = GsrOptions.from_buffer_copy(opts)
-            opts.keep_flags = 1
-        sc = self.scene.c_struct()
-        check(lib.gsr_render_pick(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), float(median_T),
-                                  best_id.data_ptr(), best_w.data_ptr(), median_id.data_ptr(), cnt.data_ptr() if count else None,
-                                  _stream_ptr(dev)))
-        self.unchecked.wrote(1)
+        best_id, best_w, median_id = self._new(opts, shape, torch.int32, -1), self._new(opts, shape, fill=0), self._new(opts, shape, torch.int32, -1)
+        cnt = self._new(opts, shape, torch.int32, 0) if count else None
+        self._enqueue_view(cam, opts, lib.gsr_render_pick, best_id, float(median_T), best_id.data_ptr(), best_w.data_ptr(),
+                           median_id.data_ptr(), cnt.data_ptr() if count else None)
         return best_id, best_w, median_id, cnt
 
     def render_pick(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, median_T: float = 0.5, count: bool = False,
@@ -1039,23 +980,11 @@ class Rasterizer:
     def _enqueue_topk(self, cam: GsrCamera, opts: GsrOptions, k: int, select: int, return_T: bool):
         """One preprocess, one bin / sort and one gsr_blend_topk (gsr_render_topk) on the current stream, unchecked like enqueue().
         Returns (ids, weights, final_T or None) with the ids as the kernel wrote them (the scene's order)."""
-        ws = self._workspace(cam.width, cam.height)
-        _, shape = self._out_shape(cam, opts)
-        dev = self.scene.device
-        # strips may include rows below the frame's last pixel row: they read "nothing drawn"
-        ids = torch.full(tuple(shape) + (k,), -1, dtype=torch.int32, device=dev)
-        weights = torch.zeros(tuple(shape) + (k,), dtype=torch.float32, device=dev)
-        final_T = torch.ones(shape, dtype=torch.float32, device=dev) if return_T else None
-        if ids.numel() == 0:  # a shard that owns no tile row
-            self.unchecked.wrote(0)
-            return ids, weights, final_T
-        if self.unchecked.slices and not opts.keep_flags:  # slice 0 holds unchecked frames: add to their record
-            opts = GsrOptions.from_buffer_copy(opts)
-            opts.keep_flags = 1
-        sc = self.scene.c_struct()
-        check(lib.gsr_render_topk(C.byref(sc), C.byref(cam), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), k, select,
-                                  ids.data_ptr(), weights.data_ptr(), final_T.data_ptr() if return_T else None, _stream_ptr(dev)))
-        self.unchecked.wrote(1)
+        shape = tuple(self._out_shape(cam, opts)[1])
+        ids, weights = self._new(opts, shape + (k,), torch.int32, -1), self._new(opts, shape + (k,), fill=0)
+        final_T = self._new(opts, shape, fill=1) if return_T else None
+        self._enqueue_view(cam, opts, lib.gsr_render_topk, ids, k, select, ids.data_ptr(), weights.data_ptr(),
+                           final_T.data_ptr() if return_T else None)
         return ids, weights, final_T
 
     def render_topk(self, cam: GsrCamera, k: int, opts: Optional[GsrOptions] = None, select: str = "heaviest", return_T: bool = False,
@@ -1111,7 +1040,7 @@ class Rasterizer:
         dtype = torch.bfloat16 if opts.output_dtype == 1 else torch.float32
         frame = shape[0] * shape[1] * shape[2]
         if out is None:
-            out = (torch.zeros if opts.output_layout == 2 else torch.empty)(full, dtype=dtype, device=self.scene.device)
+            out = self._new(opts, full, dtype)
         elif (tuple(out.shape) != full or out.dtype != dtype or not out.is_cuda or (frame and not out[0].is_contiguous())
               or (len(cams) > 1 and out.stride(0) < frame)):
             # (consecutive frames may lie further apart than a frame: the strips of a padded wire buffer, dist.FrameGather)
@@ -1247,22 +1176,26 @@ class FramesInFlight:
         for r in self.rasterizers:
             r.sort_passes = max(r.sort_passes, int(passes))
 
+    def _take_slot(self, slot: Optional[int]) -> int:
+        """The slot a submit uses: the caller's, else the next one round robin."""
+        if slot is not None:
+            return int(slot)
+        k = self._next
+        self._next = (k + 1) % len(self.rasterizers)
+        return k
+
     def submit(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None,
                slot: Optional[int] = None) -> int:
         """Enqueue one frame on the next slot's stream (round robin) and return the slot.  Unchecked, with `opts` as given
         (Rasterizer.enqueue): stats(slot) afterwards speaks for every frame the slot has rendered since its last stats()."""
-        k = self._next if slot is None else int(slot)
-        if slot is None:
-            self._next = (self._next + 1) % len(self.rasterizers)
+        k = self._take_slot(slot)
         with torch.cuda.stream(self.streams[k]):
             self.rasterizers[k].enqueue(cam, opts, out=out)
         return k
 
     def submit_batch(self, cams, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None, slot: Optional[int] = None) -> int:
         """submit() for several views at once: Rasterizer.enqueue_batch on the next slot's stream (`views` of them per launch sequence)."""
-        k = self._next if slot is None else int(slot)
-        if slot is None:
-            self._next = (self._next + 1) % len(self.rasterizers)
+        k = self._take_slot(slot)
         with torch.cuda.stream(self.streams[k]):
             self.rasterizers[k].enqueue_batch(cams, opts, out=out)
         return k
