@@ -6,19 +6,15 @@ import re
 import numpy as np
 import pytest
 
+import abi_checks as abi
 from conftest import REPO, load_golden
-
-
-def _declared():
-    text = open(os.path.join(REPO, "include", "gsr.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", text)))
+from gpu_cases import golden_args
 
 
 def test_every_declared_symbol_is_exported():
     from gsr_amd import _lib
 
-    names = _declared()
+    names = sorted(abi.declared_names())
     assert len(names) >= 12
     for n in names:
         assert hasattr(_lib.lib, n), f"{n} declared in include/gsr.h but not exported by libgsr.so"
@@ -42,8 +38,7 @@ def test_camera_setup_host_path_matches_oracle_and_reference():
     from oracle import cpu_oracle as orc
 
     g = load_golden("f1_unit.npz")
-    args = (g["qvec"], g["tvec"], float(g["fx_full"]), float(g["fy_full"]), int(g["cam_width"]), int(g["cam_height"]),
-            int(g["width"]), int(g["height"]))
+    args = golden_args(g)
     cam, ocam = _lib.camera_setup(*args), orc.camera(*args)
     assert bytes(cam) == bytes(ocam)
     assert np.array_equal(np.array(cam.w2c, np.float32).reshape(4, 4), g["w2c_T"])
@@ -69,7 +64,7 @@ def test_workspace_query_applies_the_render_entry_points_size_limits():
     n past 2^31 - 1, max_pairs past GSR_MAX_PAIRS — and the limits stated in include/gsr.h are the ones _lib.py carries."""
     from gsr_amd import _lib
 
-    text = open(os.path.join(REPO, "include", "gsr.h")).read()
+    text = abi.header()
     assert re.search(r"#define GSR_MAX_FRAME_SIDE \(65535 \* GSR_TILE\)", text) and "#define GSR_TILE 16 " in text
     assert re.search(r"#define GSR_MAX_GAUSSIANS 0x7FFFFFFFll", text) and re.search(r"#define GSR_MAX_PAIRS 0xFFFFE000ll", text)
     side, n_max, p_max = _lib.GSR_MAX_FRAME_SIDE, _lib.GSR_MAX_GAUSSIANS, _lib.GSR_MAX_PAIRS
@@ -149,7 +144,7 @@ def test_a_library_of_another_abi_version_is_refused(tmp_path):
 
     from gsr_amd import _lib
 
-    text = open(os.path.join(REPO, "include", "gsr.h")).read()
+    text = abi.header()
     assert re.search(r"#define GSR_VERSION (\d+)", text).group(1) == str(_lib.GSR_VERSION)
     src, stub = tmp_path / "stub.c", tmp_path / "libgsr_stub.so"
     src.write_text("int gsr_version(void) { return 500; }\n")

@@ -1,47 +1,32 @@
 """CPU: gsr_blend_channels / gsr_render_channels are additions to ABI 0.6.0 — declared, exported and bound; no struct or version
 moved; their argument checks run before any HIP call."""
 import ctypes as C
-import os
 import re
 
 import pytest
 
-from conftest import REPO
+import abi_checks as abi
 
 NEW = ("gsr_blend_channels", "gsr_render_channels")
-
-
-def _header():
-    return open(os.path.join(REPO, "include", "gsr.h")).read()
 
 
 def test_the_two_symbols_are_declared_exported_and_bound():
     from gsr_amd import _lib
 
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", text))
+    abi.assert_declared_exported_and_bound(NEW, 12)
     for name in NEW:
-        assert name in declared, f"{name} is not declared in include/gsr.h"
-        assert _lib.EXPORTS.count(name) == 1, f"{name} is not (once) in _lib.EXPORTS"
-        fn = getattr(_lib.lib, name)                 # AttributeError: libgsr.so does not export it
-        assert fn.restype is C.c_int and len(fn.argtypes) == 12, name
+        fn = getattr(_lib.lib, name)
         assert fn.argtypes[7] is C.c_int32 and fn.argtypes[8] is C.c_int64, name   # channels, feature_stride
-    assert sorted(_lib.EXPORTS) == sorted(declared)
-    flat = re.sub(r"\s+", " ", text)
+    flat = abi.prototypes()
     tail = (r"const GsrCamera \*cam, const GsrOptions \*opts, int64_t max_pairs, void \*workspace, size_t workspace_bytes, "
             r"const float \*features , int32_t channels, int64_t feature_stride, float \*out_map , float \*out_final_T, void \*stream\);")
     assert re.search(r"int gsr_blend_channels\(int64_t n, " + tail, flat)
     assert re.search(r"int gsr_render_channels\(const GsrScene \*scene, " + tail, flat)
-    assert re.search(r"#define GSR_MAX_FEATURE_CHANNELS 1024\b", _header()) and _lib.GSR_MAX_FEATURE_CHANNELS == 1024
+    assert re.search(r"#define GSR_MAX_FEATURE_CHANNELS 1024\b", abi.header()) and _lib.GSR_MAX_FEATURE_CHANNELS == 1024
 
 
 def test_the_abi_version_stays_and_its_comment_names_the_additions():
-    from gsr_amd import _lib
-
-    assert _lib.lib.gsr_version() == 600 and _lib.GSR_VERSION == 600
-    m = re.search(r"#define GSR_VERSION 600 /\*(.*?)\*/", _header(), flags=re.S)
-    assert m and all(name in m.group(1) for name in NEW)
-    assert C.sizeof(_lib.GsrOptions) == 84 and C.sizeof(_lib.GsrStats) == 48 and C.sizeof(_lib.GsrScene) == 64
+    abi.assert_version_and_struct_sizes(NEW)
 
 
 @pytest.mark.parametrize("entry", NEW)
@@ -60,11 +45,7 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
         head = (C.byref(sc),) if entry == "gsr_render_channels" else (0,)
         return fn(*head, cam_p, opts_p, 100, None, 0, features, channels, stride, out_map, None, None)
 
-    def refused(rc, *words):
-        err = _lib.lib.gsr_last_error().decode()
-        assert rc == _lib.GSR_ERR_BAD_ARG, (entry, rc, err)
-        assert all(w in err for w in words), (entry, err)
-        return err
+    refused = abi.refused(entry)
 
     seen = [
         refused(call(C.byref(cam), C.byref(o), None, p), "null", "features"),
@@ -91,9 +72,5 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
 
 
 def test_the_new_kernel_has_a_translation_unit_of_its_own():
-    csrc = os.path.join(REPO, "torch-gaussian-splatting-rasterizer_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert os.path.exists(os.path.join(csrc, "blend_channels.hip"))
-    assert re.search(r"^OBJS\s*=.*\bblend_channels\.o\b", mk, flags=re.M)
-    rule = re.search(r"^blend_channels\.o:.*\n\t(.*)$", mk, flags=re.M)
-    assert rule and "-fno-slp-vectorize" in rule.group(1)  # the bits depend on it: the flags of blend_features.o
+    abi.assert_own_translation_unit("blend_channels")
+    assert "-fno-slp-vectorize" in abi.makefile_recipe("blend_channels.o")  # the bits depend on it: the flags of blend_features.o

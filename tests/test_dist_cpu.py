@@ -9,7 +9,7 @@ import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
 
-from conftest import REPO
+import conftest  # noqa: F401  (a spawned worker imports this module, and conftest puts the repository on its path)
 
 
 def _free_port():
@@ -21,9 +21,6 @@ def _free_port():
 
 
 def _worker(rank, world, port, H, W, q):
-    import sys
-
-    sys.path.insert(0, REPO)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from gsr_amd import dist as gdist
@@ -54,9 +51,6 @@ def _worker(rank, world, port, H, W, q):
 def _pipeline_worker(rank, world, port, H, W, q):
     """dist.ShardedFrames (bench.py's N-GPU loop) with 1, 3 and 6 (bench.py's default) frames in flight over gloo: a fake render writes
     the rank's strip of a known frame; 14 frames, so every wire buffer is reused; rank 0 must get every frame back, in order."""
-    import sys
-
-    sys.path.insert(0, REPO)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)
     from gsr_amd import dist as gdist

@@ -13,6 +13,7 @@ import torch
 
 import margin_scenes as ms
 from conftest import assert_frames_close
+from gpu_cases import namespace
 
 SIZES = [(650, 370), (960, 540), (1283, 723)]   # pipelined one-quadrant walk (984 tiles), plain one-quadrant walk (2040), two per wave (3726)
 _CACHE = {}
@@ -52,17 +53,7 @@ def test_margin_scenes_sit_on_the_boundaries(W, H):
 
 @pytest.fixture(scope="module")
 def G():
-    from gsr_amd import renderer
-    from oracle import cpu_oracle as orc
-
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.orc = renderer, orc
-    return ns
+    return namespace()
 
 
 def _setup(G, W, H):

@@ -6,30 +6,17 @@ import re
 
 import pytest
 
+import abi_checks as abi
 from conftest import REPO
 
 NEW = ("gsr_blend_features", "gsr_render_features")
 
 
-def _header():
-    return open(os.path.join(REPO, "include", "gsr.h")).read()
-
-
 def test_the_two_symbols_are_declared_exported_and_bound():
-    from gsr_amd import _lib
-
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", text))
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/gsr.h"
-        assert name in _lib.EXPORTS, f"{name} is not in _lib.EXPORTS"
-        fn = getattr(_lib.lib, name)                 # AttributeError: libgsr.so does not export it
-        assert fn.restype is C.c_int and len(fn.argtypes) == 10, name
-    assert _lib.EXPORTS.count(NEW[0]) == 1 and _lib.EXPORTS.count(NEW[1]) == 1
-    assert sorted(_lib.EXPORTS) == sorted(declared)
+    abi.assert_declared_exported_and_bound(NEW, 10)
     # the parameter lists the issue gives: (n, cam, opts, max_pairs, workspace, bytes, features, out_map, out_final_T, stream) and the
     # same with the scene in the place of n
-    flat = re.sub(r"\s+", " ", text)
+    flat = abi.prototypes()
     assert re.search(r"int gsr_blend_features\(int64_t n, const GsrCamera \*cam, const GsrOptions \*opts, int64_t max_pairs, void \*workspace, "
                      r"size_t workspace_bytes, const float \*features , float \*out_map, float \*out_final_T, void \*stream\);", flat)
     assert re.search(r"int gsr_render_features\(const GsrScene \*scene, const GsrCamera \*cam, const GsrOptions \*opts, int64_t max_pairs, "
@@ -39,10 +26,8 @@ def test_the_two_symbols_are_declared_exported_and_bound():
 def test_the_abi_version_and_every_struct_stay_where_they_were():
     from gsr_amd import _lib
 
-    assert _lib.lib.gsr_version() == 600 and _lib.GSR_VERSION == 600
-    assert re.search(r"#define GSR_VERSION 600\b", _header())
-    m = re.search(r"#define GSR_VERSION 600 /\*(.*?)\*/", _header(), flags=re.S)
-    assert m and "gsr_blend_features" in m.group(1) and "gsr_render_features" in m.group(1)   # the additions are recorded there
+    abi.assert_version_and_struct_sizes(NEW)  # (the additions are recorded in the version's comment)
+    assert re.search(r"#define GSR_VERSION 600\b", abi.header())
     # test_abi.test_struct_sizes_match_header, restated: the feature adds no field anywhere
     assert C.sizeof(_lib.GsrScene) == 64 and _lib.GsrScene.block_bounds.offset == 56
     assert C.sizeof(_lib.GsrCamera) == 4 * (16 + 16 + 3 + 6) + 8
@@ -69,10 +54,7 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
         head = (C.byref(sc),) if entry == "gsr_render_features" else (0,)
         return fn(*head, cam_p, opts_p, 100, None, 0, features, out_map, None, None)
 
-    def refused(rc, *words):
-        err = _lib.lib.gsr_last_error().decode()
-        assert rc == _lib.GSR_ERR_BAD_ARG, (entry, rc, err)
-        assert all(w in err for w in words), (entry, err)
+    refused = abi.refused(entry)
 
     refused(call(C.byref(cam), C.byref(o), None, p), "null", "features")
     refused(call(C.byref(cam), C.byref(o), p, None), "null", "output map")

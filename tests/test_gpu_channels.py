@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from conftest import psnr
-from test_gpu_features import MIN_DB, _build, _z_cam
+from gpu_cases import MIN_DB, build as _build, namespace, z_cam as _z_cam
 
 pytestmark = pytest.mark.gpu
 
@@ -27,18 +27,7 @@ C_ALL = max(COUNTS)
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import _lib, rasterize, renderer, synthetic, utils
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.rasterize, ns.synthetic, ns.utils, ns.orc, ns.lib = renderer, rasterize, synthetic, utils, orc, _lib
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    ns.cases = {}
-    return ns
+    return namespace()
 
 
 def _case(G, name):

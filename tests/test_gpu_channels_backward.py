@@ -20,73 +20,14 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import psnr
-from test_gpu_features import MIN_DB, _build
+from gpu_cases import N_CH, N_SAMPLE, bar as _bar, gradient_case as _case, namespace, sample as _sample, weight_maps as _weight_maps
 
 pytestmark = pytest.mark.gpu
-
-N_CH = 17
-N_SAMPLE = 96
 
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import _lib, renderer, synthetic, utils
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.synthetic, ns.utils, ns.orc, ns.lib = renderer, synthetic, utils, orc, _lib
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    ns.cases = {}
-    return ns
-
-
-def _case(G, name):
-    """The scene, its Rasterizer, the oracle's preprocess and depth order, N_CH feature columns in file order and the upstream
-    gradient Gm [H, W, N_CH]; computed once and only read."""
-    if name not in G.cases:
-        packed, args = _build(G, name)
-        cam, ocam = G.renderer.make_camera(*args), G.orc.camera(*args)
-        R = G.renderer.Rasterizer(G.renderer.GaussianScene.from_packed(packed))
-        pre = G.orc.preprocess(packed, ocam)
-        order = G.orc.depth_order(pre["cam_means"])
-        gen = torch.Generator().manual_seed(23)
-        Gm = torch.randn((cam.height, cam.width, N_CH), generator=gen)
-        F = torch.randn((R.scene.n, 2 * N_CH - 1), generator=gen) * 50.0
-        bb, sg = pre["pixel_bboxes"], pre["sigmas"]
-        drawable = ((bb[:, 2] - bb[:, 0]) * (bb[:, 3] - bb[:, 1]) != 0) & (sg != 0).all(1)  # what the oracle's loop does not skip
-        G.cases[name] = dict(packed=packed, cam=cam, ocam=ocam, R=R, pre=pre, order=order, Gm=Gm, Gt=Gm.cuda(), Ft=F.cuda(),
-                             drawable=drawable, refs={})
-    return G.cases[name]
-
-
-def _weight_maps(G, c, ids, restrict):
-    """The oracle's weight maps [len(ids), H, W] of the gaussians `ids`, three per orc.composite.  restrict: over the depth order
-    up to the last of the three, and of those gaussians only whose pixel bbox meets one of the three's — nobody else changes the
-    transmittance the three are drawn with, and the one-hot columns give everybody else the colour 0."""
-    cam, n, bb, order = c["cam"], len(c["drawable"]), c["pre"]["pixel_bboxes"], c["order"]
-    rank = np.empty(n, np.int64)
-    rank[order] = np.arange(n)
-    maps = np.zeros((len(ids), cam.height, cam.width), np.float32)
-    by_depth = np.argsort(rank[ids])  # neighbours in depth share a composite: short restricted orders
-    for k0 in range(0, len(ids), 3):
-        at = by_depth[k0:k0 + 3]
-        trio, sub = ids[at], order
-        if restrict:
-            sub = order[:rank[trio].max() + 1]
-            near = np.zeros(n, bool)
-            for i in trio:
-                near |= (bb[:, 0] < bb[i, 2]) & (bb[:, 2] > bb[i, 0]) & (bb[:, 1] < bb[i, 3]) & (bb[:, 3] > bb[i, 1])
-            sub = np.ascontiguousarray(sub[near[sub]])
-        onehot = np.zeros((n, 3), np.float32)
-        onehot[trio, np.arange(len(trio))] = 1.0
-        screen, _, _ = G.orc.composite(sub, dict(c["pre"], rgb=onehot), cam.width, cam.height, limit=-1, threads=G.orc.max_threads())
-        maps[at] = screen.transpose(2, 1, 0)[:len(trio)]
-    return maps
+    return namespace()
 
 
 def _reference(G, c, ids, restrict):
@@ -99,29 +40,6 @@ def _reference(G, c, ids, restrict):
         gm = c["Gm"].numpy().astype(np.float64).reshape(-1, N_CH)
         c["refs"][key] = (w @ gm, w.sum(1))
     return c["refs"][key]
-
-
-def _bar(tag, got, ref):
-    """Per channel PSNR of the block `got` against the oracle block `ref`, peak = max |ref channel|; prints, then asserts."""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    got, ref = got.reshape(len(ref), -1), ref.reshape(len(ref), -1)
-    dbs = []
-    for ch in range(ref.shape[1]):
-        peak = float(np.abs(ref[:, ch]).max())
-        dbs.append(psnr(got[:, ch], ref[:, ch], peak=peak) if peak > 0 else (float("inf") if not got[:, ch].any() else 0.0))
-    print(f"\n{tag}: {min(dbs):.1f} .. {max(dbs):.1f} dB over {len(dbs)} channels", end="")
-    assert min(dbs) >= MIN_DB, (tag, dbs)
-    return dbs
-
-
-def _sample(c, name):
-    """N_SAMPLE seeded gaussians among those the oracle's loop does not skip; "wall": among the first 5 % of their depth order, where
-    the transmittance has not yet reached zero."""
-    pool = c["order"][c["drawable"][c["order"]]]
-    if name == "wall":
-        pool = pool[:len(pool) // 20]
-    rng = np.random.default_rng(7)
-    return np.sort(rng.choice(pool, size=min(N_SAMPLE, len(pool)), replace=False))
 
 
 # ---- 1 ------------------------------------------------------------------------------------------------------------------

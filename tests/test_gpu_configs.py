@@ -23,23 +23,14 @@ import pytest
 import torch
 
 from conftest import REPO, assert_frames_close, psnr
+from gpu_cases import namespace
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import renderer, synthetic, utils
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.synthetic, ns.utils, ns.orc = renderer, synthetic, utils, orc
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return ns
+    return namespace()
 
 
 def _ring_camera(G, W, H, pose=0):

@@ -20,6 +20,7 @@ import torch
 
 import order_scenes as osc
 from conftest import assert_frames_close
+from gpu_cases import namespace
 
 pytestmark = pytest.mark.gpu
 
@@ -31,17 +32,7 @@ _ORACLE = {}                 # oracle frames per (scene, view), computed once an
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import _lib, renderer
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.orc, ns._lib = renderer, orc, _lib
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return ns
+    return namespace()
 
 
 def _oracle(G, key, s, vi=0):

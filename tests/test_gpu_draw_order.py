@@ -16,6 +16,7 @@ import torch
 
 import order_scenes as osc
 from conftest import assert_frames_close, psnr
+from gpu_cases import namespace
 
 pytestmark = pytest.mark.gpu
 
@@ -28,17 +29,7 @@ _ORACLE = {}   # oracle frames per (scene, camera); the scenes themselves are re
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import _lib, renderer
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.orc, ns._lib = renderer, orc, _lib
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return ns
+    return namespace()
 
 
 def _small(W, H, B, **kw):

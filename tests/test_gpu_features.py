@@ -7,105 +7,20 @@ channel| (the project's standing bar for fp32 compositing: the sums are linear i
 |alpha - (1 - T)| < 1e-5, no pixel excluded.
 """
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO, golden_columns, load_golden, psnr
+from conftest import psnr
+from gpu_cases import MIN_DB, feature_case as _case, medium as _medium, namespace, oracle_maps as _oracle_maps, z_cam as _z_cam
 
 pytestmark = pytest.mark.gpu
-
-MIN_DB = 100.0
 
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import rasterize, renderer, synthetic, utils
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.rasterize, ns.synthetic, ns.utils, ns.orc = renderer, rasterize, synthetic, utils, orc
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    ns.cases = {}
-    return ns
-
-
-def _medium(G, n=200_000, seed=5, shift=1.2, W=640, H=360, pose=2):
-    cols = G.synthetic.mip360_like(n, seed)
-    for i in range(3):
-        cols[f"scale_{i}"] = (cols[f"scale_{i}"] + np.float32(shift)).astype(np.float32)
-    p = G.synthetic.ring_cameras(25)[pose]
-    fx = G.synthetic.pinhole_focal(W)
-    return G.utils.pack_gaussians(cols), (p.qvec, p.tvec, 2 * fx, 2 * fx, 2 * W, 2 * H, W, H)
-
-
-def _golden(G, name, prefix=""):
-    g = load_golden(name)
-    args = (g[prefix + "qvec"], g[prefix + "tvec"], float(g["fx_full"]), float(g["fy_full"]), int(g["cam_width"]),
-            int(g["cam_height"]), int(g["width"]), int(g["height"]))
-    return G.utils.pack_gaussians(golden_columns(g)), args
-
-
-def _build(G, name):
-    if name == "f1":
-        return _golden(G, "f1_unit.npz")
-    if name == "f2":
-        return _golden(G, "f2_small.npz")
-    if name in ("f3a", "f3b"):
-        return _golden(G, "f3_edge.npz", name[2] + "_")
-    if name == "f5":
-        sys.path.insert(0, os.path.join(REPO, "tools"))
-        import fuzz_parity
-
-        g = load_golden("f5_deep_stack.npz")
-        c = fuzz_parity.build_case(int(g["case_seed"]), int(g["max_n"]))
-        return c["packed"], c["args"]
-    if name == "medium":
-        return _medium(G)
-    if name == "1080p":
-        return _medium(G, n=600_000, seed=360, shift=0.8, W=1920, H=1080, pose=0)
-    if name == "wall":  # the "opaque wall" of test_gpu_parity._rule_cases: every opacity logit 6 (alpha capped at 0.99)
-        packed, args = _medium(G, n=300_000, shift=1.6)
-        packed["opacity_logit"] = np.full_like(packed["opacity_logit"], 6.0)
-        return packed, args
-    raise KeyError(name)
-
-
-def _z_cam(G, cam, means):
-    """fp32 camera-space depth of every gaussian: column 2 of gsr_project_to_camera_space for the camera's w2c."""
-    w2c = torch.tensor(list(cam.w2c), dtype=torch.float32).view(4, 4)
-    return G.rasterize.project_to_camera_space(torch.from_numpy(np.ascontiguousarray(means)).cuda(), w2c)[:, 2].cpu().numpy()
-
-
-def _case(G, name):
-    """packed scene (file order), cameras, a Rasterizer on the Morton-ordered scene and the test features
-    (z_cam, 1, 1000 - 3.5 z_cam) in file order."""
-    if name not in G.cases:
-        packed, args = _build(G, name)
-        cam, ocam = G.renderer.make_camera(*args), G.orc.camera(*args)
-        R = G.renderer.Rasterizer(G.renderer.GaussianScene.from_packed(packed))
-        z = _z_cam(G, cam, packed["means"])
-        F = np.stack([z, np.ones_like(z), np.float32(1000.0) - np.float32(3.5) * z], 1).astype(np.float32)
-        F[~np.isfinite(F)] = 0.0  # (gaussians with such values are culled; the array must still be finite)
-        G.cases[name] = dict(packed=packed, cam=cam, ocam=ocam, R=R, F=F, Ft=torch.from_numpy(F).cuda())
-    return G.cases[name]
-
-
-def _oracle_maps(G, c, feats, limit=-1):
-    """The oracle's compositing loop over `feats` [n,3] in the place of the colours -> (map [H,W,3], T [H,W], drawn)."""
-    if "pre" not in c:
-        c["pre"] = G.orc.preprocess(c["packed"], c["ocam"])
-        c["order"] = G.orc.depth_order(c["pre"]["cam_means"])
-    pre = dict(c["pre"], rgb=np.ascontiguousarray(feats, np.float32))
-    screen, trans, drawn = G.orc.composite(c["order"], pre, c["cam"].width, c["cam"].height, limit=limit, threads=G.orc.max_threads())
-    return screen.transpose(1, 0, 2), trans.transpose(1, 0), drawn
+    return namespace()
 
 
 def _check_against_oracle(tag, m, T, om, oT):

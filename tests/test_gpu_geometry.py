@@ -18,6 +18,7 @@ import pytest
 import torch
 
 from conftest import assert_frames_close, psnr
+from gpu_cases import namespace
 
 pytestmark = pytest.mark.gpu
 
@@ -114,17 +115,7 @@ assert _path(4096, 2033, True)["drop_from"] == 32768
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import renderer, synthetic, utils
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.synthetic, ns.utils, ns.orc = renderer, synthetic, utils, orc
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return ns
+    return namespace()
 
 
 def _columns(c, seed=12):

@@ -15,8 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_channels_backward import _bar, _case, _sample, _weight_maps
-from test_gpu_features import _build  # the scenes (also what the gradient tests' _case builds)
+from gpu_cases import bar as _bar, build as _build, gradient_case as _case, namespace, sample as _sample, weight_maps as _weight_maps
 
 pytestmark = pytest.mark.gpu
 
@@ -25,30 +24,22 @@ SAMPLED = ["f2", "f5", "medium", "wall"]
 PER_WALK = 16
 
 
+class OneThreadOracle:
+    """The oracle with one thread per composite: the small scenes' composites are a few hundred gaussians on a few thousand
+    pixels each, less work than handing it to a thread team costs (17 s against 0.04 s per scene late in a whole-suite run)."""
+    def __getattr__(self, name):
+        from oracle import cpu_oracle as orc
+
+        return getattr(orc, name)
+
+    @staticmethod
+    def max_threads():
+        return 1
+
+
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import _lib, renderer, synthetic, utils
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    class OneThreadOracle:
-        """The oracle with one thread per composite: the small scenes' composites are a few hundred gaussians on a few thousand
-        pixels each, less work than handing it to a thread team costs (17 s against 0.04 s per scene late in a whole-suite run)."""
-        def __getattr__(self, name):
-            return getattr(orc, name)
-
-        @staticmethod
-        def max_threads():
-            return 1
-
-    ns = NS()
-    ns.renderer, ns.synthetic, ns.utils, ns.orc, ns.lib = renderer, synthetic, utils, OneThreadOracle(), _lib
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    ns.cases = {}
-    return ns
+    return namespace(OneThreadOracle())
 
 
 def _ids(c, name):

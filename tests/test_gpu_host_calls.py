@@ -10,13 +10,12 @@ Three things per call, none of them a number the code under test produces:
      are held to the bar test_gpu_channels_backward applies between two runs of one gradient; a caller's `out` ends as what it
      held before plus ONE view's contribution: the overflowed first attempt added nothing.
 
-Scene: test_gpu_pick's 40 x 24 deep-tile scene (1000 gaussians, two tile rows).
+Scene: gpu_cases.deep_tile_scene, 40 x 24 (1000 gaussians, two tile rows).
 """
 import pytest
 import torch
 
-from test_gpu_channels_backward import _bar
-from test_gpu_pick import _deep_tile_scene
+from gpu_cases import bar as _bar, deep_tile_scene as _deep_tile_scene
 
 pytestmark = pytest.mark.gpu
 

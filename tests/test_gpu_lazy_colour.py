@@ -8,14 +8,13 @@ it is known, from the CPU oracle's own per-pixel evaluation, which colours nobod
 """
 import ctypes as C
 import math
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO, golden_columns, load_golden
+from conftest import golden_columns, load_golden
+from gpu_cases import f5_case, golden_args, namespace
 
 pytestmark = pytest.mark.gpu
 
@@ -24,16 +23,7 @@ SAME_COUNTERS = ("n_pairs", "fetched_entries", "wave_entries")
 
 @pytest.fixture(scope="module")
 def G():
-    from gsr_amd import _lib, renderer, synthetic, utils
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.synthetic, ns.utils, ns.orc, ns.lib = renderer, synthetic, utils, orc, _lib
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return ns
+    return namespace()
 
 
 def _ring_args(G, W, H, pose):
@@ -80,14 +70,8 @@ def _fixture_cases(G):
     out = []
     for name, prefix in (("f2_small.npz", ""), ("f3_edge.npz", "a_"), ("f3_edge.npz", "b_")):
         g = load_golden(name)
-        args = (g[prefix + "qvec"], g[prefix + "tvec"], float(g["fx_full"]), float(g["fy_full"]), int(g["cam_width"]),
-                int(g["cam_height"]), int(g["width"]), int(g["height"]))
-        out.append((name + prefix, G.utils.pack_gaussians(golden_columns(g)), G.renderer.make_camera(*args)))
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import fuzz_parity
-
-    g = load_golden("f5_deep_stack.npz")
-    c = fuzz_parity.build_case(int(g["case_seed"]), int(g["max_n"]))
+        out.append((name + prefix, G.utils.pack_gaussians(golden_columns(g)), G.renderer.make_camera(*golden_args(g, prefix))))
+    _, c = f5_case()
     out.append(("f5_deep_stack", c["packed"], G.renderer.make_camera(*c["args"])))
     return out
 

@@ -9,29 +9,14 @@ import pytest
 import torch
 
 from conftest import assert_frames_close, golden_columns, load_golden, psnr
+from gpu_cases import f5_case, fuzz_case, golden_cameras as _cams, medium_cameras as _medium, namespace
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd
-    from gsr_amd import renderer, synthetic, utils
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.synthetic, ns.utils, ns.orc = renderer, synthetic, utils, orc
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return ns
-
-
-def _cams(G, g, prefix=""):
-    args = (g[prefix + "qvec"], g[prefix + "tvec"], float(g["fx_full"]), float(g["fy_full"]), int(g["cam_width"]),
-            int(g["cam_height"]), int(g["width"]), int(g["height"]))
-    return G.renderer.make_camera(*args), G.orc.camera(*args)
+    return namespace()
 
 
 def _rel(a, b):
@@ -373,16 +358,6 @@ def test_reference_screen_layout(G):
     assert torch.equal(a, b.permute(1, 0, 2))
 
 
-def _medium(G, n=200_000, seed=5, shift=1.2, W=640, H=360, pose=2):
-    cols = G.synthetic.mip360_like(n, seed)
-    for i in range(3):
-        cols[f"scale_{i}"] = (cols[f"scale_{i}"] + np.float32(shift)).astype(np.float32)
-    p = G.synthetic.ring_cameras(25)[pose]
-    fx = G.synthetic.pinhole_focal(W)
-    args = (p.qvec, p.tvec, 2 * fx, 2 * fx, 2 * W, 2 * H, W, H)
-    return cols, G.renderer.make_camera(*args), G.orc.camera(*args)
-
-
 def test_medium_scene_vs_oracle(G):
     cols, cam, ocam = _medium(G)
     R = G.renderer.Rasterizer(G.renderer.GaussianScene.from_columns(cols))
@@ -520,15 +495,7 @@ def _rule_cases(G):
         g = load_golden(name)
         out.append((name + prefix, golden_columns(g), _cams(G, g, prefix)[0]))
     # f5: the deep-stack fuzz case (hundreds of semi-transparent layers per pixel), rebuilt from its seed like its own test does
-    import os
-    import sys
-
-    from conftest import REPO
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import fuzz_parity
-
-    g = load_golden("f5_deep_stack.npz")
-    c = fuzz_parity.build_case(int(g["case_seed"]), int(g["max_n"]))
+    _, c = f5_case()
     out.append(("f5_deep_stack", c["packed"], G.renderer.make_camera(*c["args"])))
     return out
 
@@ -1099,14 +1066,7 @@ def test_fuzz_case_that_stalled_round_2_replays(G):
     nothing (depth-sort plan 1 pass), the shifted `cam2` sees the gaussian (3 passes).  render_batch([cam, cam2, cam]) with
     the bound learned from `cam` looped forever in round 2; it must return and equal the three single renders — through
     Rasterizer and through FramesInFlight with more views than slots."""
-    import os
-    import sys
-
-    from conftest import REPO
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import fuzz_parity
-
-    c = fuzz_parity.build_case(1607415101109889117, 120000)
+    c = fuzz_case(1607415101109889117, 120000)
     assert c["n"] == 1 and (c["W"], c["H"]) == (160, 360)
     args, pose = c["args"], c["pose"]
     cam = G.renderer.make_camera(*args)
@@ -1130,15 +1090,7 @@ def test_fuzz_case_that_stalled_round_2_replays(G):
 def test_f5_deep_stacks_against_the_reference_frame(G):
     """The HIP frame of fixture f5 (see tests/test_oracle_golden.py: the reference's own frame of the deep-stack fuzz case)
     against the REFERENCE, not the oracle: no further from it than the plain-C oracle is (111.7 dB, worst pixel 3.3e-5)."""
-    import os
-    import sys
-
-    from conftest import REPO
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import fuzz_parity
-
-    g = load_golden("f5_deep_stack.npz")
-    c = fuzz_parity.build_case(int(g["case_seed"]), int(g["max_n"]))
+    g, c = f5_case()
     R = G.renderer.Rasterizer(G.renderer.GaussianScene.from_packed(c["packed"]))
     img = R.render(G.renderer.make_camera(*c["args"])).cpu().numpy()
     assert R.last_stats["n_visible"] <= int(g["n_drawn"])

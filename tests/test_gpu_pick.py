@@ -10,120 +10,20 @@ References, none of them the code under test:
     project's standing 1e-4 bar on a transmittance or a weight.
 """
 import ctypes as C
-import os
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from conftest import REPO
-from test_gpu_features import G, _build, _case, _oracle_maps, _z_cam  # noqa: F401  (G: the module fixture)
+from gpu_cases import (MEDIANS, NEVER, exact as _exact, feature_case as _case, namespace, oracle_maps as _oracle_maps,
+                       pick_case as _pick_case, z_cam as _z_cam)
 
 pytestmark = pytest.mark.gpu
 
-MEDIANS = (0.5, 0.9, 1.0)
-NEVER = 1 << 30
 
-
-# ---- scenes -------------------------------------------------------------------------------------------------------------------
-def _custom_case(G, name, packed, args):
-    if name not in G.cases:
-        cam, ocam = G.renderer.make_camera(*args), G.orc.camera(*args)
-        R = G.renderer.Rasterizer(G.renderer.GaussianScene.from_packed(packed))
-        G.cases[name] = dict(packed=packed, cam=cam, ocam=ocam, R=R)
-    return G.cases[name]
-
-
-def _deep_tile_scene():
-    """40x24 (3x2 tiles), 1000 gaussians at 1000 distinct depths, array order shuffled against depth order.  Nine in ten lie in the
-    first quadrant of tile (0, 0): small (sigma 0.5 - 0.9 px before the low-pass) and faint (opacity 0.0042 - 0.0065: alpha just above
-    1/255, on the few pixels next to the centre only), so a pixel keeps most of its transmittance through hundreds of list entries; five strong, wider ones lie late in depth
-    (ranks 560, 700, 850, 990, 995) over the same quadrant; the rest are scattered over the frame."""
-    sys.path.insert(0, os.path.join(REPO, "tests"))
-    from order_scenes import camera_args
-
-    W, H, n = 40, 24, 1000
-    args, f = camera_args(W, H)
-    rng = np.random.default_rng(17)
-    rank = rng.permutation(n)
-    z = 1.0 + 0.002 * rank
-    strong = np.isin(rank, (560, 700, 850, 990, 995))
-    away = (rank % 10 == 3) & ~strong
-    cx, cy = rng.uniform(1.5, 6.5, n), rng.uniform(1.5, 6.5, n)
-    sigma, opacity = rng.uniform(0.5, 0.9, n), rng.uniform(0.0042, 0.0065, n)
-    cx[away], cy[away] = rng.uniform(0, W, away.sum()), rng.uniform(0, H, away.sum())
-    sigma[away], opacity[away] = rng.uniform(1.5, 4.0, away.sum()), rng.uniform(0.05, 0.6, away.sum())
-    cx[strong], cy[strong] = rng.uniform(2.0, 6.0, strong.sum()), rng.uniform(2.0, 6.0, strong.sum())
-    sigma[strong], opacity[strong] = rng.uniform(3.0, 5.0, strong.sum()), rng.uniform(0.7, 0.95, strong.sum())
-    x, y = (cx + 0.5 - 0.5 * W) * z / f, (cy + 0.5 - 0.5 * H) * z / f
-    s = np.log(sigma * z / f)
-    q = rng.normal(size=(n, 4))
-    packed = dict(means=np.stack([x, y, z], 1).astype(np.float32),
-                  log_scales=np.stack([s + rng.uniform(-0.2, 0.2, n), s, s + rng.uniform(-0.2, 0.2, n)], 1).astype(np.float32),
-                  quats=(q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32),
-                  opacity_logit=np.log(opacity / (1.0 - opacity)).astype(np.float32), sh=np.zeros((n, 16, 3), np.float32))
-    return {k: np.ascontiguousarray(v) for k, v in packed.items()}, args
-
-
-def _pick_case(G, name):
-    if name == "deep":
-        return _custom_case(G, "pick_deep", *_deep_tile_scene())
-    if name == "stacks":
-        sys.path.insert(0, os.path.join(REPO, "tests"))
-        from order_scenes import OrderScene
-
-        s = OrderScene(64, 48, 12, seed=5)
-        return _custom_case(G, "pick_stacks", s.packed, s.cam_args)
-    return _case(G, name)
-
-
-# ---- the exact reference --------------------------------------------------------------------------------------------------------
-def _expected_of(Wk, appear, med, med_rank):
-    """The expected maps after some prefix: Wk [H,W,n] its weights, appear [H,W,n] the prefix each gaussian first had w > 0 in."""
-    bw = Wk.max(-1).values
-    is_max = (Wk == bw[..., None]) & (bw[..., None] > 0)
-    first = torch.where(is_max, appear, torch.full_like(appear, NEVER))  # of several maximisers: the first in the prefix sweep
-    bid = first.argmin(-1).to(torch.int32)
-    bid = torch.where(bw > 0, bid, torch.full_like(bid, -1))
-    brank = torch.where(bw > 0, first.min(-1).values, torch.zeros_like(bid))
-    return dict(best_id=bid, best_w=bw.clone(), best_rank=brank, count=(Wk > 0).sum(-1).to(torch.int32),
-                median_id={m: v.clone() for m, v in med.items()}, median_rank={m: v.clone() for m, v in med_rank.items()})
-
-
-def _exact(G, c, snapshots=()):
-    """One sweep of the prefixes per scene, shared by the tests that need it: c["exact"] = the expected maps of the whole draw,
-    c["exact_at"][k] those of draw_limit = k, c["W"] the full weight maps (file order, like the ids render_pick returns)."""
-    if "exact" in c:
-        assert all(k in c["exact_at"] for k in snapshots)
-        return c["exact"]
-    R, cam, mk = c["R"], c["cam"], G.renderer.make_options
-    n, dev = R.scene.n, R.scene.device
-    eye = torch.eye(n, dtype=torch.float32, device=dev)
-    W_full, T_full = R.render_features(cam, eye, return_T=True)
-    shape = (cam.height, cam.width)
-    appear = torch.zeros(shape + (n,), dtype=torch.int32, device=dev)
-    med = {m: torch.full(shape, -1, dtype=torch.int32, device=dev) for m in MEDIANS}
-    med_rank = {m: torch.zeros(shape, dtype=torch.int32, device=dev) for m in MEDIANS}
-    prev, at = torch.zeros_like(W_full), {}
-    for k in range(1, n + 1):  # (prefixes past the last drawn gaussian are the whole draw again)
-        Wk, Tk = R.render_features(cam, eye, mk(draw_limit=k), return_T=True)
-        new = (Wk > 0) & (prev == 0)
-        appear = torch.where(new, torch.full_like(appear, k), appear)
-        for m in MEDIANS:
-            cross = (Tk < m) & (med_rank[m] == 0)  # r = min{k : T^(k) < median_T}
-            if bool(cross.any()):
-                rows = new[cross]
-                assert bool((rows.sum(-1) == 1).all()), (k, m)  # the unique gaussian the prefix gained at these pixels
-                med[m][cross] = rows.to(torch.int32).argmax(-1).to(torch.int32)
-                med_rank[m][cross] = k
-        if k in snapshots:
-            at[k] = _expected_of(Wk, appear, med, med_rank)
-        prev = Wk
-    assert torch.equal(prev, W_full) and torch.equal(Tk, T_full)  # the sweep ended on the frame's own weights
-    c["W"], c["T"], c["appear"], c["exact_at"] = W_full, T_full, appear, at
-    c["exact"] = _expected_of(W_full, appear, med, med_rank)
-    return c["exact"]
+@pytest.fixture(scope="module")
+def G():
+    return namespace()
 
 
 def _assert_picks(tag, got, exp, median_T, count=True):

@@ -17,15 +17,18 @@ import pytest
 import torch
 
 from conftest import psnr
-from test_gpu_features import G, _case  # noqa: F401  (G: the module fixture)
-from test_gpu_pick import _custom_case, _pick_case
-from test_gpu_topk import _wall_scene
+from gpu_cases import custom_case as _custom_case, feature_case as _case, namespace, pick_case as _pick_case, wall_scene as _wall_scene
 
 pytestmark = pytest.mark.gpu
 
 INF = float("inf")
 FIXTURES = ["f1", "f3a", "f3b"]
 WIDTH_OF = {"f1": 5, "f3a": 3, "f3b": 19, "deep": 8, "wall": 4}  # channels of the near-and-far tests: every walk width (8, 4, 16 + 4, 8, 4)
+
+
+@pytest.fixture(scope="module")
+def G():
+    return namespace()
 
 
 # ---- cases ----------------------------------------------------------------------------------------------------------------------

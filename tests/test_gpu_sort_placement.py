@@ -14,6 +14,7 @@ import torch
 
 import order_scenes as osc
 from conftest import assert_frames_close
+from gpu_cases import namespace
 
 pytestmark = pytest.mark.gpu
 
@@ -24,17 +25,7 @@ _ORACLE = {}
 
 @pytest.fixture(scope="module")
 def G():
-    import gsr_amd  # noqa: F401
-    from gsr_amd import _lib, renderer
-    from oracle import cpu_oracle as orc
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.renderer, ns.orc, ns._lib = renderer, orc, _lib
-    assert torch.cuda.is_available(), "these tests need the MI355X"
-    return ns
+    return namespace()
 
 
 def _file_order(G, packed):

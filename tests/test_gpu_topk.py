@@ -3,7 +3,7 @@ nearest gaussians with w > 0, ids and weights.
 
 References, none of them the code under test:
   - exact: channel i of R.render_features(cam, eye(n)) IS w_i(p), bit for bit (the argument of tests/test_gpu_pick.py's docstring),
-    and the draw order of a pixel's contributors is the order they appear in that file's prefix sweep (`_exact` -> c["appear"]: the
+    and the draw order of a pixel's contributors is the order they appear in the prefix sweep (gpu_cases.exact -> c["appear"]: the
     value is the gaussian's position in the frame's draw order, the same at every pixel it has weight in).  The deep scene's draw
     order is its construction's: depth rank = `rank`, all depths distinct.  Expected HEAVIEST = the contributors sorted by
     (-w, appearance), first k; NEAREST = sorted by appearance, first k; both padded with -1 / 0.  Bit for bit, no pixel excluded;
@@ -14,12 +14,17 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_features import G, _case, _oracle_maps  # noqa: F401  (G: the module fixture)
-from test_gpu_pick import NEVER, _exact, _pick_case
+from gpu_cases import (NEVER, custom_case as _custom_case, exact as _exact, feature_case as _case, namespace, oracle_maps as _oracle_maps,
+                       pick_case as _pick_case, wall_scene as _wall_scene)
 
 pytestmark = pytest.mark.gpu
 
 SELECTS = ("heaviest", "nearest")
+
+
+@pytest.fixture(scope="module")
+def G():
+    return namespace()
 
 
 # ---- the exact reference --------------------------------------------------------------------------------------------------------
@@ -109,7 +114,7 @@ def test_a_deep_tile_displaces_full_lists_in_the_later_batches(G):
     R, cam = c["R"], c["cam"]
     n, dev = R.scene.n, R.scene.device
     assert n == 1000 and (cam.width, cam.height) == (40, 24)
-    rank = torch.from_numpy(np.random.default_rng(17).permutation(n)).to(dev)  # _deep_tile_scene's first draw: depth rank, file order
+    rank = torch.from_numpy(np.random.default_rng(17).permutation(n)).to(dev)  # deep_tile_scene's first draw: depth rank, file order
     if "W" not in c:
         c["W"], c["T"] = R.render_features(cam, torch.eye(n, dtype=torch.float32, device=dev), return_T=True)
     W, step = c["W"], rank + 1
@@ -162,39 +167,7 @@ def test_a_deep_tile_displaces_full_lists_in_the_later_batches(G):
 
 
 # ---- 3b: the HEAVIEST stop fires, and changes no bit -----------------------------------------------------------------------------
-def _wall_scene():
-    """32x16 (two tiles), 300 gaussians at 300 distinct depths, array order shuffled against depth order.  The six nearest are wide
-    (sigma 40 px, centred on the frame) and nearly opaque: behind them T is below every pixel's fourth weight.  The other 294 are small
-    and faint and lie behind: they keep T above zero, so the feature blend walks every one of them."""
-    from order_scenes import camera_args
-
-    W, H, n = 32, 16, 300
-    args, f = camera_args(W, H)
-    rng = np.random.default_rng(23)
-    rank = rng.permutation(n)
-    z = 1.0 + 0.002 * rank
-    front = rank < 6
-    cx, cy = rng.uniform(0, W, n), rng.uniform(0, H, n)
-    sigma, opacity = rng.uniform(3.0, 6.0, n), rng.uniform(0.05, 0.3, n)
-    cx[front], cy[front] = rng.uniform(14.0, 18.0, 6), rng.uniform(6.0, 10.0, 6)
-    sigma[front], opacity[front] = 40.0, rng.uniform(0.90, 0.97, 6)
-    x, y = (cx + 0.5 - 0.5 * W) * z / f, (cy + 0.5 - 0.5 * H) * z / f
-    s = np.log(sigma * z / f)
-    q = rng.normal(size=(n, 4))
-    packed = dict(means=np.stack([x, y, z], 1).astype(np.float32), log_scales=np.stack([s, s, s], 1).astype(np.float32),
-                  quats=(q / np.linalg.norm(q, axis=1, keepdims=True)).astype(np.float32),
-                  opacity_logit=np.log(opacity / (1.0 - opacity)).astype(np.float32), sh=np.zeros((n, 16, 3), np.float32))
-    return {k: np.ascontiguousarray(v) for k, v in packed.items()}, args, rank
-
-
 def test_the_heaviest_stop_fires_behind_an_opaque_wall_and_changes_no_bit(G):
-    import os
-    import sys
-
-    from conftest import REPO
-    from test_gpu_pick import _custom_case
-
-    sys.path.insert(0, os.path.join(REPO, "tests"))
     packed, args, rank = _wall_scene()
     c = _custom_case(G, "topk_wall", packed, args)
     R, cam = c["R"], c["cam"]

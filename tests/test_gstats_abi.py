@@ -2,37 +2,27 @@
 version moved; their argument checks run before any HIP call; Rasterizer.view_stats refuses bad arguments before it allocates; and
 the host-side arithmetic of renderer.accumulate_view_stats."""
 import ctypes as C
-import os
 import re
 import types
 
 import pytest
 import torch
 
-from conftest import REPO
+import abi_checks as abi
 
 NEW = ("gsr_blend_gaussian_stats", "gsr_render_gaussian_stats")
-
-
-def _header():
-    return open(os.path.join(REPO, "include", "gsr.h")).read()
 
 
 def test_the_two_symbols_are_declared_exported_and_bound():
     from gsr_amd import _lib
 
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", text))
+    abi.assert_declared_exported_and_bound(NEW, 11)
     for name in NEW:
-        assert name in declared, f"{name} is not declared in include/gsr.h"
-        assert _lib.EXPORTS.count(name) == 1, f"{name} is not (once) in _lib.EXPORTS"
-        fn = getattr(_lib.lib, name)                 # AttributeError: libgsr.so does not export it
-        assert fn.restype is C.c_int and len(fn.argtypes) == 11, name
+        fn = getattr(_lib.lib, name)
         assert fn.argtypes[3] is C.c_int64 and fn.argtypes[5] is C.c_size_t, name   # max_pairs, workspace_bytes
         assert all(t is C.c_void_p for t in fn.argtypes[6:]), name                   # mask, the three outputs, the stream
     assert _lib.lib.gsr_blend_gaussian_stats.argtypes[0] is C.c_int64
-    assert sorted(_lib.EXPORTS) == sorted(declared)
-    flat = re.sub(r"\s+", " ", text)
+    flat = abi.prototypes()
     tail = (r"const GsrCamera \*cam, const GsrOptions \*opts, int64_t max_pairs, void \*workspace, size_t workspace_bytes, "
             r"const uint8_t \*pixel_mask , float \*weight_sum, float \*weight_max, uint32_t \*pixels, void \*stream\);")
     assert re.search(r"int gsr_blend_gaussian_stats\(int64_t n, " + tail, flat)
@@ -40,18 +30,11 @@ def test_the_two_symbols_are_declared_exported_and_bound():
 
 
 def test_the_abi_version_stays_and_its_comment_names_the_additions():
-    from gsr_amd import _lib
-
-    assert _lib.lib.gsr_version() == 600 and _lib.GSR_VERSION == 600
-    m = re.search(r"#define GSR_VERSION 600 /\*(.*?)\*/", _header(), flags=re.S)
-    assert m and all(name in m.group(1) for name in NEW)
-    assert C.sizeof(_lib.GsrOptions) == 84 and C.sizeof(_lib.GsrStats) == 48 and C.sizeof(_lib.GsrScene) == 64
+    abi.assert_version_and_struct_sizes(NEW)
 
 
 def test_the_header_states_the_contract():
-    m = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int gsr_blend_gaussian_stats\(", _header(), flags=re.S)
-    assert m
-    doc = re.sub(r"\s+\*?\s*", " ", m.group(1))
+    doc = re.sub(r"\s+\*?\s*", " ", abi.header_comment_before(r"int gsr_blend_gaussian_stats\("))
     for words in ("exact and reproducible to the bit", "order the adds arrive in", "NON-NEGATIVE FINITE floats on entry", "ACCUMULATE",
                   "not all three", "non-zero = the pixel counts", "colour_evals = 0", "Single views"):
         assert words in doc, words
@@ -73,11 +56,7 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
         head = (C.byref(sc),) if entry == "gsr_render_gaussian_stats" else (0,)
         return fn(*head, cam_p, opts_p, 100, None, 0, mask, *outs, None)
 
-    def refused(rc, *words):
-        err = _lib.lib.gsr_last_error().decode()
-        assert rc == _lib.GSR_ERR_BAD_ARG, (entry, rc, err)
-        assert all(w in err for w in words), (entry, err)
-        return err
+    refused = abi.refused(entry)
 
     seen = [
         refused(call(None, C.byref(o)), "null", "camera"),
@@ -100,15 +79,11 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
 
 
 def test_the_new_kernel_has_a_translation_unit_of_its_own():
-    csrc = os.path.join(REPO, "torch-gaussian-splatting-rasterizer_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert os.path.exists(os.path.join(csrc, "blend_gstats.hip"))
-    assert re.search(r"^OBJS\s*=.*\bblend_gstats\.o\b", mk, flags=re.M)
-    rule = re.search(r"^blend_gstats\.o:(.*)\n\t(.*)$", mk, flags=re.M)
-    grad = re.search(r"^blend_channels_backward\.o:(.*)\n\t(.*)$", mk, flags=re.M)
-    assert rule and grad and "-fno-slp-vectorize" in rule.group(2)  # the weights' bits depend on it: the gradient kernel's flags
-    assert rule.group(2).split() == grad.group(2).split()
-    assert [d for d in rule.group(1).split() if d != "blend_gstats.hip"] == [d for d in grad.group(1).split() if d != "blend_channels_backward.hip"]
+    abi.assert_own_translation_unit("blend_gstats")
+    rule, grad = abi.makefile_rule("blend_gstats.o"), abi.makefile_rule("blend_channels_backward.o")
+    assert "-fno-slp-vectorize" in rule[1]  # the weights' bits depend on it: the gradient kernel's flags
+    assert rule[1].split() == grad[1].split()
+    assert [d for d in rule[0].split() if d != "blend_gstats.hip"] == [d for d in grad[0].split() if d != "blend_channels_backward.hip"]
 
 
 class _NoWorkspace(Exception):

@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 from conftest import golden_columns, load_golden, psnr
+from gpu_cases import f5_case, golden_args
 from oracle import cpu_oracle as orc
 
 import gsr_amd
@@ -11,8 +12,7 @@ from gsr_amd import synthetic, utils
 
 
 def _cam(g, prefix=""):
-    return orc.camera(g[prefix + "qvec"], g[prefix + "tvec"], float(g["fx_full"]), float(g["fy_full"]),
-                      int(g["cam_width"]), int(g["cam_height"]), int(g["width"]), int(g["height"]))
+    return orc.camera(*golden_args(g, prefix))
 
 
 def _rel(a, b):
@@ -150,15 +150,7 @@ def test_f5_deep_stacks_oracle_vs_the_reference():
     its log2-domain exponent.  It is not: the ORACLE (plain C, expf, the reference's own formula and order) differs from
     the reference's torch arithmetic by more than that — measured here: 192 of 5400 pixels off by more than 1e-5, the worst
     3.3e-5, 111.7 dB.  Deep stacks accumulate every alpha's last-ulp difference in T; the draw sets are identical."""
-    import os
-    import sys
-
-    from conftest import REPO
-    sys.path.insert(0, os.path.join(REPO, "tools"))
-    import fuzz_parity
-
-    g = load_golden("f5_deep_stack.npz")
-    c = fuzz_parity.build_case(int(g["case_seed"]), int(g["max_n"]))
+    g, c = f5_case()
     assert (c["n"], c["W"], c["H"]) == (int(g["n"]), int(g["width"]), int(g["height"]))
     img, drawn = orc.render(c["packed"], orc.camera(*c["args"]))
     assert drawn == int(g["n_drawn"])

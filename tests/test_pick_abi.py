@@ -1,34 +1,24 @@
 """CPU: gsr_blend_pick / gsr_render_pick are additions to ABI 0.6.0 — declared, exported and bound; no struct or version moved; their
 argument checks run before any HIP call; and the host-side id mapping (renderer.file_order_ids) is the scene's permutation."""
 import ctypes as C
-import os
 import re
 
 import pytest
 import torch
 
-from conftest import REPO
+import abi_checks as abi
 
 NEW = ("gsr_blend_pick", "gsr_render_pick")
-
-
-def _header():
-    return open(os.path.join(REPO, "include", "gsr.h")).read()
 
 
 def test_the_two_symbols_are_declared_exported_and_bound():
     from gsr_amd import _lib
 
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", text))
+    abi.assert_declared_exported_and_bound(NEW, 12)
     for name in NEW:
-        assert name in declared, f"{name} is not declared in include/gsr.h"
-        assert _lib.EXPORTS.count(name) == 1, f"{name} is not (once) in _lib.EXPORTS"
-        fn = getattr(_lib.lib, name)                 # AttributeError: libgsr.so does not export it
-        assert fn.restype is C.c_int and len(fn.argtypes) == 12, name
+        fn = getattr(_lib.lib, name)
         assert fn.argtypes[6] is C.c_float, name     # median_T
-    assert sorted(_lib.EXPORTS) == sorted(declared)
-    flat = re.sub(r"\s+", " ", text)
+    flat = abi.prototypes()
     tail = (r"const GsrCamera \*cam, const GsrOptions \*opts, int64_t max_pairs, void \*workspace, size_t workspace_bytes, "
             r"float median_T, int32_t \*out_best_id, float \*out_best_w, int32_t \*out_median_id, int32_t \*out_count, void \*stream\);")
     assert re.search(r"int gsr_blend_pick\(int64_t n, " + tail, flat)
@@ -36,17 +26,11 @@ def test_the_two_symbols_are_declared_exported_and_bound():
 
 
 def test_the_abi_version_stays_and_its_comment_names_the_additions():
-    from gsr_amd import _lib
-
-    assert _lib.lib.gsr_version() == 600 and _lib.GSR_VERSION == 600
-    m = re.search(r"#define GSR_VERSION 600 /\*(.*?)\*/", _header(), flags=re.S)
-    assert m and all(name in m.group(1) for name in NEW)
-    assert C.sizeof(_lib.GsrOptions) == 84 and C.sizeof(_lib.GsrStats) == 48 and C.sizeof(_lib.GsrScene) == 64
-    assert C.sizeof(_lib.GsrCamera) == 4 * (16 + 16 + 3 + 6) + 8 and C.sizeof(_lib.GsrDebugOut) == 72
+    abi.assert_version_and_struct_sizes(NEW)
 
 
 def test_the_header_states_what_an_id_is():
-    doc = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int gsr_blend_pick\(", _header(), flags=re.S).group(1)
+    doc = abi.header_comment_before(r"int gsr_blend_pick\(")
     flat = re.sub(r"[\s*]+", " ", doc)
     assert "indices into the caller's scene arrays" in flat
     assert "equal weights the earlier gaussian in draw order wins" in flat
@@ -69,11 +53,7 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
         head = (C.byref(sc),) if entry == "gsr_render_pick" else (0,)
         return fn(*head, cam_p, opts_p, 100, None, 0, median_T, *outs, None)
 
-    def refused(rc, *words):
-        err = _lib.lib.gsr_last_error().decode()
-        assert rc == _lib.GSR_ERR_BAD_ARG, (entry, rc, err)
-        assert all(w in err for w in words), (entry, err)
-        return err
+    refused = abi.refused(entry)
 
     seen = [
         refused(call(None, C.byref(o)), "null", "camera"),
@@ -100,12 +80,8 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
 
 
 def test_the_new_kernel_has_a_translation_unit_of_its_own():
-    csrc = os.path.join(REPO, "torch-gaussian-splatting-rasterizer_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert os.path.exists(os.path.join(csrc, "blend_pick.hip"))
-    assert re.search(r"^OBJS\s*=.*\bblend_pick\.o\b", mk, flags=re.M)
-    rule = re.search(r"^blend_pick\.o:.*\n\t(.*)$", mk, flags=re.M)
-    assert rule and "-fno-slp-vectorize" in rule.group(1)  # the weights' bits depend on it: the flags of blend_features.o
+    abi.assert_own_translation_unit("blend_pick")
+    assert "-fno-slp-vectorize" in abi.makefile_recipe("blend_pick.o")  # the weights' bits depend on it: the flags of blend_features.o
 
 
 def test_file_order_ids_is_the_scenes_permutation():

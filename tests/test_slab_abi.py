@@ -9,31 +9,20 @@ import re
 import pytest
 import torch
 
-from conftest import REPO
+import abi_checks as abi
 
 NEW = ("gsr_blend_slab", "gsr_render_slab")
-
-
-def _header():
-    return open(os.path.join(REPO, "include", "gsr.h")).read()
 
 
 def test_the_two_symbols_are_declared_exported_and_bound():
     from gsr_amd import _lib
 
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", text))
     vp = C.c_void_p
     tail = [C.POINTER(_lib.GsrCamera), C.POINTER(_lib.GsrOptions), C.c_int64, vp, C.c_size_t, vp, C.c_int32, C.c_int64, vp, vp, vp, vp, vp]
-    for name in NEW:
-        assert name in declared, f"{name} is not declared in include/gsr.h"
-        assert _lib.EXPORTS.count(name) == 1, f"{name} is not (once) in _lib.EXPORTS"
-        fn = getattr(_lib.lib, name)                 # AttributeError: libgsr.so does not export it
-        assert fn.restype is C.c_int, name
+    abi.assert_declared_exported_and_bound(NEW)
     assert list(_lib.lib.gsr_blend_slab.argtypes) == [C.POINTER(_lib.GsrScene), C.c_int64] + tail
     assert list(_lib.lib.gsr_render_slab.argtypes) == [C.POINTER(_lib.GsrScene)] + tail
-    assert sorted(_lib.EXPORTS) == sorted(declared)
-    flat = re.sub(r"\s+", " ", text)
+    flat = abi.prototypes()
     rest = (r"const GsrCamera \*cam, const GsrOptions \*opts, int64_t max_pairs, void \*workspace, size_t workspace_bytes, "
             r"const float \*features, int32_t channels, int64_t feature_stride, const float \*depth_near, const float \*depth_far, "
             r"float \*out_map, float \*out_final_T, void \*stream\);")
@@ -42,17 +31,11 @@ def test_the_two_symbols_are_declared_exported_and_bound():
 
 
 def test_the_abi_version_stays_and_its_comment_names_the_additions():
-    from gsr_amd import _lib
-
-    assert _lib.lib.gsr_version() == 600 and _lib.GSR_VERSION == 600
-    m = re.search(r"#define GSR_VERSION 600 /\*(.*?)\*/", _header(), flags=re.S)
-    assert m and all(name in m.group(1) for name in NEW)
-    assert C.sizeof(_lib.GsrOptions) == 84 and C.sizeof(_lib.GsrStats) == 48 and C.sizeof(_lib.GsrScene) == 64
-    assert C.sizeof(_lib.GsrCamera) == 4 * (16 + 16 + 3 + 6) + 8 and C.sizeof(_lib.GsrDebugOut) == 72
+    abi.assert_version_and_struct_sizes(NEW)
 
 
 def test_the_header_states_the_two_compares_the_depth_and_nan():
-    doc = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*int gsr_blend_slab\(", _header(), flags=re.S).group(1)
+    doc = abi.header_comment_before(r"int gsr_blend_slab\(")
     flat = re.sub(r"[\s*]+", " ", doc)
     assert "depth_near[p] <= z_i and z_i < depth_far[p]" in flat
     assert ">= on the near side, < on the far side" in flat
@@ -79,11 +62,7 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
         head = (C.byref(sc),) if entry == "gsr_render_slab" else (C.byref(sc) if scene else None, 0)
         return fn(*head, cam_p, opts_p, 100, None, 0, features, channels, stride, near, far, out, p, None)
 
-    def refused(rc, *words):
-        err = _lib.lib.gsr_last_error().decode()
-        assert rc == _lib.GSR_ERR_BAD_ARG, (entry, rc, err)
-        assert all(w in err for w in words), (entry, err)
-        return err
+    refused = abi.refused(entry)
 
     seen = [
         refused(call(None, C.byref(o)), "null", "camera"),
@@ -115,15 +94,11 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
 
 
 def test_the_new_kernel_has_a_translation_unit_with_the_channel_blends_flags():
-    csrc = os.path.join(REPO, "torch-gaussian-splatting-rasterizer_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert os.path.exists(os.path.join(csrc, "blend_slab.hip"))
-    assert re.search(r"^OBJS\s*=.*\bblend_slab\.o\b", mk, flags=re.M)
-    rule = re.search(r"^blend_slab\.o:.*\n\t(.*)$", mk, flags=re.M)
-    assert rule and "-fno-slp-vectorize" in rule.group(1)  # the maps' bits depend on it
-    chan = re.search(r"^blend_channels\.o:.*\n\t(.*)$", mk, flags=re.M)
-    assert rule.group(1) == chan.group(1)
-    src = open(os.path.join(csrc, "blend_slab.hip")).read()
+    abi.assert_own_translation_unit("blend_slab")
+    rule, chan = abi.makefile_recipe("blend_slab.o"), abi.makefile_recipe("blend_channels.o")
+    assert "-fno-slp-vectorize" in rule  # the maps' bits depend on it
+    assert rule == chan
+    src = open(os.path.join(abi.CSRC, "blend_slab.hip")).read()
     for width in (4, 8, 16):
         assert re.search(rf"launch_width<{width}>\(", src), width
 

@@ -2,34 +2,24 @@
 argument checks run before any HIP call; the kernel has a translation unit with the blend's flags; and the two host-side pieces
 of the Python surface (renderer.topk_composite, renderer.file_order_ids on [H,W,k] lists) do what they say on CPU tensors."""
 import ctypes as C
-import os
 import re
 
 import pytest
 import torch
 
-from conftest import REPO
+import abi_checks as abi
 
 NEW = ("gsr_blend_topk", "gsr_render_topk")
-
-
-def _header():
-    return open(os.path.join(REPO, "include", "gsr.h")).read()
 
 
 def test_the_two_symbols_are_declared_exported_and_bound():
     from gsr_amd import _lib
 
-    text = re.sub(r"/\*.*?\*/", "", _header(), flags=re.S)
-    declared = set(re.findall(r"\b(gsr_[a-z0-9_]+)\s*\(", text))
+    abi.assert_declared_exported_and_bound(NEW, 12)
     for name in NEW:
-        assert name in declared, f"{name} is not declared in include/gsr.h"
-        assert _lib.EXPORTS.count(name) == 1, f"{name} is not (once) in _lib.EXPORTS"
-        fn = getattr(_lib.lib, name)                 # AttributeError: libgsr.so does not export it
-        assert fn.restype is C.c_int and len(fn.argtypes) == 12, name
+        fn = getattr(_lib.lib, name)
         assert fn.argtypes[6] is C.c_int32 and fn.argtypes[7] is C.c_int32, name  # k, select
-    assert sorted(_lib.EXPORTS) == sorted(declared)
-    flat = re.sub(r"\s+", " ", text)
+    text, flat = abi.header_code(), abi.prototypes()
     tail = (r"const GsrCamera \*cam, const GsrOptions \*opts, int64_t max_pairs, void \*workspace, size_t workspace_bytes, "
             r"int32_t k, int32_t select, int32_t \*out_ids, float \*out_weights, float \*out_final_T, void \*stream\);")
     assert re.search(r"int gsr_blend_topk\(int64_t n, " + tail, flat)
@@ -40,17 +30,11 @@ def test_the_two_symbols_are_declared_exported_and_bound():
 
 
 def test_the_abi_version_stays_and_its_comment_names_the_additions():
-    from gsr_amd import _lib
-
-    assert _lib.lib.gsr_version() == 600 and _lib.GSR_VERSION == 600
-    m = re.search(r"#define GSR_VERSION 600 /\*(.*?)\*/", _header(), flags=re.S)
-    assert m and all(name in m.group(1) for name in NEW)
-    assert C.sizeof(_lib.GsrOptions) == 84 and C.sizeof(_lib.GsrStats) == 48 and C.sizeof(_lib.GsrScene) == 64
-    assert C.sizeof(_lib.GsrCamera) == 4 * (16 + 16 + 3 + 6) + 8 and C.sizeof(_lib.GsrDebugOut) == 72
+    abi.assert_version_and_struct_sizes(NEW)
 
 
 def test_the_header_states_the_order_of_the_slots_and_what_an_id_is():
-    doc = re.search(r"/\*((?:(?!\*/).)*?)\*/\s*#define GSR_MAX_TOPK", _header(), flags=re.S).group(1)
+    doc = abi.header_comment_before(r"#define GSR_MAX_TOPK")
     flat = re.sub(r"[\s*]+", " ", doc)
     assert "indices into the caller's scene arrays" in flat
     assert "equal weights the earlier gaussian in draw order comes first" in flat
@@ -75,11 +59,7 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
         head = (C.byref(sc),) if entry == "gsr_render_topk" else (0,)
         return fn(*head, cam_p, opts_p, 100, None, 0, k, select, *outs, None)
 
-    def refused(rc, *words):
-        err = _lib.lib.gsr_last_error().decode()
-        assert rc == _lib.GSR_ERR_BAD_ARG, (entry, rc, err)
-        assert all(w in err for w in words), (entry, err)
-        return err
+    refused = abi.refused(entry)
 
     seen = [
         refused(call(None, C.byref(o)), "null", "camera"),
@@ -109,14 +89,10 @@ def test_bad_arguments_are_refused_without_touching_a_gpu(entry):
 
 
 def test_the_new_kernel_has_a_translation_unit_of_its_own():
-    csrc = os.path.join(REPO, "torch-gaussian-splatting-rasterizer_amd", "csrc")
-    mk = open(os.path.join(csrc, "Makefile")).read()
-    assert os.path.exists(os.path.join(csrc, "blend_topk.hip"))
-    assert re.search(r"^OBJS\s*=.*\bblend_topk\.o\b", mk, flags=re.M)
-    rule = re.search(r"^blend_topk\.o:.*\n\t(.*)$", mk, flags=re.M)
-    assert rule and "-fno-slp-vectorize" in rule.group(1)  # the weights' bits depend on it: the flags of blend_pick.o
-    pick = re.search(r"^blend_pick\.o:.*\n\t(.*)$", mk, flags=re.M)
-    assert rule.group(1) == pick.group(1)
+    abi.assert_own_translation_unit("blend_topk")
+    rule, pick = abi.makefile_recipe("blend_topk.o"), abi.makefile_recipe("blend_pick.o")
+    assert "-fno-slp-vectorize" in rule  # the weights' bits depend on it: the flags of blend_pick.o
+    assert rule == pick
 
 
 def test_render_topk_refuses_a_bad_k_or_select_before_anything_else():

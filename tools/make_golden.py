@@ -342,12 +342,13 @@ def make_f4(ref, out_dir):
 def make_f5(ref, out_dir):
     """deep stacks: the fuzz case that needed the campaign's looser per-pixel threshold (tools/fuzz_parity.py, case-seed
     2519059510838425248: 45 918 gaussians with scales blown up e-fold on a 15x360 frame, hundreds of semi-transparent layers
-    per pixel).  The scene is rebuilt from the seed by fuzz_parity.build_case; only the reference's frame is stored."""
+    per pixel).  The scene is rebuilt from the seed by fuzz_scene.build_case (= fuzz_parity.build_case); only the reference's
+    frame is stored."""
     sys.path.insert(0, os.path.join(REPO, "tools"))
-    import fuzz_parity
+    from fuzz_scene import build_case
 
     case_seed, max_n = 2519059510838425248, 60000
-    c = fuzz_parity.build_case(case_seed, max_n)
+    c = build_case(case_seed, max_n)
     W, H, pose = c["W"], c["H"], c["pose"]
     _, _, fx_full, fy_full, cam_w, cam_h, _, _ = c["args"]
     cols = c["cols"]
