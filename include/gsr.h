@@ -32,7 +32,9 @@ extern "C" {
                             gsr_render_pick — per-pixel ids: the gaussian of largest weight, the one at which T crosses a threshold, the contributor count; gsr_blend_topk /
                             gsr_render_topk + GSR_MAX_TOPK — per-pixel contributor lists: the k heaviest or the k nearest gaussians of a pixel with their weights; gsr_blend_slab /
                             gsr_render_slab — gsr_blend_channels between two per-pixel depth limits: a depth test against a z-buffer, section planes, depth layers; gsr_blend_gaussian_stats /
-                            gsr_render_gaussian_stats — per-gaussian statistics of a view: the sum and the maximum of a gaussian's weights and the number of pixels it reaches, optionally under a pixel mask): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            gsr_render_gaussian_stats — per-gaussian statistics of a view: the sum and the maximum of a gaussian's weights and the number of pixels it reaches, optionally under a pixel mask; gsr_lists_views /
+                            gsr_blend_channels_views / gsr_blend_channels_backward_views / gsr_blend_gaussian_stats_views / gsr_render_channels_batch — feature maps, their gradient and the
+                            statistics for several views per launch sequence, with view_hits, the exact number of views that reach a gaussian): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -500,6 +502,67 @@ int gsr_render_batch(const GsrScene *scene, const GsrCamera *cams /* [host] */, 
 int gsr_render_batch_slots(const GsrScene *scene, const GsrCamera *cams /* [host] */, int32_t n_cams, const GsrOptions *opts,
                            int64_t max_pairs, void *const *workspaces /* [host] n_slots device pointers */, size_t workspace_bytes,
                            void *const *streams /* [host] n_slots streams */, int32_t n_slots, void *out_images, int64_t frame_stride);
+
+/* Feature maps, their gradient and the per-gaussian statistics for SEVERAL VIEWS PER LAUNCH SEQUENCE (no reference counterpart):
+ * what gsr_render_batch does for the colour frame, for gsr_blend_channels, gsr_blend_channels_backward and gsr_blend_gaussian_stats.
+ * "Views" are n_views <= GSR_MAX_BATCH_VIEWS cameras cams[n_views] [host] of one frame size; view v works in slice v of the workspace
+ * (workspace + v * S, S = gsr_workspace_bytes(n, width, height, max_pairs)), exactly as in gsr_render_batch, and every kernel of the
+ * sequence is launched once for all of them.  Every view's map, final T, weights and per-slice GsrStats (gsr_read_stats on slice v)
+ * are those of the single-view entry point under the same options, bit for bit.  Honoured and ignored options are
+ * gsr_blend_channels'; tile-row shards with output_layout = 2 are honoured (a view's plane is then its strip), output_layout = 1 is
+ * refused.
+ *
+ * gsr_lists_views: stages 1-2 (gsr_preprocess as with colour_stage = 0, then gsr_bin_sort) for the n_views cameras in ONE launch
+ * sequence: the tile lists the three gsr_blend_*_views calls below walk.  opts->keep_flags is honoured for every slice.
+ * GSR_ERR_WORKSPACE if the workspace holds fewer than n_views slices.
+ *
+ * The three blends run over the lists in slices 0 .. n_views - 1, as made by ONE gsr_lists_views call with the same cameras, options
+ * and max_pairs (any number of blends per such call).  Strides between the views' planes are in ELEMENTS (floats; bytes for the
+ * masks), at least a plane, and only read when n_views > 1:
+ *   gsr_blend_channels_views           view v writes out_maps + v * map_stride ([.., channels], as gsr_blend_channels lays it out) and,
+ *                                      if out_final_T is not NULL, out_final_T + v * T_stride; all views read the one `features`.
+ *   gsr_blend_channels_backward_views  view v reads grad_maps + v * map_stride; ALL views add into the one grad_features:
+ *                                      grad_features[i][c] += sum_v sum_p w_v,i(p) grad_maps[v][p][c].  Float atomic adds: the value
+ *                                      depends on the order the adds arrive in, as for a single view.
+ *   gsr_blend_gaussian_stats_views     view v reads pixel_masks + v * mask_stride (NULL: every drawn pixel of every view counts); all
+ *                                      views accumulate into weight_sum / weight_max / pixels as gsr_blend_gaussian_stats does (sum of
+ *                                      sums, max of maxima, sum of counts: weight_max and pixels stay exact and reproducible to the bit,
+ *                                      weight_sum depends on the order the adds arrive in), and
+ *                                        view_hits[i] += #{views v of this call : gaussian i has w > 0 in a counted pixel of v}
+ *                                      — the number of views whose exact visible set holds the gaussian.  It is exact and does not
+ *                                      depend on the order anything arrives in: the first flush of view v that reaches gaussian i
+ *                                      sets bit v of view_bits[i] with an atomic OR and adds 1 only if the bit was clear.  view_bits is
+ *                                      an [n] uint32 scratch of the caller's, required exactly when view_hits is given; the library
+ *                                      clears it on the caller's stream before the blend, so its contents are ignored on entry and
+ *                                      undefined on return.  Any of the four outputs may be NULL, not all four; an absent view_hits
+ *                                      costs nothing.
+ * gsr_render_channels_batch: any number n_cams of cameras, in groups of K = min(slices the workspace holds, GSR_MAX_BATCH_VIEWS,
+ * opts->batch_views if set, n_cams) views as gsr_render_batch loops: per group gsr_lists_views + gsr_blend_channels_views, view i in
+ * slice i % K, its map at out_maps + i * map_stride and its final T at out_final_T + i * T_stride; the slices' counters are
+ * gsr_render_batch's (the LAST view rendered there, overflows sticky).  The accumulating calls have no such one-shot form: a caller
+ * that adds into its buffers checks the lists first (gsr_read_stats on every slice, re-run gsr_lists_views until complete) and only
+ * then blends, so that an incomplete walk never reaches them.
+ * GSR_ERR_BAD_ARG, before any HIP call or look at the workspace and each with its own words: null cams, null options, n_views < 1 or
+ * > GSR_MAX_BATCH_VIEWS (n_cams < 0), cameras of different frame sizes, output_layout = 1, every refusal of the single-view function,
+ * a stride smaller than a view's map or plane (n_views > 1), all four statistics outputs NULL, view_hits without view_bits or
+ * view_bits without view_hits. */
+int gsr_lists_views(const GsrScene *scene, const GsrCamera *cams /* [host] */, int32_t n_views, const GsrOptions *opts,
+                    int64_t max_pairs, void *workspace, size_t workspace_bytes, void *stream);
+int gsr_blend_channels_views(int64_t n, const GsrCamera *cams /* [host] */, int32_t n_views, const GsrOptions *opts, int64_t max_pairs,
+                             void *workspace, size_t workspace_bytes, const float *features, int32_t channels,
+                             int64_t feature_stride, float *out_maps, int64_t map_stride, float *out_final_T /* may be NULL */,
+                             int64_t T_stride, void *stream);
+int gsr_blend_channels_backward_views(int64_t n, const GsrCamera *cams /* [host] */, int32_t n_views, const GsrOptions *opts,
+                                      int64_t max_pairs, void *workspace, size_t workspace_bytes, const float *grad_maps,
+                                      int64_t map_stride, int32_t channels, float *grad_features, int64_t grad_stride, void *stream);
+int gsr_blend_gaussian_stats_views(int64_t n, const GsrCamera *cams /* [host] */, int32_t n_views, const GsrOptions *opts,
+                                   int64_t max_pairs, void *workspace, size_t workspace_bytes,
+                                   const uint8_t *pixel_masks /* may be NULL */, int64_t mask_stride, float *weight_sum,
+                                   float *weight_max, uint32_t *pixels, uint32_t *view_hits, uint32_t *view_bits, void *stream);
+int gsr_render_channels_batch(const GsrScene *scene, const GsrCamera *cams /* [host] */, int32_t n_cams, const GsrOptions *opts,
+                              int64_t max_pairs, void *workspace, size_t workspace_bytes, const float *features, int32_t channels,
+                              int64_t feature_stride, float *out_maps, int64_t map_stride, float *out_final_T /* may be NULL */,
+                              int64_t T_stride, void *stream);
 
 /* Totals the blend's per-workgroup counters (one small kernel on `stream`: wave_entries / fetched_entries describe the
  * LAST gsr_blend of the frame, 0 if none ran; the two totals are written into the workspace's counter block, no frame

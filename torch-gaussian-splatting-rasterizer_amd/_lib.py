@@ -135,6 +135,8 @@ EXPORTS = [
     "gsr_blend_topk", "gsr_render_topk",
     "gsr_blend_slab", "gsr_render_slab",
     "gsr_blend_gaussian_stats", "gsr_render_gaussian_stats",
+    "gsr_lists_views", "gsr_blend_channels_views", "gsr_blend_channels_backward_views", "gsr_blend_gaussian_stats_views",
+    "gsr_render_channels_batch",
 ]
 
 
@@ -170,6 +172,12 @@ def _load() -> C.CDLL:
         getattr(L, "gsr_blend_" + name).argtypes = lists + tail   # the blend alone, over lists already made ...
         getattr(L, "gsr_render_" + name).argtypes = view + tail   # ... and stages 1-3 in one call: the same tail
     L.gsr_render_batch.argtypes = [scene_p, cam_p, i32, opts_p, i64, vp, sz, vp, i64, vp]
+    views = [cam_p, i32, opts_p, i64, vp, sz]        # gsr_*_views: cameras [host], how many, options, max_pairs, workspace, its bytes
+    L.gsr_lists_views.argtypes = [scene_p] + views + [vp]
+    L.gsr_blend_channels_views.argtypes = [i64] + views + [vp, i32, i64, vp, i64, vp, i64, vp]
+    L.gsr_blend_channels_backward_views.argtypes = [i64] + views + [vp, i64, i32, vp, i64, vp]
+    L.gsr_blend_gaussian_stats_views.argtypes = [i64] + views + [vp, i64, vp, vp, vp, vp, vp, vp]
+    L.gsr_render_channels_batch.argtypes = [scene_p] + views + [vp, i32, i64, vp, i64, vp, i64, vp]
     L.gsr_render_batch_slots.argtypes = [scene_p, cam_p, i32, opts_p, i64, C.POINTER(vp), sz, C.POINTER(vp), i32, vp, i64]
     L.gsr_read_stats.argtypes = [vp, sz, C.POINTER(GsrStats), vp]
     L.gsr_scene_order_bytes.argtypes = [i64, C.POINTER(sz)]

@@ -595,6 +595,13 @@ int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, co
         });
 }
 
+static int check_gaussian_stats_options(const GsrOptions *opts)
+{
+    if (opts->output_dtype == 1) { set_error("gaussian statistics are float32 / uint32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("the weights are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
 // What gsr_blend_gaussian_stats / gsr_render_gaussian_stats refuse before anything else (and before any HIP call)
 static int check_gaussian_stats(const GsrCamera *cam, const GsrOptions *opts, const float *weight_sum, const float *weight_max,
                                 const uint32_t *pixels)
@@ -602,9 +609,7 @@ static int check_gaussian_stats(const GsrCamera *cam, const GsrOptions *opts, co
     if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
     if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
     if (!weight_sum && !weight_max && !pixels) { set_error("null statistics outputs: all three"); return GSR_ERR_BAD_ARG; }
-    if (opts->output_dtype == 1) { set_error("gaussian statistics are float32 / uint32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    if (opts->accum_dtype == 1) { set_error("the weights are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
+    return check_gaussian_stats_options(opts);
 }
 
 int gsr_blend_gaussian_stats(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
@@ -778,6 +783,198 @@ int gsr_render_batch_slots(const GsrScene *scene, const GsrCamera *cams, int32_t
         // a slot's first group clears its slices' control blocks, its later groups keep the batch-sticky overflow words
         rc = render_views(scene, &cams[i], k, opts, max_pairs, workspaces[slot], workspace_bytes, static_cast<char *>(out_images) + (size_t)i * fbytes,
                           fbytes, nullptr, streams[slot], g >= n_slots);
+        if (rc) return rc;
+    }
+    return GSR_OK;
+}
+
+// ---- feature maps, their gradient and view statistics for several views per launch sequence ---------------------------------------
+// What the gsr_*_views entries refuse about their views before anything else (and before any HIP call): view v works in slice v
+static int check_views(const GsrCamera *cams, int32_t n_views, const GsrOptions *opts)
+{
+    if (!cams) { set_error("null cameras"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    if (n_views < 1 || n_views > MAX_VIEWS) { set_error("bad view count %d (1 .. %d)", (int)n_views, MAX_VIEWS); return GSR_ERR_BAD_ARG; }
+    for (int32_t i = 1; i < n_views; ++i)
+        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) {
+            set_error("views of a launch sequence must share one frame size"); return GSR_ERR_BAD_ARG;
+        }
+    if (opts->output_layout == 1) { set_error("views of a launch sequence are [H,W] maps or shard strips: output_layout = 1 is not supported"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+// Pixels of one view's plane: the frame, or (output_layout = 2) the strip of the shard's tile rows.  0 for sizes check_frame refuses
+static int64_t view_plane_pixels(const GsrCamera &cam, const GsrOptions &opts)
+{
+    if (cam.width <= 0 || cam.height <= 0) return 0;
+    int64_t rows_px = cam.height;
+    if (opts.output_layout == 2 && opts.tile_row_step >= 0 && opts.tile_row_begin >= 0) {
+        const int tiles_y = (cam.height + GSR_TILE - 1) / GSR_TILE;
+        rows_px = (int64_t)row_shard_of(opts).rows_before(tiles_y) * GSR_TILE;
+    }
+    return (int64_t)cam.width * rows_px;
+}
+
+static int check_view_stride(const char *name, int64_t stride, int64_t need, int32_t n_views, const char *what)
+{
+    if (n_views > 1 && stride < need) { set_error("bad %s %lld: smaller than %s (%lld)", name, (long long)stride, what, (long long)need); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+// The frame's checks for n_views views in slices 0 .. n_views - 1 of the workspace; *ws describes them (check_frame's, with the views)
+static int check_view_slices(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, Workspace *ws)
+{
+    const int rc = check_frame(n, &cams[0], opts, max_pairs, workspace, workspace_bytes, ws);
+    if (rc) return rc;
+    if (workspace_bytes / ws->bytes < (size_t)n_views) {
+        set_error("workspace too small for %d views per launch: %zu bytes given, %zu needed", (int)n_views, workspace_bytes, ws->bytes * (size_t)n_views);
+        return GSR_ERR_WORKSPACE;
+    }
+    if (n_views > 1) {
+        ws->views = n_views;
+        ws->view_stride = ws->bytes;
+    }
+    return GSR_OK;
+}
+
+// Stages 1-2 of gsr_lists_views; keep_batch_words: a later group of gsr_render_channels_batch
+static int lists_views(const GsrScene *scene, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs,
+                       void *workspace, size_t workspace_bytes, void *stream, bool keep_batch_words)
+{
+    Workspace ws;
+    int rc = check_view_slices(scene->n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    GsrOptions o = *opts;
+    o.colour_stage = 0;
+    const FramePlan plan = plan_frame(ws, o);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    rc = launch_preprocess(*scene, cams, o, ws, plan, nullptr, reset_words_of(&o, keep_batch_words), s);
+    if (rc) return rc;
+    return bin_sort_impl(&o, ws, plan, s);
+}
+
+int gsr_lists_views(const GsrScene *scene, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs,
+                    void *workspace, size_t workspace_bytes, void *stream)
+{
+    int rc = check_scene(scene);
+    if (rc) return rc;
+    rc = check_views(cams, n_views, opts);
+    if (rc) return rc;
+    return lists_views(scene, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream, false);
+}
+
+// gsr_blend_X_views behind its own argument checks: the frame's checks for the slices, the plan, and launch(cam, opts, ws, plan, s)
+extern "C++" {
+template <class Launch>
+static int run_on_view_lists(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, void *stream, Launch launch)
+{
+    Workspace ws;
+    const int rc = check_view_slices(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, &ws);
+    if (rc) return rc;
+    return launch(cams[0], *opts, ws, plan_frame(ws, *opts), static_cast<hipStream_t>(stream));
+}
+}  // extern "C++"
+
+static int check_channels_views(const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, const float *features, int32_t channels,
+                                int64_t feature_stride, const float *out_maps, int64_t map_stride, const float *out_final_T, int64_t T_stride)
+{
+    int rc = check_views(cams, n_views, opts);
+    if (rc) return rc;
+    rc = check_channels(&cams[0], opts, features, channels, feature_stride, out_maps);
+    if (rc) return rc;
+    const int64_t plane = view_plane_pixels(cams[0], *opts);
+    rc = check_view_stride("map_stride", map_stride, plane * channels, n_views, "a view's map");
+    if (rc) return rc;
+    return out_final_T ? check_view_stride("T_stride", T_stride, plane, n_views, "a view's final-T plane") : GSR_OK;
+}
+
+int gsr_blend_channels_views(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, float *out_maps,
+                             int64_t map_stride, float *out_final_T, int64_t T_stride, void *stream)
+{
+    const int rc = check_channels_views(cams, n_views, opts, features, channels, feature_stride, out_maps, map_stride, out_final_T, T_stride);
+    if (rc) return rc;
+    return run_on_view_lists(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_channels(c, o, ws, plan, features, channels, feature_stride, out_maps, out_final_T, s, map_stride, T_stride);
+        });
+}
+
+int gsr_blend_channels_backward_views(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs,
+                                      void *workspace, size_t workspace_bytes, const float *grad_maps, int64_t map_stride, int32_t channels,
+                                      float *grad_features, int64_t grad_stride, void *stream)
+{
+    int rc = check_views(cams, n_views, opts);
+    if (rc) return rc;
+    rc = check_channels_backward(&cams[0], opts, grad_maps, channels, grad_features, grad_stride);
+    if (rc) return rc;
+    rc = check_view_stride("map_stride", map_stride, view_plane_pixels(cams[0], *opts) * channels, n_views, "a view's gradient map");
+    if (rc) return rc;
+    return run_on_view_lists(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_channels_backward(c, o, ws, plan, grad_maps, channels, grad_features, grad_stride, s, map_stride);
+        });
+}
+
+int gsr_blend_gaussian_stats_views(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs,
+                                   void *workspace, size_t workspace_bytes, const uint8_t *pixel_masks, int64_t mask_stride,
+                                   float *weight_sum, float *weight_max, uint32_t *pixels, uint32_t *view_hits, uint32_t *view_bits,
+                                   void *stream)
+{
+    int rc = check_views(cams, n_views, opts);
+    if (rc) return rc;
+    if (!weight_sum && !weight_max && !pixels && !view_hits) { set_error("null statistics outputs: all four"); return GSR_ERR_BAD_ARG; }
+    if (view_hits && !view_bits) { set_error("view_hits needs the view_bits scratch"); return GSR_ERR_BAD_ARG; }
+    if (!view_hits && view_bits) { set_error("a view_bits scratch without view_hits"); return GSR_ERR_BAD_ARG; }
+    rc = check_gaussian_stats_options(opts);
+    if (rc) return rc;
+    if (pixel_masks) {
+        rc = check_view_stride("mask_stride", mask_stride, view_plane_pixels(cams[0], *opts), n_views, "a view's mask plane");
+        if (rc) return rc;
+    }
+    return run_on_view_lists(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) -> int {
+            // the scratch is this launch sequence's: bit v = view v has counted the gaussian
+            if (view_hits && ws.n > 0) GSR_HIP(hipMemsetAsync(view_bits, 0, sizeof(uint32_t) * (size_t)ws.n, s));
+            return launch_blend_gstats(c, o, ws, plan, pixel_masks, weight_sum, weight_max, pixels, s, mask_stride, view_hits, view_bits);
+        });
+}
+
+int gsr_render_channels_batch(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs,
+                              void *workspace, size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride,
+                              float *out_maps, int64_t map_stride, float *out_final_T, int64_t T_stride, void *stream)
+{
+    int rc = check_scene(scene);
+    if (rc) return rc;
+    if (!cams) { set_error("null cameras"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    if (n_cams < 0) { set_error("bad camera count %d", (int)n_cams); return GSR_ERR_BAD_ARG; }
+    if (n_cams == 0) return GSR_OK;
+    for (int32_t i = 1; i < n_cams; ++i)  // every camera against the first, whatever the group it falls into
+        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) {
+            set_error("views of a launch sequence must share one frame size"); return GSR_ERR_BAD_ARG;
+        }
+    // (a group's own checks, on a group as large as any: the strides are asked for whenever there is a second camera)
+    rc = check_channels_views(cams, std::min<int32_t>(n_cams, 2), opts, features, channels, feature_stride, out_maps, map_stride, out_final_T, T_stride);
+    if (rc) return rc;
+    rc = check_sizes(scene->n, cams[0].width, cams[0].height, max_pairs);
+    if (rc) return rc;
+    const int K = views_per_launch(scene, &cams[0], opts, max_pairs, workspace_bytes, n_cams);
+    for (int32_t i = 0; i < n_cams; i += std::max(K, 1)) {
+        // K = 0: the workspace does not hold one view — the group's checks report it.  A slice's first view clears its whole control
+        // block, its later views (i >= K) keep the batch-sticky overflow words, as in gsr_render_batch
+        const int k = std::max(1, std::min<int32_t>(K, n_cams - i));
+        rc = lists_views(scene, &cams[i], k, opts, max_pairs, workspace, workspace_bytes, stream, i > 0);
+        if (rc) return rc;
+        float *maps = out_maps + (size_t)i * (size_t)map_stride, *Ts = out_final_T ? out_final_T + (size_t)i * (size_t)T_stride : nullptr;
+        GsrOptions o = *opts;
+        o.colour_stage = 0;
+        rc = run_on_view_lists(scene->n, &cams[i], k, &o, max_pairs, workspace, workspace_bytes, stream,
+            [&](const GsrCamera &c, const GsrOptions &oo, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+                return launch_blend_channels(c, oo, ws, plan, features, channels, feature_stride, maps, Ts, s, map_stride, T_stride);
+            });
         if (rc) return rc;
     }
     return GSR_OK;

@@ -19,6 +19,8 @@
 //   ring [1024] + wc [8] + done: tile_list_next's
 // = 9216 + 1024 * CH + 4132 B: 21.5 KB at CH = 8 (7 workgroups per CU), 29.7 KB at CH = 16 (5).
 // The record's colour words are neither read nor written and tile_work is only read, as in blend_features.hip.
+// Several views per launch (gridDim.y, gsr_blend_channels_views): view blockIdx.y walks its slice of the workspace and writes its own
+// map (blend_args_of_view: out_view_stride) and its own final-T plane (ChannelArgs.T_view_stride); all views read one features array.
 #include "blend_weight_walk.h"
 
 namespace gsr {
@@ -96,26 +98,32 @@ __global__ __launch_bounds__(256, ChannelWaves<CH>::value) void blend_channels_k
         const bool drawn = t.px < a.xlim && t.py < a.ylim;  // Q1: last column / row stay zero, T stays 1
         const size_t pix = frame_pixel(a, t.ty, t.px, t.py);
         store_channel_pixel<Q>(static_cast<float *>(a.out) + pix * (size_t)ch.channels + ch.c0, acc, nch, ch.vec_out, drawn);
-        if (a.out_T) a.out_T[pix] = drawn ? T : 1.0f;
+        // (view blockIdx.y's plane: the map's offset is blend_args_of_view's, through out_view_stride)
+        if (a.out_T) a.out_T[(size_t)blockIdx.y * (size_t)ch.T_view_stride + pix] = drawn ? T : 1.0f;
     }
 }
 
 template <int CH>
-static void launch_width(int slots, const BlendArgs &a, const ChannelArgs &ch, hipStream_t s)
+static void launch_width(int slots, int views, const BlendArgs &a, const ChannelArgs &ch, hipStream_t s)
 {
-    hipLaunchKernelGGL(blend_channels_kernel<CH>, dim3((unsigned)slots), dim3(256), 0, s, a, ch);
+    hipLaunchKernelGGL(blend_channels_kernel<CH>, dim3((unsigned)slots, (unsigned)views), dim3(256), 0, s, a, ch);
 }
 
 int launch_blend_channels(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *features,
-                          int channels, int64_t stride, float *out_map, float *out_T, hipStream_t s)
+                          int channels, int64_t stride, float *out_map, float *out_T, hipStream_t s, int64_t map_view_stride,
+                          int64_t T_view_stride)
 {
     BlendArgs a;
     int slots;
-    const int rc = weight_walk_begin("feature maps", cam, opts, ws, plan, out_map, out_T, s, &a, &slots);
+    const int rc = weight_walk_begin("feature maps", cam, opts, ws, plan, out_map, out_T, s, &a, &slots, WalkViews::Several,
+                                     (size_t)map_view_stride * sizeof(float));
     if (rc || !slots) return rc;
-    return for_channel_groups(features, stride, out_map, channels, 8, [&](const ChannelArgs &ch, int width) -> int {
-        if (width == 16) launch_width<16>(slots, a, ch, s);
-        else launch_width<8>(slots, a, ch, s);
+    return for_channel_groups(features, stride, out_map, channels, 8, [&](const ChannelArgs &group, int width) -> int {
+        ChannelArgs ch = group;
+        ch.T_view_stride = T_view_stride;
+        if (ws.views > 1 && map_view_stride % 4 != 0) ch.vec_out = 0;  // a later view's pixels need not start on 16 bytes
+        if (width == 16) launch_width<16>(slots, ws.views, a, ch, s);
+        else launch_width<8>(slots, ws.views, a, ch, s);
         GSR_HIP(hipGetLastError());
         a.out_T = nullptr;  // every group ends with the same T: the first one's store is enough
         return GSR_OK;

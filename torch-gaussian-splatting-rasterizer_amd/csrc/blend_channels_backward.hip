@@ -26,6 +26,8 @@
 //   ring [1024] + wc [8] + done: tile_list_next's
 // = 10240 + 1024 * CH + 4132 B: 22.0 KB at CH = 8 (7 workgroups per CU), 30.0 KB at CH = 16 (5).
 // Float atomic sums depend on the order the adds arrive in: two runs of the same input may differ in the last bits.
+// Several views per launch (gridDim.y, gsr_blend_channels_backward_views): view blockIdx.y walks its slice of the workspace and reads
+// its own gradient map (ChannelGradArgs.map_view_stride); all views add into the one grad_features with the same atomics.
 #include "blend_weight_walk.h"
 
 namespace gsr {
@@ -38,6 +40,7 @@ struct ChannelGradArgs {
     int nch;                // this walk handles channels c0 .. c0 + nch - 1, 1 <= nch <= CH
     int pad_shift;          // log2 of nch rounded up to a power of two: the flush's lanes per row
     int vec_map;            // 16-byte loads of the pixels are aligned (decided on the host)
+    int64_t map_view_stride;  // several views per launch: floats between the views' gradient maps (all add into grad_features)
 };
 
 constexpr uint32_t ENTRY_TOUCHED = 1u << 31;  // ids are below 2^28 (LIST_ID_MASK)
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(256, ChannelGradWaves<CH>::value) void blend_channe
 #pragma unroll
     for (int c = 0; c < CH; ++c) g[c] = 0.0f;
     if (t.px < a.W && t.py < a.H && t.px < a.xlim && t.py < a.ylim) {
-        const float *gp = ch.grad_map + frame_pixel(a, t.ty, t.px, t.py) * (size_t)ch.channels;
+        const float *gp = ch.grad_map + (size_t)blockIdx.y * (size_t)ch.map_view_stride + frame_pixel(a, t.ty, t.px, t.py) * (size_t)ch.channels;
         const ChannelRow<Q> row = load_channel_row<Q>(gp, nch, ch.vec_map);
 #pragma unroll
         for (int q = 0; q < Q; ++q) { g[4 * q] = row.v[q].x; g[4 * q + 1] = row.v[q].y; g[4 * q + 2] = row.v[q].z; g[4 * q + 3] = row.v[q].w; }
@@ -191,18 +194,19 @@ __global__ __launch_bounds__(256, ChannelGradWaves<CH>::value) void blend_channe
 }
 
 template <int CH>
-static void launch_width(int slots, const BlendArgs &a, const ChannelGradArgs &ch, hipStream_t s)
+static void launch_width(int slots, int views, const BlendArgs &a, const ChannelGradArgs &ch, hipStream_t s)
 {
-    hipLaunchKernelGGL(blend_channels_backward_kernel<CH>, dim3((unsigned)slots), dim3(256), 0, s, a, ch);
+    hipLaunchKernelGGL(blend_channels_backward_kernel<CH>, dim3((unsigned)slots, (unsigned)views), dim3(256), 0, s, a, ch);
 }
 
 // for_channel_groups with the gradient map in the place of the forward's map (vec_map is the forward's vec_out)
 int launch_blend_channels_backward(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
-                                   const float *grad_map, int channels, float *grad_features, int64_t stride, hipStream_t s)
+                                   const float *grad_map, int channels, float *grad_features, int64_t stride, hipStream_t s,
+                                   int64_t map_view_stride)
 {
     BlendArgs a;  // no map is written
     int slots;
-    const int rc = weight_walk_begin("feature gradients", cam, opts, ws, plan, nullptr, nullptr, s, &a, &slots);
+    const int rc = weight_walk_begin("feature gradients", cam, opts, ws, plan, nullptr, nullptr, s, &a, &slots, WalkViews::Several);
     if (rc || !slots) return rc;
     return for_channel_groups(grad_features, stride, grad_map, channels, 8, [&](const ChannelArgs &g, int width) -> int {
         ChannelGradArgs ch;
@@ -213,9 +217,10 @@ int launch_blend_channels_backward(const GsrCamera &cam, const GsrOptions &opts,
         ch.nch = g.nch;
         ch.pad_shift = 0;
         while ((1 << ch.pad_shift) < ch.nch) ++ch.pad_shift;
-        ch.vec_map = g.vec_out;
-        if (width == 16) launch_width<16>(slots, a, ch, s);
-        else launch_width<8>(slots, a, ch, s);
+        ch.vec_map = g.vec_out && (ws.views == 1 || map_view_stride % 4 == 0);  // a later view's pixels need not start on 16 bytes
+        ch.map_view_stride = map_view_stride;
+        if (width == 16) launch_width<16>(slots, ws.views, a, ch, s);
+        else launch_width<8>(slots, ws.views, a, ch, s);
         GSR_HIP(hipGetLastError());
         return GSR_OK;
     });

@@ -20,7 +20,7 @@
 //                 arrays with global_atomic_add_f32, global_atomic_umax and global_atomic_add (one dword per row and array: the shape
 //                 of the gradient kernel's one-channel flush) and back to zero.  Unmarked rows cost no atomic;
 //   outputs       WANT (template parameter, bit 0 sum, 1 max, 2 pixels) removes an absent output's chain, LDS atomic and global
-//                 atomic at compile time: seven instantiations;
+//                 atomic at compile time: seven instantiations (each once more with HITS, below);
 //   masked waves  a wave none of whose 64 pixels is counted has finished before its first batch (exact: every w' is 0), and a tile
 //                 whose four waves have stages nothing: a small region of interest costs what it covers.
 //
@@ -33,6 +33,16 @@
 // = 8192 + 1024 + 1024 + 4096 + 4132 B = 18.0 KB: LDS allows 8 workgroups per CU, and so do the registers (launch bound 8).
 // Max and pixels do not depend on the order the atomics arrive in: two runs give the same bits.  The float sums may differ in
 // their last bits.
+//
+// Several views per launch (gridDim.y, gsr_blend_gaussian_stats_views): view blockIdx.y walks its slice of the workspace
+// (blend_args_of_view) and reads its own mask plane; all views flush into the same three arrays with the same atomics.  view_hits[i]
+// += the views that reach gaussian i with w > 0 in a counted pixel: in the flush a marked row also does atomicOr(view_bits + i,
+// 1 << blockIdx.y) and, if the bit was clear in the value that came back, atomicAdd(view_hits + i, 1) — exactly one flush per
+// (gaussian, view) finds it clear, whatever the order.  view_bits is the caller's scratch, cleared by the host before the launch.
+// An absent view_hits is a template bit, HITS, like WANT: without it the flush is the single-view kernel's, instruction for
+// instruction, and so are the registers.
+// Fifteen instantiations: WANT 1 .. 7 with and without HITS, and WANT = 0 with it — view_hits alone.  With gridDim.y == 1 every
+// view offset is zero.
 #include "blend_weight_walk.h"
 
 namespace gsr {
@@ -42,6 +52,10 @@ struct GaussStatsArgs {
     float *weight_sum;     // [n], null unless WANT & 1
     uint32_t *weight_max;  // [n] float bits, null unless WANT & 2
     uint32_t *pixels;      // [n], null unless WANT & 4
+    // several views per launch (gridDim.y): view blockIdx.y reads its own mask plane and all views add into the outputs above
+    int64_t mask_view_stride;  // bytes between the views' mask planes
+    uint32_t *view_hits;   // [n] += the views of this launch that reach the gaussian with w > 0 in a counted pixel; may be null
+    uint32_t *view_bits;   // [n] scratch, cleared by the host before the launch: bit v = view v has been counted in view_hits
 };
 
 constexpr int WANT_SUM = 1, WANT_MAX = 2, WANT_PIXELS = 4;
@@ -85,10 +99,10 @@ __device__ __forceinline__ void gstats_add(float w, bool counted, int lane, uint
     }
 }
 
-template <int WANT>
+template <int WANT, bool HITS>
 __global__ __launch_bounds__(256, 8) void blend_gstats_kernel(BlendArgs args, const GaussStatsArgs gs)
 {
-    static_assert(WANT >= 1 && WANT <= 7, "at least one output");
+    static_assert(WANT >= 0 && WANT <= 7 && (WANT != 0 || HITS), "at least one output; WANT 0: view_hits alone");
     const BlendArgs a = blend_args_of_view(args);
     __shared__ float4 srec[2][256];
     __shared__ uint4 sS[256];
@@ -108,7 +122,7 @@ __global__ __launch_bounds__(256, 8) void blend_gstats_kernel(BlendArgs args, co
     // does this pixel count?  Not where the forward stores 0 (Q1's last column / row) or nothing (outside the frame), nor where the
     // caller's mask says so
     bool counted = t.px < a.W && t.py < a.H && t.px < a.xlim && t.py < a.ylim;
-    if (counted && gs.mask) counted = ldg(gs.mask, frame_pixel(a, t.ty, t.px, t.py)) != 0;
+    if (counted && gs.mask) counted = ldg(gs.mask, (size_t)blockIdx.y * (size_t)gs.mask_view_stride + frame_pixel(a, t.ty, t.px, t.py)) != 0;
     sS[tid] = make_uint4(0u, 0u, 0u, 0u);  // published by the barrier below
 
     float T = 1.0f;
@@ -164,6 +178,10 @@ __global__ __launch_bounds__(256, 8) void blend_gstats_kernel(BlendArgs args, co
                 if (WANT & WANT_SUM) unsafeAtomicAdd(gs.weight_sum + i, __uint_as_float(r.x));
                 if (WANT & WANT_MAX) atomicMax(gs.weight_max + i, r.y);
                 if (WANT & WANT_PIXELS) atomicAdd(gs.pixels + i, r.z);
+                if (HITS) {  // the first flush of this view that reaches gaussian i finds the view's bit clear
+                    const uint32_t bit = 1u << blockIdx.y;
+                    if (!(atomicOr(gs.view_bits + i, bit) & bit)) atomicAdd(gs.view_hits + i, 1u);
+                }
                 sS[tid] = make_uint4(0u, 0u, 0u, 0u);
             }
         }
@@ -172,29 +190,40 @@ __global__ __launch_bounds__(256, 8) void blend_gstats_kernel(BlendArgs args, co
     blend_stats_out<256, false>(a, t, tid, lane, wave, lds, evaluated, fetched, 0u);
 }
 
-template <int WANT>
-static void launch_want(int slots, const BlendArgs &a, const GaussStatsArgs &gs, hipStream_t s)
+template <int WANT, bool HITS>
+static void launch_one(int slots, int views, const BlendArgs &a, const GaussStatsArgs &gs, hipStream_t s)
 {
-    hipLaunchKernelGGL(blend_gstats_kernel<WANT>, dim3((unsigned)slots), dim3(256), 0, s, a, gs);
+    hipLaunchKernelGGL((blend_gstats_kernel<WANT, HITS>), dim3((unsigned)slots, (unsigned)views), dim3(256), 0, s, a, gs);
+}
+
+template <int WANT>
+static void launch_want(int slots, int views, const BlendArgs &a, const GaussStatsArgs &gs, hipStream_t s)
+{
+    if (gs.view_hits) launch_one<WANT, true>(slots, views, a, gs, s);
+    else launch_one<WANT, false>(slots, views, a, gs, s);
 }
 
 int launch_blend_gstats(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const uint8_t *pixel_mask,
-                        float *weight_sum, float *weight_max, uint32_t *pixels, hipStream_t s)
+                        float *weight_sum, float *weight_max, uint32_t *pixels, hipStream_t s, int64_t mask_view_stride,
+                        uint32_t *view_hits, uint32_t *view_bits)
 {
     BlendArgs a;  // no map is written
     int slots;
-    const int rc = weight_walk_begin("gaussian statistics", cam, opts, ws, plan, nullptr, nullptr, s, &a, &slots);
+    const int rc = weight_walk_begin("gaussian statistics", cam, opts, ws, plan, nullptr, nullptr, s, &a, &slots, WalkViews::Several);
     if (rc || !slots) return rc;
-    const GaussStatsArgs gs = {pixel_mask, weight_sum, reinterpret_cast<uint32_t *>(weight_max), pixels};
+    const GaussStatsArgs gs = {pixel_mask, weight_sum, reinterpret_cast<uint32_t *>(weight_max), pixels, mask_view_stride, view_hits, view_bits};
+    const int views = ws.views;
     switch ((weight_sum ? WANT_SUM : 0) | (weight_max ? WANT_MAX : 0) | (pixels ? WANT_PIXELS : 0)) {
-    case 1: launch_want<1>(slots, a, gs, s); break;
-    case 2: launch_want<2>(slots, a, gs, s); break;
-    case 3: launch_want<3>(slots, a, gs, s); break;
-    case 4: launch_want<4>(slots, a, gs, s); break;
-    case 5: launch_want<5>(slots, a, gs, s); break;
-    case 6: launch_want<6>(slots, a, gs, s); break;
-    case 7: launch_want<7>(slots, a, gs, s); break;
-    default: set_error("null statistics outputs: all three"); return GSR_ERR_BAD_ARG;
+    case 1: launch_want<1>(slots, views, a, gs, s); break;
+    case 2: launch_want<2>(slots, views, a, gs, s); break;
+    case 3: launch_want<3>(slots, views, a, gs, s); break;
+    case 4: launch_want<4>(slots, views, a, gs, s); break;
+    case 5: launch_want<5>(slots, views, a, gs, s); break;
+    case 6: launch_want<6>(slots, views, a, gs, s); break;
+    case 7: launch_want<7>(slots, views, a, gs, s); break;
+    default:
+        if (!view_hits) { set_error("null statistics outputs: all three"); return GSR_ERR_BAD_ARG; }
+        launch_one<0, true>(slots, views, a, gs, s);
     }
     GSR_HIP(hipGetLastError());
     return GSR_OK;

@@ -6,7 +6,8 @@
 //   - next_batch_planes:  next_batch with the kernel's own third planes;
 //   - walk_survivors / walk_survivors_single and keep_b128: a chunk's survivors in draw order;
 //   - ChannelArgs, load_channel_row, store_channel_pixel, blend_channels_add, dpp_add: rows of channels;
-//   - host: weight_walk_begin (the launch prelude), for_channel_groups (a map's channels in walks of 16 / 8 / 4).
+//   - host: weight_walk_begin (the launch prelude; WalkViews: whether the launcher's kernel takes several views per launch),
+//     for_channel_groups (a map's channels in walks of 16 / 8 / 4).
 // The workgroup is blend_kernel's (blend_common.h): 256 threads per 16x16 tile, wave = 8x8 quadrant, lane = pixel, the same lists,
 // footprint ballots, launch order and stat words.  blend_kernel itself, blend_one and next_batch stay as they are: the colour
 // frame's asm walks are pinned to them bit for bit.  The callables are always_inline lambdas that capture the
@@ -116,6 +117,7 @@ struct ChannelArgs {
     int channels;           // of the whole map: a pixel's values lie channels floats apart
     int c0, nch;            // this walk composites channels c0 .. c0 + nch - 1, 1 <= nch <= CH
     int vec_in, vec_out;    // 16-byte loads of the rows / stores of the pixels are aligned (decided on the host)
+    int64_t T_view_stride;  // several views per launch (blend_channels_kernel): floats between the views' final-T planes
 };
 
 template <int Q> struct ChannelRow { float4 v[Q]; };
@@ -191,15 +193,22 @@ __device__ __forceinline__ float dpp_add(float x)
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
-// The prelude of every launcher: the single-view refusal under the caller's noun, the arguments, the launch order — heaviest tiles
+// The prelude of every launcher: the single-view refusal under the caller's noun (unless it takes several), the arguments, the launch order — heaviest tiles
 // first, by what the last colour blend on this workspace staged where that is known (a schedule only).  tile_work stays null: these
 // kernels never write it.  *slots == 0: an empty frame, nothing to launch.
+// views: what the launcher's kernel takes.  Several — it is launched with dim3(*slots, ws.views), view blockIdx.y walks slice
+// blockIdx.y of the workspace (blend_args_of_view) and writes out + blockIdx.y * out_view_stride BYTES; whatever else it keeps per
+// view it finds through strides in its own argument struct.  Single (pick, top-k, slab): a workspace of several views is refused.
+enum class WalkViews { Single, Several };
 inline int weight_walk_begin(const char *noun, const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
-                             void *out, float *out_T, hipStream_t s, BlendArgs *a, int *slots)
+                             void *out, float *out_T, hipStream_t s, BlendArgs *a, int *slots, WalkViews views = WalkViews::Single,
+                             size_t out_view_stride = 0)
 {
     *slots = 0;
-    if (ws.views > 1) { set_error("%s: single views only", noun); return GSR_ERR_BAD_ARG; }
+    if (ws.views > 1 && views == WalkViews::Single) { set_error("%s: single views only", noun); return GSR_ERR_BAD_ARG; }
     *a = blend_args_common(cam, opts, ws, plan, out, out_T);
+    a->view_stride = ws.view_stride;  // (0 for a single view: every offset is zero)
+    a->out_view_stride = out_view_stride;
     if (a->rows > 0 && a->tiles_x > 0) *slots = launch_tile_order(ws, plan, true, s);
     return GSR_OK;
 }
@@ -222,6 +231,7 @@ inline int for_channel_groups(const float *features, int64_t stride, const float
         // 16-byte accesses where every row / pixel of this group starts on a 16-byte boundary
         ch.vec_in = reinterpret_cast<uintptr_t>(ch.features) % 16 == 0 && stride % 4 == 0;
         ch.vec_out = reinterpret_cast<uintptr_t>(map + c0) % 16 == 0 && channels % 4 == 0;
+        ch.T_view_stride = 0;
         const int rc = launch(ch, width);
         if (rc) return rc;
         c0 += ch.nch;

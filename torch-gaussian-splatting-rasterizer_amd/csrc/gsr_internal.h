@@ -241,12 +241,16 @@ int launch_tile_order(const Workspace &ws, const FramePlan &plan, bool use_hint,
 // Stage 3 for caller-supplied channels (blend_features.hip): out_map[p] = sum_i w_i(p) features[i], single views only
 int launch_blend_features(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *features,
                           float *out_map, float *out_T, hipStream_t s);
-// The same for `channels` channels, rows `stride` floats apart, up to 16 channels per walk (blend_channels.hip): one launch per group
+// The same for `channels` channels, rows `stride` floats apart, up to 16 channels per walk (blend_channels.hip): one launch per group.
+// ws.views views per launch: view v writes out_map + v * map_view_stride and out_T + v * T_view_stride (floats); all read `features`
 int launch_blend_channels(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *features,
-                          int channels, int64_t stride, float *out_map, float *out_T, hipStream_t s);
-// The transpose of launch_blend_channels in the channels (blend_channels_backward.hip): grad_features[i] += sum_p w_i(p) grad_map[p]
+                          int channels, int64_t stride, float *out_map, float *out_T, hipStream_t s, int64_t map_view_stride = 0,
+                          int64_t T_view_stride = 0);
+// The transpose of launch_blend_channels in the channels (blend_channels_backward.hip): grad_features[i] += sum_p w_i(p) grad_map[p].
+// ws.views views per launch: view v reads grad_map + v * map_view_stride (floats); all add into the one grad_features
 int launch_blend_channels_backward(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
-                                   const float *grad_map, int channels, float *grad_features, int64_t stride, hipStream_t s);
+                                   const float *grad_map, int channels, float *grad_features, int64_t stride, hipStream_t s,
+                                   int64_t map_view_stride = 0);
 // Stage 3 for ids (blend_pick.hip): per pixel the gaussian of largest weight (+ that weight), the first one after which T < median_T,
 // and (out_count != nullptr: the COUNT kernel) how many had w > 0.  Any output may be null; single views only
 int launch_blend_pick(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, float median_T,
@@ -263,9 +267,12 @@ int launch_blend_slab(const GsrCamera &cam, const GsrOptions &opts, const Worksp
                       float *out_map, float *out_T, hipStream_t s);
 // Per-gaussian statistics of the view's weights over the counted pixels (blend_gstats.hip): weight_sum[i] += sum_p w_i(p),
 // weight_max[i] = max(old, max_p w_i(p)), pixels[i] += #{p : w_i(p) > 0}; any of the three may be null, not all; pixel_mask null: every
-// drawn pixel counts; single views only
+// drawn pixel counts.  ws.views views per launch: view v reads pixel_mask + v * mask_view_stride bytes and all accumulate into the
+// three arrays; view_hits[i] (may be null, may be the only output) += the views that reach gaussian i with w > 0 in a counted pixel,
+// through view_bits [n], a scratch the caller has cleared on the stream
 int launch_blend_gstats(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const uint8_t *pixel_mask,
-                        float *weight_sum, float *weight_max, uint32_t *pixels, hipStream_t s);
+                        float *weight_sum, float *weight_max, uint32_t *pixels, hipStream_t s, int64_t mask_view_stride = 0,
+                        uint32_t *view_hits = nullptr, uint32_t *view_bits = nullptr);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

@@ -428,6 +428,29 @@ class _RenderFeatures(torch.autograd.Function):
         return g, None, None, None, None, None
 
 
+class _RenderFeaturesBatch(torch.autograd.Function):
+    """render_features_batch as a differentiable function of the features alone: ONE node for all views, whose backward is
+    Rasterizer.feature_gradient_batch under the same cameras and options (the views' gradients summed by the kernel)."""
+
+    @staticmethod
+    def forward(ctx, features, rasterizer, cams, opts, return_T, scene_order):
+        ctx.rasterizer, ctx.scene_order = rasterizer, scene_order
+        ctx.cams = [GsrCamera.from_buffer_copy(c) for c in cams]
+        ctx.opts = GsrOptions.from_buffer_copy(opts or make_options())
+        res = rasterizer._render_features_batch(cams, features.detach(), opts, return_T, scene_order)
+        if return_T:
+            ctx.mark_non_differentiable(res[1])
+        return res
+
+    @staticmethod
+    def backward(ctx, grad_out, *_):
+        g = ctx.rasterizer.feature_gradient_batch(ctx.cams, grad_out, ctx.opts, scene_order=ctx.scene_order)
+        return g, None, None, None, None, None
+
+
+VIEW_STATS_BATCH = VIEW_STATS + ("views",)  # the names view_stats_batch's `want` takes: ViewStats' fields, then the view count
+
+
 # render_features: maps of more channels than this go through gsr_render_channels (many channels per walk of the tile lists), the
 # others through the three-channel blend.  DESIGN.md §5.11 has the measurement the rule rests on.
 WIDE_BLEND_ABOVE = 3
@@ -1030,6 +1053,193 @@ class Rasterizer:
         m = self.render_pick(cam, opts)
         return int(m.best_id[int(y), int(x)]), int(m.median_id[int(y), int(x)])
 
+    # -- feature maps, their gradient and view statistics, `views` cameras per launch sequence -----------------
+    def _view_list(self, cams, opts: GsrOptions):
+        """The cameras of a *_batch call as a list, refused as libgsr refuses them: at least one, one frame size, no screen layout."""
+        cams = list(cams)
+        if not cams:
+            raise ValueError("a batch needs at least one view")
+        if opts.output_layout == 1:
+            raise ValueError("batches hold [H,W] maps or shard strips: output_layout = 1 is not supported")
+        if any((c.width, c.height) != (cams[0].width, cams[0].height) for c in cams):
+            raise ValueError("the views of a batch must share one frame size")
+        return cams
+
+    def _view_groups(self, cams, opts: GsrOptions):
+        """(index of its first camera, the group's cameras as a ctypes array) per launch sequence: `views` cameras at a time, fewer
+        with opts.batch_views or in the last group."""
+        k = self._views_per_launch(opts, len(cams))
+        return [(i, (GsrCamera * len(cams[i:i + k]))(*cams[i:i + k])) for i in range(0, len(cams), k)]
+
+    def _enqueue_lists_views(self, arr, opts: GsrOptions) -> GsrOptions:
+        """gsr_lists_views for one group (view j in slice j) on the current stream, unchecked like enqueue_batch() and with its rule
+        for the slices' records; returns the options the call ran with."""
+        ws = self._workspace(arr[0].width, arr[0].height)
+        self._reset_slices(self.unchecked.to_reset(len(arr)))
+        o = GsrOptions.from_buffer_copy(opts)
+        o.keep_flags = 1 if (self.unchecked.slices or opts.keep_flags) else 0
+        sc = self.scene.c_struct()
+        check(lib.gsr_lists_views(C.byref(sc), arr, len(arr), C.byref(o), self.max_pairs, ws.data_ptr(), ws.numel(), _stream_ptr(self.scene.device)))
+        self.unchecked.wrote(len(arr))
+        return o
+
+    def _checked_lists_views(self, arr, opts: GsrOptions, what: str) -> GsrOptions:
+        """_checked_lists for one group of views: gsr_lists_views, stats() on every slice and a re-run until all are complete (the
+        worst view decides); only then may the caller's gsr_blend_*_views add, with the options returned here."""
+        def attempt(o):
+            o = GsrOptions.from_buffer_copy(o)
+            o.colour_stage = 0
+            return self._enqueue_lists_views(arr, o)
+
+        return _render_checked([self], [None], opts, attempt, 8, what)
+
+    def _blend_lists_views(self, arr, opts: GsrOptions, entry, *args) -> None:
+        """One gsr_blend_*_views entry over the lists in slices 0 .. len(arr) - 1 (the workspace is asked for again, as in _blend_lists)."""
+        ws = self._workspace(arr[0].width, arr[0].height)
+        check(entry(self.scene.n, arr, len(arr), C.byref(opts), self.max_pairs, ws.data_ptr(), ws.numel(), *args, _stream_ptr(self.scene.device)))
+
+    def render_features_batch(self, cams, features: torch.Tensor, opts: Optional[GsrOptions] = None, return_T: bool = False,
+                              scene_order: bool = False):
+        """render_features for several cameras of one frame size, `views` of them per launch sequence (gsr_render_channels_batch: one
+        preprocess, one set of sorts and one blend per group): [B, H, W, C] (a tile-row shard: [B, rows*16, W, C]) and, with return_T,
+        the final transmittances [B, H, W].  Every view's map and T are render_features' bit for bit; every C goes through the
+        many-channel blend.  features, scene_order: render_features'.  Checked and re-rendered on overflow like render_batch(): the
+        worst view decides.  Differentiable in `features` like render_features: one autograd node for all views, whose backward is
+        feature_gradient_batch()."""
+        if features.requires_grad and torch.is_grad_enabled():
+            return _RenderFeaturesBatch.apply(features, self, list(cams), opts, return_T, scene_order)
+        return self._render_features_batch(cams, features, opts, return_T, scene_order)
+
+    def _render_features_batch(self, cams, features: torch.Tensor, opts: Optional[GsrOptions], return_T: bool, scene_order: bool):
+        opts = opts or make_options()
+        cams = self._view_list(cams, opts)
+        rows = self._feature_rows(features, scene_order)
+        n_ch, B = int(rows.shape[1]), len(cams)
+        shape, tshape = self._out_shape(cams[0], opts)
+        arr = (GsrCamera * B)(*cams)
+
+        def attempt(o):
+            out = self._new(o, (B,) + tuple(shape[:2]) + (n_ch,))
+            T = self._new(o, (B,) + tuple(tshape), fill=1) if return_T else None
+            if out.numel() == 0 or self.scene.n == 0:  # a shard that owns no tile row, or nothing to draw: zeros, T = 1
+                out.zero_()
+                self.unchecked.wrote(0)
+                return (out, T) if return_T else out
+            ws = self._workspace(cams[0].width, cams[0].height)
+            k = self._views_per_launch(o, B)
+            self._reset_slices(self.unchecked.to_reset(k))
+            o = GsrOptions.from_buffer_copy(o)
+            o.keep_flags = 1 if (self.unchecked.slices or o.keep_flags) else 0
+            sc = self.scene.c_struct()
+            check(lib.gsr_render_channels_batch(C.byref(sc), arr, B, C.byref(o), self.max_pairs, ws.data_ptr(), ws.numel(), rows.data_ptr(),
+                                                n_ch, int(rows.stride(0)), out.data_ptr(), out[0].numel(), T.data_ptr() if return_T else None,
+                                                T[0].numel() if return_T else 0, _stream_ptr(self.scene.device)))
+            self.unchecked.wrote(k)
+            return (out, T) if return_T else out
+
+        return _render_checked([self], [None], opts, attempt, 4, "feature map batch")
+
+    def feature_gradient_batch(self, cams, grad_maps: torch.Tensor, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None,
+                               scene_order: bool = False) -> torch.Tensor:
+        """The transpose of render_features_batch: [n, C] with row i = sum_v sum_p w_v,i(p) grad_maps[v][p] — the sum of
+        feature_gradient over the cameras, added up by the kernel (gsr_blend_channels_backward_views), `views` cameras per launch
+        sequence.  grad_maps: [B, H, W, C] as render_features_batch lays the maps out (made contiguous float32), finite.  Order of the
+        result, `out` and its accumulation: feature_gradient's.  Two phases per group, with or without `out`: gsr_lists_views, stats()
+        and a re-run until every slice is complete, and only then the blend that adds — an incomplete walk never reaches the buffer.
+        Float atomic sums may differ in the last bits between two calls."""
+        opts = opts or make_options()
+        cams = self._view_list(cams, opts)
+        dev, n, B = self.scene.device, self.scene.n, len(cams)
+        _require_cuda(grad_maps, "grad_maps")
+        shape, _ = self._out_shape(cams[0], opts)
+        if grad_maps.dim() != 4 or tuple(grad_maps.shape[:3]) != (B,) + tuple(shape[:2]) or not 1 <= grad_maps.shape[3] <= _lib.GSR_MAX_FEATURE_CHANNELS:
+            raise ValueError(f"grad_maps must have shape {(B,) + tuple(shape[:2])} + (1 <= C <= {_lib.GSR_MAX_FEATURE_CHANNELS},), got {tuple(grad_maps.shape)}")
+        if grad_maps.device != dev:
+            raise ValueError("grad_maps must live on the scene's device")
+        n_ch = int(grad_maps.shape[3])
+        gm = grad_maps.detach().to(torch.float32).contiguous()
+        if out is not None:
+            if tuple(out.shape) != (n, n_ch) or out.dtype != torch.float32 or out.device != dev or (
+                    n and (out.stride(1) != 1 or out.stride(0) < n_ch)):
+                raise ValueError(f"out must be a float32 tensor of shape [{n}, {n_ch}] on the scene's device with unit element stride")
+        if n == 0 or gm.numel() == 0:  # nothing to draw, or a shard that owns no tile row: no workspace (feature_gradient's rule)
+            return out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
+        buf = out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
+        for i, arr in self._view_groups(cams, opts):
+            o = self._checked_lists_views(arr, opts, "feature gradient batch")
+            self._blend_lists_views(arr, o, lib.gsr_blend_channels_backward_views, gm[i].data_ptr(), gm[0].numel(), n_ch, buf.data_ptr(),
+                                    int(buf.stride(0)))
+        if out is not None or scene_order:
+            return buf
+        return file_order_gradient(buf, self.scene.order_t)
+
+    def _stats_batch_request(self, cams, opts: GsrOptions, masks, out, want):
+        """view_stats_batch's argument checks, before any workspace or buffer is made: (wanted flags of VIEW_STATS_BATCH, the masks as
+        they came with each checked and made one byte per pixel — or None when no camera has one)."""
+        if isinstance(want, str) or not all(isinstance(w, str) for w in want):
+            raise ValueError(f"want must be a sequence of names from {VIEW_STATS_BATCH}, got {want!r}")
+        if not len(want) or any(w not in VIEW_STATS_BATCH for w in want):
+            raise ValueError(f"want must name at least one of {VIEW_STATS_BATCH} and nothing else, got {tuple(want)!r}")
+        flags = tuple(name in want for name in VIEW_STATS_BATCH)
+        masks = [None] * len(cams) if masks is None else list(masks)
+        if len(masks) != len(cams):
+            raise ValueError(f"masks must hold one entry per camera: {len(masks)} for {len(cams)} cameras")
+        masks = [self._stats_request(cams[0], opts, m, None, VIEW_STATS)[1] for m in masks]  # (None stays None)
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 2 or not isinstance(out[0], tuple):
+                raise ValueError("out must be (ViewStats, views), as view_stats_batch returns them")
+            if any(flags[:3]):
+                self._stats_request(cams[0], opts, None, out[0], [w for w in VIEW_STATS if w in want])
+            v, n = out[1], self.scene.n
+            if flags[3] and (not isinstance(v, torch.Tensor) or tuple(v.shape) != (n,) or v.dtype != torch.int32
+                             or v.device != self.scene.device or not v.is_contiguous()):
+                raise ValueError(f"out's views must be a contiguous {torch.int32} tensor of shape [{n}] on the scene's device")
+        return flags, (masks if any(m is not None for m in masks) else None)
+
+    def view_stats_batch(self, cams, opts: Optional[GsrOptions] = None, masks=None, out=None, scene_order: bool = False,
+                         want=VIEW_STATS_BATCH):
+        """view_stats over several cameras of one frame size into ONE set of buffers, `views` cameras per launch sequence
+        (gsr_blend_gaussian_stats_views): (ViewStats, views) with weight_sum summed, weight_max the maximum and pixels summed over the
+        cameras, and views [n] int32 = in how many of them the gaussian reaches a counted pixel with w > 0 — counted exactly, in the
+        kernel.  `want` names what to compute ("sum", "max", "pixels", "views"); the rest is None and costs nothing.  weight_max,
+        pixels and views are exact and reproducible to the bit, weight_sum is a float atomic sum.
+        masks: None, or one mask (view_stats') or None per camera; they travel as one uint8 [B, H, W] tensor, ones for None.
+        Order of the result: view_stats'.  out: (ViewStats, views) of [n] tensors in the SCENE's order (only the wanted ones needed) to
+        ACCUMULATE into; they are returned.  Two phases per group, with or without `out`: gsr_lists_views, stats() and a re-run until
+        every slice is complete, and only then the blend that adds.  Sets last_stats."""
+        opts = opts or make_options()
+        cams = self._view_list(cams, opts)
+        flags, masks = self._stats_batch_request(cams, opts, masks, out, want)
+        dev, n = self.scene.device, self.scene.n
+        dtypes = (torch.float32, torch.float32, torch.int32, torch.int32)
+        given = out is not None
+        have = (tuple(out[0]) + (out[1],)) if given else (None,) * 4
+        bufs = [((have[k] if given else torch.zeros(n, dtype=dtypes[k], device=dev)) if flags[k] else None) for k in range(4)]
+
+        def result():
+            if given or scene_order:
+                return ViewStats(*bufs[:3]), bufs[3]
+            back = [None if b is None else file_order_gradient(b, self.scene.order_t) for b in bufs]
+            return ViewStats(*back[:3]), back[3]
+
+        tshape = tuple(self._out_shape(cams[0], opts)[1])
+        if n == 0 or 0 in tshape:  # nothing to draw, or a shard that owns no tile row: no workspace (view_stats' rule)
+            return result()
+        stacked = None
+        if masks is not None:
+            stacked = torch.ones((len(cams),) + tshape, dtype=torch.uint8, device=dev)
+            for j, m in enumerate(masks):
+                if m is not None:
+                    stacked[j] = m
+        bits = torch.empty(n, dtype=torch.int32, device=dev) if flags[3] else None  # libgsr's scratch: cleared by every call
+        ptrs = [b.data_ptr() if b is not None else None for b in bufs] + [bits.data_ptr() if bits is not None else None]
+        plane = tshape[0] * tshape[1]
+        for i, arr in self._view_groups(cams, opts):
+            o = self._checked_lists_views(arr, opts, "view statistics batch")
+            self._blend_lists_views(arr, o, lib.gsr_blend_gaussian_stats_views, stacked[i].data_ptr() if stacked is not None else None,
+                                    plane, *ptrs)
+        return result()
+
     def _batch_out(self, cams, opts: GsrOptions, out: Optional[torch.Tensor]):
         """(out, frame_stride in elements) of a batch: whole frames [B,H,W,3], or with a tile-row shard (output_layout = 2) the
         strips [B,rows*16,W,3]."""
@@ -1123,11 +1333,15 @@ class Rasterizer:
 def accumulate_view_stats(R: "Rasterizer", cams, opts: Optional[GsrOptions] = None, masks=None):
     """Rasterizer.view_stats over a camera set into one set of buffers: (ViewStats, views) in the order of the file the scene was
     loaded from — weight_sum summed, weight_max the maximum and pixels summed over the views, and `views` [n] int32 = in how many
-    of the views the gaussian reached a counted pixel.  masks: None, or one mask (or None) per camera."""
+    of the views the gaussian reached a counted pixel.  masks: None, or one mask (or None) per camera.  A Rasterizer with `views` > 1
+    takes all cameras through ONE view_stats_batch call (`views` of them per launch sequence, the view count exact from the kernel);
+    else one view_stats call per camera."""
     cams = list(cams)
     masks = [None] * len(cams) if masks is None else list(masks)
     if len(masks) != len(cams):
         raise ValueError(f"masks must hold one entry per camera: {len(masks)} for {len(cams)} cameras")
+    if getattr(R, "views", 1) > 1 and cams:
+        return R.view_stats_batch(cams, opts, masks)
     n, dev = R.scene.n, R.scene.device
     total = ViewStats(torch.zeros(n, dtype=torch.float32, device=dev), torch.zeros(n, dtype=torch.float32, device=dev),
                       torch.zeros(n, dtype=torch.int32, device=dev))
