@@ -20,8 +20,84 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 from fuzz_scene import build_case  # noqa: E402  (tools/fuzz_scene.py, next to this file; tests/gpu_cases.fuzz_case is the same function)
 
 
+def maps_campaign(a):
+    """--maps: the map kernels (feature / channel blend, its backward, pick, top-k, slab, view statistics, K views per launch)
+    against the float64 reference of tools/fuzz_maps.py on fresh campaign cases small enough for it (H * W * drawn <= 2e7), in
+    file and in Morton order, with the check functions the suite runs on its pinned seeds.  A case whose drawn neighbours lie
+    closer than 16 ulps in depth gets the identities between the kernels only; one over an exclusion cap is counted and skipped.
+    A gradient whose bar fails on a cancelling sum of one or two rows (fuzz_maps._gradient_bar) is tallied as ill-conditioned, not as
+    a failure, while its error stays under 1e-5 of the terms' own magnitude.  Tallies go to --maps-out."""
+    import fuzz_maps as fm
+    import gsr_amd  # noqa: F401
+    from gsr_amd import renderer
+    from oracle import cpu_oracle as orc
+
+    master = np.random.default_rng(a.seed)
+    t_end = time.time() + a.seconds
+    tally = dict(cases=0, checked=0, identities_only=0, too_large=0, over_a_cap=0, ill_conditioned_gradient=0, failures=0)
+    worst, shares, failed = {}, {}, []
+    while time.time() < t_end and not (a.case_seed is not None and tally["cases"]):
+        case_seed = int(master.integers(0, 1 << 62)) if a.case_seed is None else a.case_seed
+        c = build_case(case_seed, a.max_n)
+        tally["cases"] += 1
+        pre = orc.preprocess(c["packed"], orc.camera(*c["args"]))
+        bb = pre["pixel_bboxes"]
+        drawn = int((((bb[:, 2] - bb[:, 0]) * (bb[:, 3] - bb[:, 1]) != 0) & (pre["sigmas"] != 0).all(1)).sum())
+        desc = f"case-seed={case_seed} n={c['n']} {c['W']}x{c['H']} gen={c['gen'].__name__} drawn={drawn}"
+        if c["H"] * c["W"] * drawn > 2e7:
+            tally["too_large"] += 1
+            continue
+        print(f"case {tally['cases']}: {desc}", flush=True)  # before it runs: a stall then points at its case
+        for order in ("file", "morton"):
+            try:
+                scene = renderer.GaussianScene.from_packed(c["packed"], spatial_order=order == "morton")
+                R = renderer.Rasterizer(scene)
+                views = [(renderer.make_camera(*args), ref) for args, ref in fm.case_views(orc, c, scene.order)]
+                cam, ref = views[0]
+                F, Gm = fm.features_of(case_seed % 1000, c["n"]), fm.upstream_of(case_seed % 1000, c["H"], c["W"], 3)
+                if any(fm.facts(r)["min_gap_ulps"] < 16 for _, r in views):
+                    tally["identities_only"] += 1
+                    figs = dict(identities=fm.run_identities(renderer, R, [v for v, _ in views], F, Gm[0]))
+                else:
+                    sh = fm.shares(ref)
+                    for k, v in sh.items():
+                        shares[k] = max(shares.get(k, 0.0), v)
+                    if any(fm.shares(r)[k] > cap for _, r in views for k, cap in fm.CAPS.items()):
+                        tally["over_a_cap"] += 1
+                        continue
+                    from gsr_amd import rasterize
+                    w2c = torch.tensor(list(cam.w2c), dtype=torch.float32).view(4, 4)
+                    z = rasterize.project_to_camera_space(torch.from_numpy(c["packed"]["means"]).cuda(), w2c)[:, 2].cpu().numpy()
+                    figs = dict(forward=fm.run_forward(R, cam, ref, F), slab=fm.run_slab(R, cam, ref, F, z),
+                                backward=fm.run_backward(R, cam, ref, Gm[0], lenient=True), stats=fm.run_stats(R, cam, ref),
+                                pick=fm.run_pick(R, cam, ref), topk=fm.run_topk(R, cam, ref),
+                                views=fm.run_views(renderer, R, views, F, Gm, lenient=True))
+                    tally["checked"] += 1
+                    tally["ill_conditioned_gradient"] += any("ill_conditioned_rel" in f for f in figs.values())
+                for kind, fig in figs.items():
+                    for k, v in fig.items():
+                        key = f"{kind}.{k}"
+                        worst[key] = (min if k.startswith("dB") else max)(worst.get(key, v), v)
+            except Exception as e:  # noqa: BLE001
+                tally["failures"] += 1
+                failed.append(f"{desc} order={order}: {type(e).__name__}: {str(e)[:300]}")
+                print("FAIL " + failed[-1], flush=True)
+    lines = ["fuzz_parity.py --maps: " + ", ".join(f"{k} {v}" for k, v in tally.items()) + f" (seed {a.seed}, max_n {a.max_n})",
+             "largest share left out, reference alone: " + ", ".join(f"{k} {100 * v:.2f} %" for k, v in sorted(shares.items())),
+             "worst figure per kind (dB: the lowest; errors and shares: the largest):"]
+    lines += [f"  {k} = {v:.3g}" for k, v in sorted(worst.items())] + ["FAIL " + f for f in failed]
+    os.makedirs(os.path.dirname(os.path.abspath(a.maps_out)), exist_ok=True)
+    with open(a.maps_out, "w") as f:
+        f.write("\n".join(lines) + "\n")
+    print("\n".join(lines), flush=True)
+    sys.exit(1 if tally["failures"] else 0)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--maps", action="store_true", help="check the map kernels against the float64 reference of tools/fuzz_maps.py "
+                    "instead of the colour frame (cases with H * W * drawn <= 2e7); tallies go to --maps-out")
+    ap.add_argument("--maps-out", default=os.path.join(REPO, "profiles", "fuzz_maps_summary.txt"))
     ap.add_argument("--seconds", type=float, default=120.0)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--max-n", type=int, default=60000)
@@ -29,6 +105,8 @@ def main():
     ap.add_argument("--report-flips", action="store_true", help="print every case in which a pixel sits on the alpha > 1/255 step "
                     "(differs from the oracle by more than 1e-5): how often, and by how much, the tolerance is actually used")
     a = ap.parse_args()
+    if a.maps:
+        return maps_campaign(a)
 
     import gsr_amd  # noqa: F401
     from conftest import psnr
