@@ -34,7 +34,9 @@ extern "C" {
                             gsr_render_slab — gsr_blend_channels between two per-pixel depth limits: a depth test against a z-buffer, section planes, depth layers; gsr_blend_gaussian_stats /
                             gsr_render_gaussian_stats — per-gaussian statistics of a view: the sum and the maximum of a gaussian's weights and the number of pixels it reaches, optionally under a pixel mask; gsr_lists_views /
                             gsr_blend_channels_views / gsr_blend_channels_backward_views / gsr_blend_gaussian_stats_views / gsr_render_channels_batch — feature maps, their gradient and the
-                            statistics for several views per launch sequence, with view_hits, the exact number of views that reach a gaussian): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            statistics for several views per launch sequence, with view_hits, the exact number of views that reach a gaussian; gsr_blend_splat_backward /
+                            gsr_render_splat_backward — the gradient of a feature map and of the final T with respect to the 2-D splat: opacity, 2-D mean, inverse 2-D covariance, and the
+                            per-pixel absolute mean gradients): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -338,6 +340,49 @@ int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, co
                                  size_t workspace_bytes, const float *grad_map /* [.., channels], layout per opts->output_layout */,
                                  int32_t channels, float *grad_features /* row i at + i * grad_stride */, int64_t grad_stride,
                                  void *stream);
+
+/* The gradient of a feature map with respect to the 2-D SPLAT, under the camera and options of the forward.  With the map
+ * out_map[p] = sum_i w_i(p) f_i of gsr_blend_channels, its final transmittance T_final[p], and
+ *   L = sum_p grad_map[p] . out_map[p] + sum_p grad_T[p] T_final[p],
+ * row i of grad_splat ([n][8] float32, 32 bytes a row) receives the derivative of L in what gsr_preprocess computes for gaussian i
+ * (GsrDebugOut: opacity, screen_means, sigmas = the inverse 2-D covariance s0, s1, s2):
+ *   [0] dL/d opacity   [1] dL/d mean_x   [2] dL/d mean_y   [3] dL/d s0   [4] dL/d s1   [5] dL/d s2
+ *   [6] sum_p |dL/d mean_x restricted to pixel p|   [7] the same for mean_y   (want_abs only; else columns 6 and 7 are not touched).
+ * Means are in pixels.  Per pair: dx = mean_x - x, dy = mean_y - y, power = -(s0 dx^2 + s1 dy^2) / 2 - s2 dx dy, u = opacity
+ * exp(power), alpha = min(0.99, u), kept where alpha > 1/255 and power <= 0.  The support (footprint, threshold, power <= 0) is held
+ * fixed, and the cap has derivative 0: a pair with u >= 0.99 contributes nothing (the reference implementation of 3DGS lets the
+ * gradient pass through its cap; this does not).  The weights, the lists and the stop rule are gsr_blend_channels', bit for bit; the
+ * walk runs twice inside the one launch (first for S' = sum_i w_i s_i + grad_T T_final with s_i = grad_map[p] . f_i, then for the
+ * gradients, with what lies behind gaussian i formed as S' minus the running sum), no per-pixel state is taken from the caller and
+ * no map is written.  More than 16 channels are further launches inside this call; grad_T enters once.
+ * It ADDS into grad_splat (the caller zeroes it, or keeps summing over views); rows of gaussians no pixel draws are not touched.
+ * features: as gsr_blend_channels reads them, rows feature_stride >= channels floats apart.  grad_map: float32, contiguous, layout
+ * per opts->output_layout with `channels` channels (what gsr_blend_channels writes); grad_T: NULL or one float per pixel in the
+ * layout of out_final_T; pixels the forward leaves 0 / 1 (the undrawn last column / row of reference_compat) contribute nothing.
+ * min_T >= 0: a pair whose incoming transmittance T_i is below min_T contributes nothing of its own (it still counts in what lies
+ * in front of the others); 0 switches it off.  Honoured and ignored options, and what it leaves alone on the workspace, are
+ * gsr_blend_channels'; gsr_read_stats afterwards describes the second walk (wave_entries / fetched_entries are the forward's).
+ *   - The sums are float atomic adds: their value depends on the order the adds arrive in, so two calls with the same input can
+ *     differ in the last bits.
+ *   - Accuracy: S' minus the running sum carries an absolute error of about 2^-24 |S'| alpha / (1 - alpha) per pixel, so a gaussian
+ *     seen only through T <~ 1e-6 gets a gradient that is tiny but relatively meaningless; min_T and early_out_T cut such pairs off.
+ *   - features, grad_map and grad_T must be finite.
+ *   - grad_splat must not alias features, grad_map or grad_T.
+ * GSR_ERR_BAD_ARG, before any HIP call or look at the workspace, for a null camera, options, features, grad_map or grad_splat,
+ * channels < 1 or > GSR_MAX_FEATURE_CHANNELS, feature_stride < channels, min_T negative or not finite, want_abs with channels > 16
+ * (the absolute sums are not linear in the channels: one walk), output_dtype = 1, accum_dtype = 1.  Single views. */
+int gsr_blend_splat_backward(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, const float *features /* row i at features + i * feature_stride */,
+                             int64_t feature_stride, int32_t channels, const float *grad_map /* [.., channels] */,
+                             const float *grad_T /* may be NULL */, float min_T, int32_t want_abs, float *grad_splat /* [n][8], ADDS */,
+                             void *stream);
+
+/* gsr_preprocess (as with colour_stage = 0) + gsr_bin_sort + gsr_blend_splat_backward */
+int gsr_render_splat_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                              size_t workspace_bytes, const float *features /* row i at features + i * feature_stride */,
+                              int64_t feature_stride, int32_t channels, const float *grad_map /* [.., channels] */,
+                              const float *grad_T /* may be NULL */, float min_T, int32_t want_abs, float *grad_splat /* [n][8], ADDS */,
+                              void *stream);
 
 /* Stage 3 for what no blended channel can hold — per pixel p, over the same depth-ordered lists and with the same weights
  * w_i = alpha_i T_i (and the same T, bit for bit) as gsr_blend_features (no reference counterpart):

@@ -137,6 +137,7 @@ EXPORTS = [
     "gsr_blend_gaussian_stats", "gsr_render_gaussian_stats",
     "gsr_lists_views", "gsr_blend_channels_views", "gsr_blend_channels_backward_views", "gsr_blend_gaussian_stats_views",
     "gsr_render_channels_batch",
+    "gsr_blend_splat_backward", "gsr_render_splat_backward",
 ]
 
 
@@ -171,6 +172,9 @@ def _load() -> C.CDLL:
                        ("topk", [i32, i32, vp, vp, vp, vp]), ("gaussian_stats", [vp, vp, vp, vp, vp])):
         getattr(L, "gsr_blend_" + name).argtypes = lists + tail   # the blend alone, over lists already made ...
         getattr(L, "gsr_render_" + name).argtypes = view + tail   # ... and stages 1-3 in one call: the same tail
+    splat = [vp, i64, i32, vp, vp, C.c_float, i32, vp, vp]  # features, their stride, channels, grad_map, grad_T, min_T, want_abs, grad_splat [n][8], stream
+    L.gsr_blend_splat_backward.argtypes = lists + splat
+    L.gsr_render_splat_backward.argtypes = view + splat
     L.gsr_render_batch.argtypes = [scene_p, cam_p, i32, opts_p, i64, vp, sz, vp, i64, vp]
     views = [cam_p, i32, opts_p, i64, vp, sz]        # gsr_*_views: cameras [host], how many, options, max_pairs, workspace, its bytes
     L.gsr_lists_views.argtypes = [scene_p] + views + [vp]

@@ -595,6 +595,57 @@ int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, co
         });
 }
 
+// What gsr_blend_splat_backward / gsr_render_splat_backward refuse before anything else (and before any HIP call)
+static int check_splat_backward(const GsrCamera *cam, const GsrOptions *opts, const float *features, int64_t feature_stride,
+                                int32_t channels, const float *grad_map, float min_T, int32_t want_abs, const float *grad_splat)
+{
+    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    if (!features) { set_error("null features"); return GSR_ERR_BAD_ARG; }
+    if (!grad_map) { set_error("null gradient map"); return GSR_ERR_BAD_ARG; }
+    if (!grad_splat) { set_error("null splat gradient"); return GSR_ERR_BAD_ARG; }
+    if (channels < 1 || channels > GSR_MAX_FEATURE_CHANNELS) {
+        set_error("bad channels %d (1 .. %d)", channels, GSR_MAX_FEATURE_CHANNELS); return GSR_ERR_BAD_ARG;
+    }
+    if (feature_stride < channels) {
+        set_error("bad feature_stride %lld: rows of %d channels overlap", (long long)feature_stride, channels); return GSR_ERR_BAD_ARG;
+    }
+    if (!(min_T >= 0.0f) || min_T > 3.4028234e38f) { set_error("bad min_T %g: a finite value >= 0", (double)min_T); return GSR_ERR_BAD_ARG; }
+    if (want_abs && channels > 16) {
+        set_error("want_abs with %d channels: the absolute sums are not linear in the channels, one walk of at most 16", channels);
+        return GSR_ERR_BAD_ARG;
+    }
+    if (opts->output_dtype == 1) { set_error("gradient maps are float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("splat gradients are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+int gsr_blend_splat_backward(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, const float *features, int64_t feature_stride, int32_t channels,
+                             const float *grad_map, const float *grad_T, float min_T, int32_t want_abs, float *grad_splat, void *stream)
+{
+    const int rc = check_splat_backward(cam, opts, features, feature_stride, channels, grad_map, min_T, want_abs, grad_splat);
+    if (rc) return rc;
+    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_splat_backward(c, o, ws, plan, features, feature_stride, channels, grad_map, grad_T, min_T, want_abs != 0,
+                                               grad_splat, s);
+        });
+}
+
+int gsr_render_splat_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                              size_t workspace_bytes, const float *features, int64_t feature_stride, int32_t channels,
+                              const float *grad_map, const float *grad_T, float min_T, int32_t want_abs, float *grad_splat, void *stream)
+{
+    const int rc = check_splat_backward(cam, opts, features, feature_stride, channels, grad_map, min_T, want_abs, grad_splat);
+    if (rc) return rc;
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
+            return launch_blend_splat_backward(c, o, ws, plan, features, feature_stride, channels, grad_map, grad_T, min_T, want_abs != 0,
+                                               grad_splat, s);
+        });
+}
+
 static int check_gaussian_stats_options(const GsrOptions *opts)
 {
     if (opts->output_dtype == 1) { set_error("gaussian statistics are float32 / uint32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }

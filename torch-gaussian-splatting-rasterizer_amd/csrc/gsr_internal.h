@@ -273,6 +273,12 @@ int launch_blend_slab(const GsrCamera &cam, const GsrOptions &opts, const Worksp
 int launch_blend_gstats(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const uint8_t *pixel_mask,
                         float *weight_sum, float *weight_max, uint32_t *pixels, hipStream_t s, int64_t mask_view_stride = 0,
                         uint32_t *view_hits = nullptr, uint32_t *view_bits = nullptr);
+// The gradient of a feature map (and of the final T) with respect to the 2-D splat (blend_splat_backward.hip): row i of grad_splat
+// [n][8] += {d/d opacity, d/d mean x, y, d/d sigma 0, 1, 2, and with want_abs the per-pixel absolute mean terms}; grad_T may be
+// null; want_abs: channels <= 16; single views only
+int launch_blend_splat_backward(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
+                                const float *features, int64_t stride, int channels, const float *grad_map, const float *grad_T,
+                                float min_T, bool want_abs, float *grad_splat, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

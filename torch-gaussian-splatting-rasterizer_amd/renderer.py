@@ -374,6 +374,29 @@ class ViewStats(NamedTuple):
 VIEW_STATS = ("sum", "max", "pixels")  # the names `want` takes, in ViewStats' field order
 
 
+class SplatGradient(NamedTuple):
+    """Rasterizer.splat_gradient: per gaussian, the gradient of L = <grad_map, map> + <grad_T, final T> with respect to what the
+    preprocess computes for it (preprocess_debug's names).  mean2d [n, 2]: d L / d screen_means, in 1 / pixel (multiply by W / 2,
+    H / 2 for the NDC norm 3DGS densifies by); sigmas [n, 3]: d L / d (s0, s1, s2), the inverse 2-D covariance; opacity [n]:
+    d L / d opacity (opacity_logit_gradient chains it to the logit); abs_mean2d [n, 2]: the per-pixel absolute values of the two
+    mean terms, summed (the AbsGS densification statistic), or None when it was not asked for.  All float32."""
+    mean2d: torch.Tensor
+    sigmas: torch.Tensor
+    opacity: torch.Tensor
+    abs_mean2d: Optional[torch.Tensor]
+
+
+def opacity_logit_gradient(scene: "GaussianScene", g: SplatGradient, scene_order: bool = False) -> torch.Tensor:
+    """[n]: d L / d opacity_logit = g.opacity * o (1 - o) with o = sigmoid(opacity_logit), the chain through the activation the
+    preprocess applies.  `g` in the file's order (scene_order=True: in the order of the scene's resident arrays, as it was asked
+    for)."""
+    x = scene.t["opacity_logit"]
+    chain = torch.sigmoid(x) * torch.sigmoid(-x)  # o (1 - o) without the cancellation of 1 - o (at logit 12, 1 - o = 6e-6)
+    if not scene_order:
+        chain = file_order_gradient(chain, scene.order_t)
+    return g.opacity * chain
+
+
 TOPK_SELECT = {"heaviest": _lib.GSR_TOPK_HEAVIEST, "nearest": _lib.GSR_TOPK_NEAREST}
 
 
@@ -794,6 +817,68 @@ class Rasterizer:
         o = self._checked_lists(cam, opts, "feature gradient")
         self._blend_lists(cam, o, lib.gsr_blend_channels_backward, gm.data_ptr(), n_ch, out.data_ptr(), int(out.stride(0)))
         return out
+
+    # -- the gradient of a feature map with respect to opacity and the 2-D splat ----------------------------------------------------
+    def splat_gradient(self, cam: GsrCamera, features: torch.Tensor, grad_map: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
+                       opts: Optional[GsrOptions] = None, min_T: float = 0.0, abs_mean: bool = False,
+                       out: Optional[torch.Tensor] = None, scene_order: bool = False) -> SplatGradient:
+        """The gradient of L = <grad_map, render_features(cam, features)> + <grad_T, final T> with respect to every gaussian's
+        opacity, 2-D mean and inverse 2-D covariance — preprocess_debug's opacity, screen_means and sigmas — under the same camera
+        and options (gsr_render_splat_backward).  The weights, lists and stop rule are the forward's; the support of a splat (its
+        footprint, the 1/255 threshold) is held fixed and the alpha cap at 0.99 has derivative 0.  features: [n, C] as
+        render_features takes them (scene_order applies to them and to the result); grad_map: [H, W, C] as render_features lays the
+        map out; grad_T: [H, W] in the layout of the final T, or None.  All finite, float32.
+        Units: means are in pixels, so mean2d is per pixel; multiply by W / 2, H / 2 for the NDC norm of 3DGS's densification.
+        abs_mean=True also sums the per-pixel absolute values of the two mean terms (AbsGS); C <= 16 then (they are not linear in
+        the channels).  min_T > 0: a pair whose incoming transmittance is below it contributes nothing of its own.
+        Accuracy: what lies behind a gaussian in a pixel is formed as the pixel's total minus a running sum, which carries an
+        absolute error of about 2^-24 |total| alpha / (1 - alpha) per pixel; a gaussian seen only through T <~ 1e-6 gets a gradient
+        that is tiny but relatively meaningless.  min_T and opts.early_out_T are the remedies.
+        Returns a SplatGradient in the order of the file the scene was loaded from (scene_order=True: of the scene's resident
+        arrays).  With `out` — [n, 8] float32 contiguous on the scene's device, in the SCENE's order, columns (opacity, mean x, y,
+        s0, s1, s2, |mean x|, |mean y|) — the gradient is ACCUMULATED into `out` (columns 6 and 7 only with abs_mean) and the
+        SplatGradient returned holds views of it, in the scene's order: stages 1-2 are checked and re-run first and only then does
+        the blend add.  Float atomic sums may differ in the last bits between two calls."""
+        opts = opts or make_options()
+        dev, n = self.scene.device, self.scene.n
+        self._check_features(features, _lib.GSR_MAX_FEATURE_CHANNELS)
+        n_ch = int(features.shape[1])
+        _require_cuda(grad_map, "grad_map")
+        shape, tshape = self._out_shape(cam, opts)
+        if tuple(grad_map.shape) != tuple(shape[:2]) + (n_ch,) or grad_map.device != dev:
+            raise ValueError(f"grad_map must have shape {tuple(shape[:2]) + (n_ch,)} on the scene's device, got {tuple(grad_map.shape)}")
+        if grad_T is not None and (not isinstance(grad_T, torch.Tensor) or tuple(grad_T.shape) != tuple(tshape) or grad_T.device != dev):
+            raise ValueError(f"grad_T must be a tensor of shape {tuple(tshape)} (the layout of the final T) on the scene's device")
+        if not (float(min_T) >= 0.0 and float(min_T) < float("inf")):
+            raise ValueError(f"min_T must be finite and >= 0, got {min_T}")
+        if abs_mean and n_ch > 16:
+            raise ValueError(f"abs_mean takes at most 16 channels (the absolute sums are not linear in them), got {n_ch}")
+        if out is not None and (tuple(out.shape) != (n, 8) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous float32 tensor of shape [{n}, 8] on the scene's device")
+        gm = grad_map.detach().to(torch.float32).contiguous()
+        gt = grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None
+
+        def result(buf, in_scene_order):
+            g = buf if in_scene_order else file_order_gradient(buf, self.scene.order_t)
+            return SplatGradient(g[:, 1:3], g[:, 3:6], g[:, 0], g[:, 6:8] if abs_mean else None)
+
+        if n == 0 or gm.numel() == 0:  # nothing to draw, or a shard that owns no tile row
+            return result(out if out is not None else torch.zeros((n, 8), dtype=torch.float32, device=dev), out is not None or scene_order)
+        rows = self._feature_rows(features.detach(), scene_order)
+        tail = (rows.data_ptr(), int(rows.stride(0)), n_ch, gm.data_ptr(), gt.data_ptr() if gt is not None else None, float(min_T),
+                int(bool(abs_mean)))
+        if out is None:
+            buf = torch.empty((n, 8), dtype=torch.float32, device=dev)
+
+            def attempt(o):  # a re-run after an overflow starts from zero again
+                buf.zero_()
+                self._enqueue_view(cam, o, lib.gsr_render_splat_backward, buf, *tail, buf.data_ptr())
+
+            _render_checked([self], [None], opts, attempt, 8, "splat gradient")
+            return result(buf, scene_order)
+        o = self._checked_lists(cam, opts, "splat gradient")
+        self._blend_lists(cam, o, lib.gsr_blend_splat_backward, *tail, out.data_ptr())
+        return result(out, True)
 
     def blend_weights(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[n]: every gaussian's blend weight summed over the drawn pixels of this view, sum_p w_i(p) — feature_gradient of a
