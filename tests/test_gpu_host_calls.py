@@ -1,5 +1,6 @@
-"""GPU: what the host side of every public single-view call of Rasterizer asks of libgsr — which entries, in which order, with which
-options — read off a recording proxy around renderer.lib that forwards every call to the real library.
+"""GPU: what the host side of every public single-view call of Rasterizer, and of its calls that take several views per launch
+sequence, asks of libgsr — which entries, in which order, with which options — read off a recording proxy around renderer.lib that
+forwards every call to the real library.
 
 Three things per call, none of them a number the code under test produces:
   a. the entry sequence, written out below (CALLS);
@@ -10,7 +11,11 @@ Three things per call, none of them a number the code under test produces:
      are held to the bar test_gpu_channels_backward applies between two runs of one gradient; a caller's `out` ends as what it
      held before plus ONE view's contribution: the overflowed first attempt added nothing.
 
-Scene: gpu_cases.deep_tile_scene, 40 x 24 (1000 gaussians, two tile rows).
+Scene: gpu_cases.deep_tile_scene, 40 x 24 (1000 gaussians, two tile rows).  The batch rows (BATCH) take the one camera three times
+through a Rasterizer(views=2): two groups, 2 + 1 views, the smallest case with a second group and a slice that is reset.  There
+stats() reads one slice per view of the group; render_batch and render_features_batch are one entry for all groups, the other
+two check each group's lists (gsr_lists_views) before the group's blend adds, with or without `out`; an `out` ends as what it
+held before plus exactly the three views.
 """
 import pytest
 import torch
@@ -40,8 +45,16 @@ CALLS = {
     "gradient_out": ((), LISTS, ("gsr_blend_channels_backward",)),
     "weights_out": ((), LISTS, ("gsr_blend_channels_backward",)),
     "view_stats_out": ((), LISTS, ("gsr_blend_gaussian_stats",)),
+    "render_batch": ((), ("gsr_render_batch",), ()),
+    "features_batch5": ((), ("gsr_render_channels_batch",), ()),
+    "gradient_batch": ((), ("gsr_lists_views",), ("gsr_blend_channels_backward_views",)),
+    "view_stats_batch": ((), ("gsr_lists_views",), ("gsr_blend_gaussian_stats_views",)),
+    "gradient_batch_out": ((), ("gsr_lists_views",), ("gsr_blend_channels_backward_views",)),
+    "view_stats_batch_out": ((), ("gsr_lists_views",), ("gsr_blend_gaussian_stats_views",)),
 }
-ATOMIC = {"gradient": (0,), "weights": (0,), "view_stats": (0,)}  # outputs that are float atomic sums, by position in the result
+BATCH = tuple(name for name in CALLS if "batch" in name)  # three cameras through a Rasterizer(views=2); for these the triple is per group
+# outputs that are float atomic sums, by position in the result
+ATOMIC = {"gradient": (0,), "weights": (0,), "view_stats": (0,), "gradient_batch": (0,), "view_stats_batch": (0,)}
 
 
 class _Recorder:
@@ -83,9 +96,12 @@ def S():
     s.scene = renderer.GaussianScene.from_packed(packed)
     s.R = renderer.Rasterizer(s.scene)
     s.R.render(s.cam)
+    s.R2 = renderer.Rasterizer(s.scene, views=2)
+    s.R2.render(s.cam)
     gen = torch.Generator().manual_seed(23)
     s.F = torch.randn((s.scene.n, 5), generator=gen).cuda()
     s.G = torch.randn((s.cam.height, s.cam.width, 5), generator=gen).cuda()
+    s.G3 = torch.randn((3, s.cam.height, s.cam.width, 5), generator=gen).cuda()
     s.roomy = {}
     return s
 
@@ -103,12 +119,14 @@ def _rows(S, o):
 
 
 def _flat(res):
-    return [t for t in (res if isinstance(res, tuple) else (res,)) if t is not None]
+    """The tensors of a result, in order (view_stats_batch nests a ViewStats)."""
+    return [t for r in (res if isinstance(res, tuple) else (res,)) if r is not None for t in (_flat(r) if isinstance(r, tuple) else (r,))]
 
 
 def _run(S, R, name, o, outs=None):
     """One public call by its CALLS name -> the list of tensors it returns.  `outs`: the buffers of an accumulating call."""
     cam, rows, VS = S.cam, _rows(S, o), S.renderer.ViewStats
+    cams = [cam] * 3
     plane = lambda v: torch.full((rows, cam.width), v, dtype=torch.float32, device="cuda")
     if name.endswith("_out") and outs is None:
         outs = _zero_outs(S, name)
@@ -129,43 +147,66 @@ def _run(S, R, name, o, outs=None):
         "gradient_out": lambda: R.feature_gradient(cam, S.G[:rows], o, out=outs[0]),
         "weights_out": lambda: R.blend_weights(cam, o, out=outs[0]),
         "view_stats_out": lambda: R.view_stats(cam, o, out=VS(*outs)),
+        "render_batch": lambda: R.render_batch(cams, o),
+        "features_batch5": lambda: R.render_features_batch(cams, S.F, o, return_T=True),
+        "gradient_batch": lambda: R.feature_gradient_batch(cams, S.G3[:, :rows], o, scene_order=True),
+        "view_stats_batch": lambda: R.view_stats_batch(cams, o, scene_order=True),
+        "gradient_batch_out": lambda: R.feature_gradient_batch(cams, S.G3[:, :rows], o, out=outs[0]),
+        "view_stats_batch_out": lambda: R.view_stats_batch(cams, o, out=(VS(*outs[:3]), outs[3])),
     }[name]
     return _flat(call())
 
 
 def _zero_outs(S, name):
     n = S.scene.n
-    if name == "gradient_out":
+    if name in ("gradient_out", "gradient_batch_out"):
         return [torch.zeros((n, 5), device="cuda")]
     if name == "weights_out":
         return [torch.zeros(n, device="cuda")]
-    return [torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda"), torch.zeros(n, dtype=torch.int32, device="cuda")]
+    counts = 2 if name == "view_stats_batch_out" else 1  # pixels, and the batch's views
+    return [torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")] + [torch.zeros(n, dtype=torch.int32, device="cuda") for _ in range(counts)]
 
 
 def _sequence(name, attempts):
     pre, attempt, post = CALLS[name]
-    return pre + (attempt + STATS) * attempts + post
+    if name not in BATCH:
+        return pre + (attempt + STATS) * attempts + post
+    if not post:  # one entry for both groups; stats() then reads the two slices
+        return (attempt + STATS * 2) * attempts
+    # two phases per group: the first group's lists run `attempts` times, the second group (one view) finds the room they made
+    return (attempt + STATS * 2) * attempts + post + attempt + STATS + post
+
+
+def _adds_after_the_check(name):
+    """The call's blend adds into a buffer, so it runs after its lists were checked: with `out`, and the two batches always."""
+    return name.endswith("_out") or name in ("gradient_batch", "view_stats_batch")
+
+
+def _rasterizer(S, name):
+    return S.R2 if name in BATCH else S.R
 
 
 def _check_closing_blend(rec, name):
     """An accumulating call's blend runs once, after the last check, with colour_stage = 0 and the depth-sort bound its lists got."""
     (blend, bo), (sort, so) = rec.calls[-1], rec.calls[-3]
-    assert blend == CALLS[name][2][0] and sort == "gsr_bin_sort", rec.names()
+    assert blend == CALLS[name][2][0] and sort == ("gsr_lists_views" if name in BATCH else "gsr_bin_sort"), rec.names()
     assert bo["colour_stage"] == 0 and bo["depth_sort_passes"] == so["depth_sort_passes"], (name, bo, so)
 
 
 @pytest.mark.parametrize("name", list(CALLS))
 def test_entries_and_chaining(S, rec, name):
-    R, mk = S.R, S.renderer.make_options
+    R, mk = _rasterizer(S, name), S.renderer.make_options
     assert R.unchecked.slices == 0
     # a. nothing unchecked: the sequence, and no struct asks to keep a record.  The accumulating calls get colour_stage = 1 from the
     #    caller, which their lists and their blend must not run with.
-    _run(S, R, name, mk(colour_stage=1) if name.endswith("_out") else mk())
+    _run(S, R, name, mk(colour_stage=1) if _adds_after_the_check(name) else mk())
     assert rec.names() == _sequence(name, 1), name
     assert rec.options_before_the_first_check() and all(o["keep_flags"] == 0 for o in rec.options_before_the_first_check()), name
     assert R.sort_passes > 0 and all(o["depth_sort_passes"] == R.sort_passes for o in rec.options_before_the_first_check()), name
-    if name.endswith("_out"):
+    if _adds_after_the_check(name):
         _check_closing_blend(rec, name)
+    if name in BATCH:  # every struct of the call, the second group's included
+        assert all(o["keep_flags"] == 0 for _, o in rec.calls if o is not None), name
     # b. one frame enqueued and not read: the call adds to its record
     R.enqueue(S.cam)
     assert R.unchecked.slices == 1
@@ -174,6 +215,8 @@ def test_entries_and_chaining(S, rec, name):
     assert rec.names() == _sequence(name, 1), name
     assert rec.options_before_the_first_check() and all(o["keep_flags"] == 1 for o in rec.options_before_the_first_check()), name
     assert R.unchecked.slices == 0
+    if name in BATCH:  # the first group adds to the record (its blend runs with its lists' options); the second starts from a read one
+        assert [o["keep_flags"] for _, o in rec.calls if o is not None] == ([1, 1, 0, 0] if CALLS[name][2] else [1]), name
     # a shard without tile rows (two tile rows, the third of three shards): no render, list or blend entry is called
     del rec.calls[:]
     outs = [torch.full_like(t, 3) for t in _zero_outs(S, name)] if name.endswith("_out") else None
@@ -190,7 +233,7 @@ def _roomy(S, name):
     """What the roomy rasterizer returns for the call (scene order), computed once."""
     base = name[:-4] if name.endswith("_out") else name
     if base not in S.roomy:
-        S.roomy[base] = _run(S, S.R, base, S.renderer.make_options())
+        S.roomy[base] = _run(S, _rasterizer(S, base), base, S.renderer.make_options())
     return S.roomy[base]
 
 
@@ -198,11 +241,13 @@ def _roomy(S, name):
 def test_an_overflowed_attempt_is_run_again_and_leaves_no_trace(S, rec, name):
     ref = _roomy(S, name)
     del rec.calls[:]
-    small = S.renderer.Rasterizer(S.scene, max_pairs=64)
+    small = S.renderer.Rasterizer(S.scene, max_pairs=64, views=2 if name in BATCH else 1)
     if not name.endswith("_out"):
         got = _run(S, small, name, S.renderer.make_options())
         assert rec.names() == _sequence(name, 2), (name, rec.names())
         assert small.max_pairs > 64
+        if _adds_after_the_check(name):
+            _check_closing_blend(rec, name)
         assert len(got) == len(ref)
         for k, (g, r) in enumerate(zip(got, ref)):
             if k in ATOMIC.get(name, ()):
@@ -216,15 +261,15 @@ def test_an_overflowed_attempt_is_run_again_and_leaves_no_trace(S, rec, name):
         o_t = S.scene.order_t
         ref = ref if o_t is None else [ref[0].index_select(0, o_t)]
     outs = [ref[0].clone()]
-    if name == "view_stats_out":
+    if name in ("view_stats_out", "view_stats_batch_out"):
         mid = float(ref[1][ref[1] > 0].median())
-        outs += [torch.full_like(ref[1], mid), torch.full_like(ref[2], 7)]
+        outs += [torch.full_like(ref[1], mid)] + [torch.full_like(r, 7) for r in ref[2:]]
     got = _run(S, small, name, S.renderer.make_options(), outs)
     assert rec.names() == _sequence(name, 2), (name, rec.names())
     assert small.max_pairs > 64
     _check_closing_blend(rec, name)
     assert all(g is o for g, o in zip(got, outs))
     _bar(f"{name} sum after a retry", outs[0].cpu().numpy(), 2.0 * ref[0].double().cpu().numpy())
-    if name == "view_stats_out":
+    if name in ("view_stats_out", "view_stats_batch_out"):
         assert bool((ref[1] > mid).any()) and bool(((ref[1] > 0) & (ref[1] < mid)).any())
-        assert torch.equal(outs[1], torch.clamp(ref[1], min=mid)) and torch.equal(outs[2], ref[2] + 7)
+        assert torch.equal(outs[1], torch.clamp(ref[1], min=mid)) and all(torch.equal(o, r + 7) for o, r in zip(outs[2:], ref[2:]))

@@ -354,20 +354,97 @@ int gsr_bin_sort(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_
     return bin_sort_impl(opts, ws, plan_frame(ws, *opts), static_cast<hipStream_t>(stream));
 }
 
+// A scene named beside lists of n gaussians (gsr_blend, gsr_blend_slab): check_scene's refusals, and the lists must be its own
+static int check_scene_of_lists(const GsrScene *scene, int64_t n)
+{
+    const int rc = check_scene(scene);
+    if (rc) return rc;
+    if (scene->n != n) { set_error("scene->n = %lld but n = %lld", (long long)scene->n, (long long)n); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
 int gsr_blend(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
               size_t workspace_bytes, void *out_image, float *out_final_T, void *stream)
 {
     if (!out_image) { set_error("null output image"); return GSR_ERR_BAD_ARG; }
-    if (scene) {
-        const int rc = check_scene(scene);
-        if (rc) return rc;
-        if (scene->n != n) { set_error("scene->n = %lld but n = %lld", (long long)scene->n, (long long)n); return GSR_ERR_BAD_ARG; }
-    }
+    int rc = scene ? check_scene_of_lists(scene, n) : GSR_OK;
+    if (rc) return rc;
     Workspace ws;
-    int rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
+    rc = check_frame(n, cam, opts, max_pairs, workspace, workspace_bytes, &ws);
     if (rc) return rc;
     return launch_blend(*cam, *opts, ws, plan_frame(ws, *opts), out_image, 0, out_final_T, scene, static_cast<hipStream_t>(stream));
 }
+
+// ---- what the entries that take several cameras say about them, once each ----------------------------------------------------
+// Every camera has the first one's frame size, or `wording` is the refusal (the frame batches and the view entries word it
+// differently).  refuse_empty: a camera without pixels is refused as the loop comes to it (the frame batches)
+static int check_one_frame_size(const GsrCamera *cams, int32_t n_cams, const char *wording, bool refuse_empty = false)
+{
+    for (int32_t i = 0; i < n_cams; ++i) {
+        if (refuse_empty && (cams[i].width <= 0 || cams[i].height <= 0)) { set_error("bad frame size %dx%d", cams[i].width, cams[i].height); return GSR_ERR_BAD_ARG; }
+        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) { set_error("%s", wording); return GSR_ERR_BAD_ARG; }
+    }
+    return GSR_OK;
+}
+
+// Pixels of one view's plane: the frame, or (output_layout = 2) the strip of the shard's tile rows.  0 for sizes check_frame
+// refuses; a shard check_frame refuses counts as the whole frame
+static int64_t view_plane_pixels(const GsrCamera &cam, const GsrOptions &opts)
+{
+    if (cam.width <= 0 || cam.height <= 0) return 0;
+    int64_t rows_px = cam.height;
+    if (opts.output_layout == 2 && opts.tile_row_step >= 0 && opts.tile_row_begin >= 0) {
+        const int tiles_y = (cam.height + GSR_TILE - 1) / GSR_TILE;
+        rows_px = (int64_t)row_shard_of(opts).rows_before(tiles_y) * GSR_TILE;
+    }
+    return (int64_t)cam.width * rows_px;
+}
+
+// The frame's checks for n_views views in slices 0 .. n_views - 1 of the workspace; *ws describes them (check_frame's, with the views)
+static int check_view_slices(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, Workspace *ws)
+{
+    const int rc = check_frame(n, &cams[0], opts, max_pairs, workspace, workspace_bytes, ws);
+    if (rc) return rc;
+    if (workspace_bytes / ws->bytes < (size_t)n_views) {
+        set_error("workspace too small for %d views per launch: %zu bytes given, %zu needed", (int)n_views, workspace_bytes, ws->bytes * (size_t)n_views);
+        return GSR_ERR_WORKSPACE;
+    }
+    if (n_views > 1) {
+        ws->views = n_views;
+        ws->view_stride = ws->bytes;
+    }
+    return GSR_OK;
+}
+
+// How many views go through one launch sequence: as many slices as the workspace holds, at most MAX_VIEWS, GsrOptions.batch_views
+// (when set) and the views there are.  0: the workspace does not hold one view.
+static int views_per_launch(const GsrScene *scene, const GsrCamera *cam0, const GsrOptions *opts, int64_t max_pairs, size_t workspace_bytes, int32_t n_cams)
+{
+    Workspace ws;
+    const size_t per = carve_workspace(nullptr, scene->n, cam0->width, cam0->height, max_pairs, &ws);
+    size_t k = workspace_bytes / per;
+    k = std::min<size_t>(k, (size_t)MAX_VIEWS);
+    if (opts->batch_views > 0) k = std::min<size_t>(k, (size_t)opts->batch_views);
+    return (int)std::min<size_t>(k, (size_t)std::max<int32_t>(n_cams, 1));
+}
+
+// The cameras of a batch, K per launch sequence: group(first camera, how many, the group's number) until one fails.  K = 0: the
+// workspace does not hold one view — groups of one, and the first group's own checks report it.  Whose control blocks a group finds
+// used is the caller's to say from the group's number: a slice's first view clears its whole block, the views that follow in later
+// groups keep the batch-sticky overflow words (reset_words_of)
+extern "C++" {
+template <class Group>
+static int for_view_groups(int32_t n_cams, int K, Group group)
+{
+    int32_t g = 0;
+    for (int32_t i = 0; i < n_cams; i += std::max(K, 1), ++g) {
+        const int rc = group(i, std::max(1, std::min<int32_t>(K, n_cams - i)), g);
+        if (rc) return rc;
+    }
+    return GSR_OK;
+}
+}  // extern "C++"
 
 // Stages 1-3 for `views` cameras through ONE launch sequence: view v works in slice v of the workspace (slices of
 // gsr_workspace_bytes() bytes) and renders into out_images + v * out_view_stride bytes.
@@ -380,16 +457,8 @@ static int render_views(const GsrScene *scene, const GsrCamera *cams, int views,
     if (!out_images) { set_error("null output image"); return GSR_ERR_BAD_ARG; }
     if (!cams || views < 1 || views > MAX_VIEWS || (views > 1 && out_final_T)) { set_error("bad view count %d", views); return GSR_ERR_BAD_ARG; }
     Workspace ws;
-    rc = check_frame(scene->n, &cams[0], opts, max_pairs, workspace, workspace_bytes, &ws);
+    rc = check_view_slices(scene->n, cams, views, opts, max_pairs, workspace, workspace_bytes, &ws);
     if (rc) return rc;
-    if (views > 1) {
-        if (workspace_bytes / ws.bytes < (size_t)views) {
-            set_error("workspace too small for %d views per launch: %zu bytes given, %zu needed", views, workspace_bytes, ws.bytes * (size_t)views);
-            return GSR_ERR_WORKSPACE;
-        }
-        ws.views = views;
-        ws.view_stride = ws.bytes;
-    }
     const FramePlan plan = plan_frame(ws, *opts);
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = launch_preprocess(*scene, cams, *opts, ws, plan, nullptr, reset_words_of(opts, keep_batch_words), s);
@@ -407,25 +476,257 @@ int gsr_render_forward(const GsrScene *scene, const GsrCamera *cam, const GsrOpt
     return render_views(scene, cam, 1, opts, max_pairs, workspace, workspace_bytes, out_image, 0, out_final_T, stream, false);
 }
 
-// What gsr_blend_features / gsr_render_features refuse before anything else (and before any HIP call)
-static int check_features(const GsrCamera *cam, const GsrOptions *opts, const float *features, const float *out_map)
+static int check_batch(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs, const void *out_images,
+                       int64_t frame_stride)
 {
-    if (!cam || !opts) { set_error("null camera/options"); return GSR_ERR_BAD_ARG; }
-    if (!features) { set_error("null features"); return GSR_ERR_BAD_ARG; }
-    if (!out_map) { set_error("null output map"); return GSR_ERR_BAD_ARG; }
-    if (opts->output_dtype == 1) { set_error("feature maps are float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    if (opts->accum_dtype == 1) { set_error("feature maps are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (!scene || !cams || n_cams < 0 || !out_images || !opts) { set_error("bad argument"); return GSR_ERR_BAD_ARG; }
+    if (scene->n < 0 || scene->n > 0x7FFFFFFF || max_pairs < 0) { set_error("bad argument"); return GSR_ERR_BAD_ARG; }
+    const int rc = check_one_frame_size(cams, n_cams, "views of a batch must share one frame size", true);
+    if (rc) return rc;
+    // what one view writes: the frame, or (output_layout = 2) the strip of its shard's tile rows
+    if (n_cams > 0 && frame_stride < view_plane_pixels(cams[0], *opts) * 3) { set_error("frame_stride smaller than a frame"); return GSR_ERR_BAD_ARG; }
     return GSR_OK;
 }
 
-// What every gsr_blend_X / gsr_render_X pair does behind its own argument checks: check_scene (when a scene is given), the frame's
-// checks, the plan, and launch(cam, opts, ws, plan, s) on the lists — those already in the workspace (scene == nullptr: n
-// gaussians), or the ones made here from the scene: stages 1 and 2 with colour_stage = 0 (nobody here needs a colour: the
-// preprocess reads no SH row, the records keep their "unevaluated" marks).
+// The frames of a checked batch, group g in slot g % n_slots (its workspace, its stream): the slot's first group finds its slices
+// unused, whatever g its later ones have
+static int render_groups(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs,
+                         void *const *workspaces, size_t workspace_bytes, void *const *streams, int32_t n_slots, void *out_images, int64_t frame_stride)
+{
+    const size_t fbytes = (size_t)frame_stride * (opts->output_dtype == 1 ? 2 : 4);
+    return for_view_groups(n_cams, views_per_launch(scene, &cams[0], opts, max_pairs, workspace_bytes, n_cams), [&](int32_t first, int count, int32_t g) {
+        return render_views(scene, &cams[first], count, opts, max_pairs, workspaces[g % n_slots], workspace_bytes,
+                            static_cast<char *>(out_images) + (size_t)first * fbytes, fbytes, nullptr, streams[g % n_slots], g >= n_slots);
+    });
+}
+
+int gsr_render_batch(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs,
+                     void *workspace, size_t workspace_bytes, void *out_images, int64_t frame_stride, void *stream)
+{
+    const int rc = check_batch(scene, cams, n_cams, opts, max_pairs, out_images, frame_stride);
+    if (rc || n_cams == 0) return rc;
+    return render_groups(scene, cams, n_cams, opts, max_pairs, &workspace, workspace_bytes, &stream, 1, out_images, frame_stride);
+}
+
+int gsr_render_batch_slots(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs,
+                           void *const *workspaces, size_t workspace_bytes, void *const *streams, int32_t n_slots, void *out_images,
+                           int64_t frame_stride)
+{
+    if (!workspaces || !streams || n_slots < 1) { set_error("bad argument"); return GSR_ERR_BAD_ARG; }
+    const int rc = check_batch(scene, cams, n_cams, opts, max_pairs, out_images, frame_stride);
+    if (rc) return rc;
+    for (int32_t k = 0; k < n_slots; ++k) {
+        if (!workspaces[k]) { set_error("null workspace in slot %d", (int)k); return GSR_ERR_BAD_ARG; }
+        for (int32_t j = 0; j < k; ++j)
+            if (workspaces[j] == workspaces[k]) { set_error("slots %d and %d share a workspace", (int)j, (int)k); return GSR_ERR_BAD_ARG; }
+    }
+    if (n_cams == 0) return GSR_OK;
+    return render_groups(scene, cams, n_cams, opts, max_pairs, workspaces, workspace_bytes, streams, n_slots, out_images, frame_stride);
+}
+
+// ---- list consumers: blends that walk the colour frame's tile lists and do something of their own with the weights ------------
+// One struct per kind holds the call's own arguments in the order its entries take them (a view stride is 0 where one view is all
+// there is) and says
+//   check(cam, opts)                    what the kind refuses before anything else, and before any HIP call, in this order;
+//   launch(lists)                       its blend over them;
+//   check_view_strides(plane, n_views)  where the kind takes several views per launch sequence: its strides against a view's plane.
+// The entries below are one call each of the runners behind the structs.  DESIGN.md section 5.26 says what a new kind writes.
 extern "C++" {  // (templates cannot have C linkage)
-template <class Launch>
-static int run_on_lists(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs,
-                        void *workspace, size_t workspace_bytes, void *stream, Launch launch)
+struct Lists {  // what a consumer walks: the (first) view, the options the lists were made with, where they lie, the frame's plan, the stream
+    const GsrCamera &cam; const GsrOptions &opts; const Workspace &ws; const FramePlan &plan; hipStream_t s;
+};
+
+static int check_camera_options(const GsrCamera *cam, const GsrOptions *opts)
+{
+    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
+    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+// `channels` values per row, rows `stride` floats apart (`name`: what the entry calls the stride)
+static int check_channel_rows(int32_t channels, const char *name, int64_t stride)
+{
+    if (channels < 1 || channels > GSR_MAX_FEATURE_CHANNELS) {
+        set_error("bad channels %d (1 .. %d)", channels, GSR_MAX_FEATURE_CHANNELS); return GSR_ERR_BAD_ARG;
+    }
+    if (stride < channels) { set_error("bad %s %lld: rows of %d channels overlap", name, (long long)stride, channels); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+// No consumer stores or accumulates bfloat16: "<outputs_are>: output_dtype = 1 ..." and "<sums_are> accumulated in float32: ..."
+static int refuse_bf16(const GsrOptions *opts, const char *outputs_are, const char *sums_are)
+{
+    if (opts->output_dtype == 1) { set_error("%s: output_dtype = 1 (bfloat16) is not supported", outputs_are); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("%s accumulated in float32: accum_dtype = 1 (bfloat16) is not supported", sums_are); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+static int check_view_stride(const char *name, int64_t stride, int64_t need, int32_t n_views, const char *what)
+{
+    if (n_views > 1 && stride < need) { set_error("bad %s %lld: smaller than %s (%lld)", name, (long long)stride, what, (long long)need); return GSR_ERR_BAD_ARG; }
+    return GSR_OK;
+}
+
+struct Features {  // three channels
+    const float *features; float *out_map, *out_final_T;
+    int check(const GsrCamera *cam, const GsrOptions *opts) const
+    {
+        if (!cam || !opts) { set_error("null camera/options"); return GSR_ERR_BAD_ARG; }
+        if (!features) { set_error("null features"); return GSR_ERR_BAD_ARG; }
+        if (!out_map) { set_error("null output map"); return GSR_ERR_BAD_ARG; }
+        return refuse_bf16(opts, "feature maps are float32", "feature maps are");
+    }
+    int launch(const Lists &l) const { return launch_blend_features(l.cam, l.opts, l.ws, l.plan, features, out_map, out_final_T, l.s); }
+};
+
+struct Channels {  // any number of channels; view v writes out_map + v * map_stride and out_final_T + v * T_stride
+    const float *features; int32_t channels; int64_t feature_stride;
+    float *out_map, *out_final_T; int64_t map_stride, T_stride;
+    int check(const GsrCamera *cam, const GsrOptions *opts) const
+    {
+        int rc = check_camera_options(cam, opts);
+        if (rc) return rc;
+        if (!features) { set_error("null features"); return GSR_ERR_BAD_ARG; }
+        if (!out_map) { set_error("null output map"); return GSR_ERR_BAD_ARG; }
+        rc = check_channel_rows(channels, "feature_stride", feature_stride);
+        return rc ? rc : refuse_bf16(opts, "feature maps are float32", "feature maps are");
+    }
+    int check_view_strides(int64_t plane, int32_t n_views) const
+    {
+        const int rc = check_view_stride("map_stride", map_stride, plane * channels, n_views, "a view's map");
+        if (rc) return rc;
+        return out_final_T ? check_view_stride("T_stride", T_stride, plane, n_views, "a view's final-T plane") : GSR_OK;
+    }
+    Channels from_view(int32_t v) const  // the same call for the views from v on
+    {
+        Channels c = *this;
+        c.out_map += (size_t)v * (size_t)map_stride;
+        if (out_final_T) c.out_final_T += (size_t)v * (size_t)T_stride;
+        return c;
+    }
+    int launch(const Lists &l) const
+    {
+        return launch_blend_channels(l.cam, l.opts, l.ws, l.plan, features, channels, feature_stride, out_map, out_final_T, l.s, map_stride, T_stride);
+    }
+};
+
+struct Slab {  // Channels between two depth planes, either of which may be null; scene: whose means give the depths (null: the preprocess's)
+    Channels maps; const GsrScene *scene; const float *depth_near, *depth_far;
+    int check(const GsrCamera *cam, const GsrOptions *opts) const { return maps.check(cam, opts); }
+    int launch(const Lists &l) const
+    {
+        return launch_blend_slab(l.cam, l.opts, l.ws, l.plan, scene ? scene->means : nullptr, maps.features, maps.channels, maps.feature_stride,
+                                 depth_near, depth_far, maps.out_map, maps.out_final_T, l.s);
+    }
+};
+
+struct ChannelsBackward {  // view v reads grad_map + v * map_stride; all add into the one grad_features
+    const float *grad_map; int32_t channels; float *grad_features; int64_t grad_stride, map_stride;
+    int check(const GsrCamera *cam, const GsrOptions *opts) const
+    {
+        int rc = check_camera_options(cam, opts);
+        if (rc) return rc;
+        if (!grad_map) { set_error("null gradient map"); return GSR_ERR_BAD_ARG; }
+        if (!grad_features) { set_error("null feature gradient"); return GSR_ERR_BAD_ARG; }
+        rc = check_channel_rows(channels, "grad_stride", grad_stride);
+        return rc ? rc : refuse_bf16(opts, "gradient maps are float32", "feature gradients are");
+    }
+    int check_view_strides(int64_t plane, int32_t n_views) const
+    {
+        return check_view_stride("map_stride", map_stride, plane * channels, n_views, "a view's gradient map");
+    }
+    int launch(const Lists &l) const { return launch_blend_channels_backward(l.cam, l.opts, l.ws, l.plan, grad_map, channels, grad_features, grad_stride, l.s, map_stride); }
+};
+
+struct SplatBackward {
+    const float *features; int64_t feature_stride; int32_t channels;
+    const float *grad_map, *grad_T; float min_T; int32_t want_abs; float *grad_splat;
+    int check(const GsrCamera *cam, const GsrOptions *opts) const
+    {
+        int rc = check_camera_options(cam, opts);
+        if (rc) return rc;
+        if (!features) { set_error("null features"); return GSR_ERR_BAD_ARG; }
+        if (!grad_map) { set_error("null gradient map"); return GSR_ERR_BAD_ARG; }
+        if (!grad_splat) { set_error("null splat gradient"); return GSR_ERR_BAD_ARG; }
+        rc = check_channel_rows(channels, "feature_stride", feature_stride);
+        if (rc) return rc;
+        if (!(min_T >= 0.0f) || min_T > 3.4028234e38f) { set_error("bad min_T %g: a finite value >= 0", (double)min_T); return GSR_ERR_BAD_ARG; }
+        if (want_abs && channels > 16) {
+            set_error("want_abs with %d channels: the absolute sums are not linear in the channels, one walk of at most 16", channels);
+            return GSR_ERR_BAD_ARG;
+        }
+        return refuse_bf16(opts, "gradient maps are float32", "splat gradients are");
+    }
+    int launch(const Lists &l) const
+    {
+        return launch_blend_splat_backward(l.cam, l.opts, l.ws, l.plan, features, feature_stride, channels, grad_map, grad_T, min_T, want_abs != 0, grad_splat, l.s);
+    }
+};
+
+struct GaussianStats {  // view v reads pixel_mask + v * mask_stride; view_hits / view_bits: the form for several views alone (several)
+    const uint8_t *pixel_mask; float *weight_sum, *weight_max; uint32_t *pixels;
+    int64_t mask_stride; uint32_t *view_hits, *view_bits; bool several;
+    int check(const GsrCamera *cam, const GsrOptions *opts) const
+    {
+        const int rc = check_camera_options(cam, opts);
+        if (rc) return rc;
+        if (!weight_sum && !weight_max && !pixels && !view_hits) {
+            set_error("null statistics outputs: all %s", several ? "four" : "three"); return GSR_ERR_BAD_ARG;
+        }
+        if (view_hits && !view_bits) { set_error("view_hits needs the view_bits scratch"); return GSR_ERR_BAD_ARG; }
+        if (!view_hits && view_bits) { set_error("a view_bits scratch without view_hits"); return GSR_ERR_BAD_ARG; }
+        return refuse_bf16(opts, "gaussian statistics are float32 / uint32", "the weights are");
+    }
+    int check_view_strides(int64_t plane, int32_t n_views) const
+    {
+        return pixel_mask ? check_view_stride("mask_stride", mask_stride, plane, n_views, "a view's mask plane") : GSR_OK;
+    }
+    int launch(const Lists &l) const
+    {
+        // the scratch is this launch sequence's: bit v = view v has counted the gaussian
+        if (view_hits && l.ws.n > 0) GSR_HIP(hipMemsetAsync(view_bits, 0, sizeof(uint32_t) * (size_t)l.ws.n, l.s));
+        return launch_blend_gstats(l.cam, l.opts, l.ws, l.plan, pixel_mask, weight_sum, weight_max, pixels, l.s, mask_stride, view_hits, view_bits);
+    }
+};
+
+struct Pick {
+    float median_T; int32_t *out_best_id; float *out_best_w; int32_t *out_median_id, *out_count;
+    int check(const GsrCamera *cam, const GsrOptions *opts) const
+    {
+        const int rc = check_camera_options(cam, opts);
+        if (rc) return rc;
+        if (!out_best_id && !out_best_w && !out_median_id && !out_count) { set_error("null pick outputs: all four"); return GSR_ERR_BAD_ARG; }
+        if (!(median_T > 0.0f && median_T <= 1.0f)) {  // (a NaN fails both compares)
+            set_error("bad median_T %g (0 < median_T <= 1)", (double)median_T); return GSR_ERR_BAD_ARG;
+        }
+        return refuse_bf16(opts, "pick maps are int32 / float32", "pick weights are");
+    }
+    int launch(const Lists &l) const { return launch_blend_pick(l.cam, l.opts, l.ws, l.plan, median_T, out_best_id, out_best_w, out_median_id, out_count, l.s); }
+};
+
+struct TopK {
+    int32_t k, select, *out_ids; float *out_weights, *out_final_T;
+    int check(const GsrCamera *cam, const GsrOptions *opts) const
+    {
+        const int rc = check_camera_options(cam, opts);
+        if (rc) return rc;
+        if (!out_ids && !out_weights) { set_error("null top-k outputs: both ids and weights"); return GSR_ERR_BAD_ARG; }
+        if (k < 1 || k > GSR_MAX_TOPK) { set_error("bad k %d (1 .. %d)", k, GSR_MAX_TOPK); return GSR_ERR_BAD_ARG; }
+        if (select != GSR_TOPK_HEAVIEST && select != GSR_TOPK_NEAREST) {
+            set_error("bad select %d (GSR_TOPK_HEAVIEST = 0, GSR_TOPK_NEAREST = 1)", select); return GSR_ERR_BAD_ARG;
+        }
+        return refuse_bf16(opts, "top-k lists are int32 / float32", "top-k weights are");
+    }
+    int launch(const Lists &l) const { return launch_blend_topk(l.cam, l.opts, l.ws, l.plan, k, select, out_ids, out_weights, out_final_T, l.s); }
+};
+
+// What every gsr_blend_X / gsr_render_X pair does behind the consumer's own checks: check_scene (when a scene is given), the frame's
+// checks, the plan, and the consumer's launch on the lists — those already in the workspace (scene == nullptr: n gaussians), or
+// the ones made here from the scene: stages 1 and 2 with colour_stage = 0 (nobody here needs a colour: the preprocess reads no SH
+// row, the records keep their "unevaluated" marks).
+template <class Consumer>
+static int on_lists(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                    size_t workspace_bytes, void *stream, const Consumer &c)
 {
     int rc = scene ? check_scene(scene) : GSR_OK;
     if (rc) return rc;
@@ -442,450 +743,163 @@ static int run_on_lists(const GsrScene *scene, int64_t n, const GsrCamera *cam, 
         rc = bin_sort_impl(&o, ws, plan, s);
         if (rc) return rc;
     }
-    return launch(*cam, o, ws, plan, s);
+    return c.launch(Lists{*cam, o, ws, plan, s});
 }
 
-// gsr_render_X: the scene is not optional ("null scene" is check_scene's to say)
-template <class Launch>
-static int render_on_lists(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
-                           size_t workspace_bytes, void *stream, Launch launch)
+// gsr_blend_X: the consumer's checks, then its blend over the lists of n gaussians in the workspace
+template <class Consumer>
+static int run_on_lists(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
+                        void *stream, const Consumer &c)
 {
+    const int rc = c.check(cam, opts);
+    return rc ? rc : on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream, c);
+}
+
+// gsr_render_X: the consumer's checks, then stages 1-2 and its blend; the scene is not optional ("null scene" is check_scene's to say)
+template <class Consumer>
+static int render_on_lists(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                           size_t workspace_bytes, void *stream, const Consumer &c)
+{
+    const int rc = c.check(cam, opts);
+    if (rc) return rc;
     if (!scene) return check_scene(scene);
-    return run_on_lists(scene, 0, cam, opts, max_pairs, workspace, workspace_bytes, stream, launch);
+    return on_lists(scene, 0, cam, opts, max_pairs, workspace, workspace_bytes, stream, c);
 }
 }  // extern "C++"
 
 int gsr_blend_features(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
                        const float *features, float *out_map, float *out_final_T, void *stream)
 {
-    const int rc = check_features(cam, opts, features, out_map);
-    if (rc) return rc;
-    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_features(c, o, ws, plan, features, out_map, out_final_T, s);
-        });
+    return run_on_lists(n, cam, opts, max_pairs, workspace, workspace_bytes, stream, Features{features, out_map, out_final_T});
 }
 
 int gsr_render_features(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                         size_t workspace_bytes, const float *features, float *out_map, float *out_final_T, void *stream)
 {
-    const int rc = check_features(cam, opts, features, out_map);
-    if (rc) return rc;
-    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_features(c, o, ws, plan, features, out_map, out_final_T, s);
-        });
-}
-
-// What gsr_blend_channels / gsr_render_channels refuse before anything else (and before any HIP call)
-static int check_channels(const GsrCamera *cam, const GsrOptions *opts, const float *features, int32_t channels, int64_t feature_stride,
-                          const float *out_map)
-{
-    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
-    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
-    if (!features) { set_error("null features"); return GSR_ERR_BAD_ARG; }
-    if (!out_map) { set_error("null output map"); return GSR_ERR_BAD_ARG; }
-    if (channels < 1 || channels > GSR_MAX_FEATURE_CHANNELS) {
-        set_error("bad channels %d (1 .. %d)", channels, GSR_MAX_FEATURE_CHANNELS); return GSR_ERR_BAD_ARG;
-    }
-    if (feature_stride < channels) {
-        set_error("bad feature_stride %lld: rows of %d channels overlap", (long long)feature_stride, channels); return GSR_ERR_BAD_ARG;
-    }
-    if (opts->output_dtype == 1) { set_error("feature maps are float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    if (opts->accum_dtype == 1) { set_error("feature maps are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream, Features{features, out_map, out_final_T});
 }
 
 int gsr_blend_channels(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
                        const float *features, int32_t channels, int64_t feature_stride, float *out_map, float *out_final_T, void *stream)
 {
-    const int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
-    if (rc) return rc;
-    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_channels(c, o, ws, plan, features, channels, feature_stride, out_map, out_final_T, s);
-        });
+    return run_on_lists(n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+                        Channels{features, channels, feature_stride, out_map, out_final_T, 0, 0});
 }
 
 int gsr_render_channels(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                         size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, float *out_map,
                         float *out_final_T, void *stream)
 {
-    const int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
-    if (rc) return rc;
     return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_channels(c, o, ws, plan, features, channels, feature_stride, out_map, out_final_T, s);
-        });
+                           Channels{features, channels, feature_stride, out_map, out_final_T, 0, 0});
 }
 
-// gsr_blend_slab / gsr_render_slab refuse gsr_blend_channels' cases; the depth planes may be null.  gsr_blend_slab may name the scene
-// whose means it reads; it preprocesses nothing
+// gsr_blend_slab may name the scene whose means it reads, which must then be the lists' own; it preprocesses nothing
 int gsr_blend_slab(const GsrScene *scene, int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                    size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, const float *depth_near,
                    const float *depth_far, float *out_map, float *out_final_T, void *stream)
 {
-    int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
-    if (rc) return rc;
-    if (scene) {
-        rc = check_scene(scene);
-        if (rc) return rc;
-        if (scene->n != n) { set_error("scene->n = %lld but n = %lld", (long long)scene->n, (long long)n); return GSR_ERR_BAD_ARG; }
-    }
-    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_slab(c, o, ws, plan, scene ? scene->means : nullptr, features, channels, feature_stride, depth_near,
-                                     depth_far, out_map, out_final_T, s);
-        });
+    const Slab c{{features, channels, feature_stride, out_map, out_final_T, 0, 0}, scene, depth_near, depth_far};
+    int rc = c.check(cam, opts);
+    if (!rc && scene) rc = check_scene_of_lists(scene, n);
+    return rc ? rc : on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream, c);
 }
 
 int gsr_render_slab(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, const float *depth_near,
                     const float *depth_far, float *out_map, float *out_final_T, void *stream)
 {
-    const int rc = check_channels(cam, opts, features, channels, feature_stride, out_map);
-    if (rc) return rc;
     return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_slab(c, o, ws, plan, scene->means, features, channels, feature_stride, depth_near, depth_far, out_map,
-                                     out_final_T, s);
-        });
-}
-
-// What gsr_blend_channels_backward / gsr_render_channels_backward refuse before anything else (and before any HIP call)
-static int check_channels_backward(const GsrCamera *cam, const GsrOptions *opts, const float *grad_map, int32_t channels,
-                                   const float *grad_features, int64_t grad_stride)
-{
-    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
-    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
-    if (!grad_map) { set_error("null gradient map"); return GSR_ERR_BAD_ARG; }
-    if (!grad_features) { set_error("null feature gradient"); return GSR_ERR_BAD_ARG; }
-    if (channels < 1 || channels > GSR_MAX_FEATURE_CHANNELS) {
-        set_error("bad channels %d (1 .. %d)", channels, GSR_MAX_FEATURE_CHANNELS); return GSR_ERR_BAD_ARG;
-    }
-    if (grad_stride < channels) {
-        set_error("bad grad_stride %lld: rows of %d channels overlap", (long long)grad_stride, channels); return GSR_ERR_BAD_ARG;
-    }
-    if (opts->output_dtype == 1) { set_error("gradient maps are float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    if (opts->accum_dtype == 1) { set_error("feature gradients are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
+                           Slab{{features, channels, feature_stride, out_map, out_final_T, 0, 0}, scene, depth_near, depth_far});
 }
 
 int gsr_blend_channels_backward(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                                 size_t workspace_bytes, const float *grad_map, int32_t channels, float *grad_features, int64_t grad_stride,
                                 void *stream)
 {
-    const int rc = check_channels_backward(cam, opts, grad_map, channels, grad_features, grad_stride);
-    if (rc) return rc;
-    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_channels_backward(c, o, ws, plan, grad_map, channels, grad_features, grad_stride, s);
-        });
+    return run_on_lists(n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+                        ChannelsBackward{grad_map, channels, grad_features, grad_stride, 0});
 }
 
 int gsr_render_channels_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                                  size_t workspace_bytes, const float *grad_map, int32_t channels, float *grad_features,
                                  int64_t grad_stride, void *stream)
 {
-    const int rc = check_channels_backward(cam, opts, grad_map, channels, grad_features, grad_stride);
-    if (rc) return rc;
     return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_channels_backward(c, o, ws, plan, grad_map, channels, grad_features, grad_stride, s);
-        });
-}
-
-// What gsr_blend_splat_backward / gsr_render_splat_backward refuse before anything else (and before any HIP call)
-static int check_splat_backward(const GsrCamera *cam, const GsrOptions *opts, const float *features, int64_t feature_stride,
-                                int32_t channels, const float *grad_map, float min_T, int32_t want_abs, const float *grad_splat)
-{
-    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
-    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
-    if (!features) { set_error("null features"); return GSR_ERR_BAD_ARG; }
-    if (!grad_map) { set_error("null gradient map"); return GSR_ERR_BAD_ARG; }
-    if (!grad_splat) { set_error("null splat gradient"); return GSR_ERR_BAD_ARG; }
-    if (channels < 1 || channels > GSR_MAX_FEATURE_CHANNELS) {
-        set_error("bad channels %d (1 .. %d)", channels, GSR_MAX_FEATURE_CHANNELS); return GSR_ERR_BAD_ARG;
-    }
-    if (feature_stride < channels) {
-        set_error("bad feature_stride %lld: rows of %d channels overlap", (long long)feature_stride, channels); return GSR_ERR_BAD_ARG;
-    }
-    if (!(min_T >= 0.0f) || min_T > 3.4028234e38f) { set_error("bad min_T %g: a finite value >= 0", (double)min_T); return GSR_ERR_BAD_ARG; }
-    if (want_abs && channels > 16) {
-        set_error("want_abs with %d channels: the absolute sums are not linear in the channels, one walk of at most 16", channels);
-        return GSR_ERR_BAD_ARG;
-    }
-    if (opts->output_dtype == 1) { set_error("gradient maps are float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    if (opts->accum_dtype == 1) { set_error("splat gradients are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
+                           ChannelsBackward{grad_map, channels, grad_features, grad_stride, 0});
 }
 
 int gsr_blend_splat_backward(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                              size_t workspace_bytes, const float *features, int64_t feature_stride, int32_t channels,
                              const float *grad_map, const float *grad_T, float min_T, int32_t want_abs, float *grad_splat, void *stream)
 {
-    const int rc = check_splat_backward(cam, opts, features, feature_stride, channels, grad_map, min_T, want_abs, grad_splat);
-    if (rc) return rc;
-    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_splat_backward(c, o, ws, plan, features, feature_stride, channels, grad_map, grad_T, min_T, want_abs != 0,
-                                               grad_splat, s);
-        });
+    return run_on_lists(n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+                        SplatBackward{features, feature_stride, channels, grad_map, grad_T, min_T, want_abs, grad_splat});
 }
 
 int gsr_render_splat_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                               size_t workspace_bytes, const float *features, int64_t feature_stride, int32_t channels,
                               const float *grad_map, const float *grad_T, float min_T, int32_t want_abs, float *grad_splat, void *stream)
 {
-    const int rc = check_splat_backward(cam, opts, features, feature_stride, channels, grad_map, min_T, want_abs, grad_splat);
-    if (rc) return rc;
     return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_splat_backward(c, o, ws, plan, features, feature_stride, channels, grad_map, grad_T, min_T, want_abs != 0,
-                                               grad_splat, s);
-        });
-}
-
-static int check_gaussian_stats_options(const GsrOptions *opts)
-{
-    if (opts->output_dtype == 1) { set_error("gaussian statistics are float32 / uint32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    if (opts->accum_dtype == 1) { set_error("the weights are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
-}
-
-// What gsr_blend_gaussian_stats / gsr_render_gaussian_stats refuse before anything else (and before any HIP call)
-static int check_gaussian_stats(const GsrCamera *cam, const GsrOptions *opts, const float *weight_sum, const float *weight_max,
-                                const uint32_t *pixels)
-{
-    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
-    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
-    if (!weight_sum && !weight_max && !pixels) { set_error("null statistics outputs: all three"); return GSR_ERR_BAD_ARG; }
-    return check_gaussian_stats_options(opts);
+                           SplatBackward{features, feature_stride, channels, grad_map, grad_T, min_T, want_abs, grad_splat});
 }
 
 int gsr_blend_gaussian_stats(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                              size_t workspace_bytes, const uint8_t *pixel_mask, float *weight_sum, float *weight_max, uint32_t *pixels,
                              void *stream)
 {
-    const int rc = check_gaussian_stats(cam, opts, weight_sum, weight_max, pixels);
-    if (rc) return rc;
-    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_gstats(c, o, ws, plan, pixel_mask, weight_sum, weight_max, pixels, s);
-        });
+    return run_on_lists(n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
+                        GaussianStats{pixel_mask, weight_sum, weight_max, pixels, 0, nullptr, nullptr, false});
 }
 
 int gsr_render_gaussian_stats(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                               size_t workspace_bytes, const uint8_t *pixel_mask, float *weight_sum, float *weight_max, uint32_t *pixels,
                               void *stream)
 {
-    const int rc = check_gaussian_stats(cam, opts, weight_sum, weight_max, pixels);
-    if (rc) return rc;
     return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_gstats(c, o, ws, plan, pixel_mask, weight_sum, weight_max, pixels, s);
-        });
-}
-
-// What gsr_blend_pick / gsr_render_pick refuse before anything else (and before any HIP call)
-static int check_pick(const GsrCamera *cam, const GsrOptions *opts, float median_T, const int32_t *out_best_id, const float *out_best_w,
-                      const int32_t *out_median_id, const int32_t *out_count)
-{
-    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
-    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
-    if (!out_best_id && !out_best_w && !out_median_id && !out_count) { set_error("null pick outputs: all four"); return GSR_ERR_BAD_ARG; }
-    if (!(median_T > 0.0f && median_T <= 1.0f)) {  // (a NaN fails both compares)
-        set_error("bad median_T %g (0 < median_T <= 1)", (double)median_T); return GSR_ERR_BAD_ARG;
-    }
-    if (opts->output_dtype == 1) { set_error("pick maps are int32 / float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    if (opts->accum_dtype == 1) { set_error("pick weights are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
+                           GaussianStats{pixel_mask, weight_sum, weight_max, pixels, 0, nullptr, nullptr, false});
 }
 
 int gsr_blend_pick(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
                    float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id, int32_t *out_count, void *stream)
 {
-    const int rc = check_pick(cam, opts, median_T, out_best_id, out_best_w, out_median_id, out_count);
-    if (rc) return rc;
-    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_pick(c, o, ws, plan, median_T, out_best_id, out_best_w, out_median_id, out_count, s);
-        });
+    return run_on_lists(n, cam, opts, max_pairs, workspace, workspace_bytes, stream, Pick{median_T, out_best_id, out_best_w, out_median_id, out_count});
 }
 
 int gsr_render_pick(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, float median_T, int32_t *out_best_id, float *out_best_w, int32_t *out_median_id,
                     int32_t *out_count, void *stream)
 {
-    const int rc = check_pick(cam, opts, median_T, out_best_id, out_best_w, out_median_id, out_count);
-    if (rc) return rc;
     return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_pick(c, o, ws, plan, median_T, out_best_id, out_best_w, out_median_id, out_count, s);
-        });
-}
-
-// What gsr_blend_topk / gsr_render_topk refuse before anything else (and before any HIP call)
-static int check_topk(const GsrCamera *cam, const GsrOptions *opts, int32_t k, int32_t select, const int32_t *out_ids, const float *out_weights)
-{
-    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
-    if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
-    if (!out_ids && !out_weights) { set_error("null top-k outputs: both ids and weights"); return GSR_ERR_BAD_ARG; }
-    if (k < 1 || k > GSR_MAX_TOPK) { set_error("bad k %d (1 .. %d)", k, GSR_MAX_TOPK); return GSR_ERR_BAD_ARG; }
-    if (select != GSR_TOPK_HEAVIEST && select != GSR_TOPK_NEAREST) {
-        set_error("bad select %d (GSR_TOPK_HEAVIEST = 0, GSR_TOPK_NEAREST = 1)", select); return GSR_ERR_BAD_ARG;
-    }
-    if (opts->output_dtype == 1) { set_error("top-k lists are int32 / float32: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    if (opts->accum_dtype == 1) { set_error("top-k weights are accumulated in float32: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
+                           Pick{median_T, out_best_id, out_best_w, out_median_id, out_count});
 }
 
 int gsr_blend_topk(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace, size_t workspace_bytes,
                    int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T, void *stream)
 {
-    const int rc = check_topk(cam, opts, k, select, out_ids, out_weights);
-    if (rc) return rc;
-    return run_on_lists(nullptr, n, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_topk(c, o, ws, plan, k, select, out_ids, out_weights, out_final_T, s);
-        });
+    return run_on_lists(n, cam, opts, max_pairs, workspace, workspace_bytes, stream, TopK{k, select, out_ids, out_weights, out_final_T});
 }
 
 int gsr_render_topk(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                     size_t workspace_bytes, int32_t k, int32_t select, int32_t *out_ids, float *out_weights, float *out_final_T,
                     void *stream)
 {
-    const int rc = check_topk(cam, opts, k, select, out_ids, out_weights);
-    if (rc) return rc;
-    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_topk(c, o, ws, plan, k, select, out_ids, out_weights, out_final_T, s);
-        });
-}
-
-// How many views go through one launch sequence: as many slices as the workspace holds, at most MAX_VIEWS, GsrOptions.batch_views
-// (when set) and the views there are.  0: the workspace does not hold one view.
-static int views_per_launch(const GsrScene *scene, const GsrCamera *cam0, const GsrOptions *opts, int64_t max_pairs, size_t workspace_bytes, int32_t n_cams)
-{
-    Workspace ws;
-    const size_t per = carve_workspace(nullptr, scene->n, cam0->width, cam0->height, max_pairs, &ws);
-    size_t k = workspace_bytes / per;
-    k = std::min<size_t>(k, (size_t)MAX_VIEWS);
-    if (opts->batch_views > 0) k = std::min<size_t>(k, (size_t)opts->batch_views);
-    return (int)std::min<size_t>(k, (size_t)std::max<int32_t>(n_cams, 1));
-}
-
-static int check_batch(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs, const void *out_images,
-                       int64_t frame_stride)
-{
-    if (!scene || !cams || n_cams < 0 || !out_images || !opts) { set_error("bad argument"); return GSR_ERR_BAD_ARG; }
-    if (scene->n < 0 || scene->n > 0x7FFFFFFF || max_pairs < 0) { set_error("bad argument"); return GSR_ERR_BAD_ARG; }
-    for (int32_t i = 0; i < n_cams; ++i) {
-        if (cams[i].width <= 0 || cams[i].height <= 0) { set_error("bad frame size %dx%d", cams[i].width, cams[i].height); return GSR_ERR_BAD_ARG; }
-        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) { set_error("views of a batch must share one frame size"); return GSR_ERR_BAD_ARG; }
-    }
-    // what one view writes: the frame, or (output_layout = 2) the strip of its shard's tile rows
-    int64_t rows_px = cams[0].height;
-    if (n_cams > 0 && opts->output_layout == 2) {
-        const int tiles_y = (cams[0].height + GSR_TILE - 1) / GSR_TILE;
-        rows_px = (int64_t)row_shard_of(*opts).rows_before(tiles_y) * GSR_TILE;
-    }
-    if (n_cams > 0 && frame_stride < (int64_t)cams[0].width * rows_px * 3) { set_error("frame_stride smaller than a frame"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
-}
-
-int gsr_render_batch(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs,
-                     void *workspace, size_t workspace_bytes, void *out_images, int64_t frame_stride, void *stream)
-{
-    int rc = check_batch(scene, cams, n_cams, opts, max_pairs, out_images, frame_stride);
-    if (rc || n_cams == 0) return rc;
-    const int K = views_per_launch(scene, &cams[0], opts, max_pairs, workspace_bytes, n_cams);
-    const size_t fbytes = (size_t)frame_stride * (opts->output_dtype == 1 ? 2 : 4);
-    for (int32_t i = 0; i < n_cams; i += std::max(K, 1)) {
-        // K = 0: the workspace does not hold one view — render_views reports it.  A slice's first view clears its whole control
-        // block, its later views (i >= K) keep the batch-sticky overflow words
-        const int k = std::max(1, std::min<int32_t>(K, n_cams - i));
-        rc = render_views(scene, &cams[i], k, opts, max_pairs, workspace, workspace_bytes, static_cast<char *>(out_images) + (size_t)i * fbytes,
-                          fbytes, nullptr, stream, i > 0);
-        if (rc) return rc;
-    }
-    return GSR_OK;
-}
-
-int gsr_render_batch_slots(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs,
-                           void *const *workspaces, size_t workspace_bytes, void *const *streams, int32_t n_slots, void *out_images,
-                           int64_t frame_stride)
-{
-    if (!workspaces || !streams || n_slots < 1) { set_error("bad argument"); return GSR_ERR_BAD_ARG; }
-    int rc = check_batch(scene, cams, n_cams, opts, max_pairs, out_images, frame_stride);
-    if (rc) return rc;
-    for (int32_t k = 0; k < n_slots; ++k) {
-        if (!workspaces[k]) { set_error("null workspace in slot %d", (int)k); return GSR_ERR_BAD_ARG; }
-        for (int32_t j = 0; j < k; ++j)
-            if (workspaces[j] == workspaces[k]) { set_error("slots %d and %d share a workspace", (int)j, (int)k); return GSR_ERR_BAD_ARG; }
-    }
-    if (n_cams == 0) return GSR_OK;
-    const int K = views_per_launch(scene, &cams[0], opts, max_pairs, workspace_bytes, n_cams);
-    const size_t fbytes = (size_t)frame_stride * (opts->output_dtype == 1 ? 2 : 4);
-    int32_t g = 0;
-    for (int32_t i = 0; i < n_cams; i += std::max(K, 1), ++g) {
-        const int32_t slot = g % n_slots;
-        const int k = std::max(1, std::min<int32_t>(K, n_cams - i));
-        // a slot's first group clears its slices' control blocks, its later groups keep the batch-sticky overflow words
-        rc = render_views(scene, &cams[i], k, opts, max_pairs, workspaces[slot], workspace_bytes, static_cast<char *>(out_images) + (size_t)i * fbytes,
-                          fbytes, nullptr, streams[slot], g >= n_slots);
-        if (rc) return rc;
-    }
-    return GSR_OK;
+    return render_on_lists(scene, cam, opts, max_pairs, workspace, workspace_bytes, stream, TopK{k, select, out_ids, out_weights, out_final_T});
 }
 
 // ---- feature maps, their gradient and view statistics for several views per launch sequence ---------------------------------------
+static const char VIEWS_OF_TWO_SIZES[] = "views of a launch sequence must share one frame size";
+
 // What the gsr_*_views entries refuse about their views before anything else (and before any HIP call): view v works in slice v
 static int check_views(const GsrCamera *cams, int32_t n_views, const GsrOptions *opts)
 {
     if (!cams) { set_error("null cameras"); return GSR_ERR_BAD_ARG; }
     if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
     if (n_views < 1 || n_views > MAX_VIEWS) { set_error("bad view count %d (1 .. %d)", (int)n_views, MAX_VIEWS); return GSR_ERR_BAD_ARG; }
-    for (int32_t i = 1; i < n_views; ++i)
-        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) {
-            set_error("views of a launch sequence must share one frame size"); return GSR_ERR_BAD_ARG;
-        }
-    if (opts->output_layout == 1) { set_error("views of a launch sequence are [H,W] maps or shard strips: output_layout = 1 is not supported"); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
-}
-
-// Pixels of one view's plane: the frame, or (output_layout = 2) the strip of the shard's tile rows.  0 for sizes check_frame refuses
-static int64_t view_plane_pixels(const GsrCamera &cam, const GsrOptions &opts)
-{
-    if (cam.width <= 0 || cam.height <= 0) return 0;
-    int64_t rows_px = cam.height;
-    if (opts.output_layout == 2 && opts.tile_row_step >= 0 && opts.tile_row_begin >= 0) {
-        const int tiles_y = (cam.height + GSR_TILE - 1) / GSR_TILE;
-        rows_px = (int64_t)row_shard_of(opts).rows_before(tiles_y) * GSR_TILE;
-    }
-    return (int64_t)cam.width * rows_px;
-}
-
-static int check_view_stride(const char *name, int64_t stride, int64_t need, int32_t n_views, const char *what)
-{
-    if (n_views > 1 && stride < need) { set_error("bad %s %lld: smaller than %s (%lld)", name, (long long)stride, what, (long long)need); return GSR_ERR_BAD_ARG; }
-    return GSR_OK;
-}
-
-// The frame's checks for n_views views in slices 0 .. n_views - 1 of the workspace; *ws describes them (check_frame's, with the views)
-static int check_view_slices(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
-                             size_t workspace_bytes, Workspace *ws)
-{
-    const int rc = check_frame(n, &cams[0], opts, max_pairs, workspace, workspace_bytes, ws);
+    const int rc = check_one_frame_size(cams, n_views, VIEWS_OF_TWO_SIZES);
     if (rc) return rc;
-    if (workspace_bytes / ws->bytes < (size_t)n_views) {
-        set_error("workspace too small for %d views per launch: %zu bytes given, %zu needed", (int)n_views, workspace_bytes, ws->bytes * (size_t)n_views);
-        return GSR_ERR_WORKSPACE;
-    }
-    if (n_views > 1) {
-        ws->views = n_views;
-        ws->view_stride = ws->bytes;
-    }
+    if (opts->output_layout == 1) { set_error("views of a launch sequence are [H,W] maps or shard strips: output_layout = 1 is not supported"); return GSR_ERR_BAD_ARG; }
     return GSR_OK;
 }
 
@@ -915,58 +929,51 @@ int gsr_lists_views(const GsrScene *scene, const GsrCamera *cams, int32_t n_view
     return lists_views(scene, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream, false);
 }
 
-// gsr_blend_X_views behind its own argument checks: the frame's checks for the slices, the plan, and launch(cam, opts, ws, plan, s)
 extern "C++" {
-template <class Launch>
-static int run_on_view_lists(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
-                             size_t workspace_bytes, void *stream, Launch launch)
+// What a gsr_blend_X_views entry refuses before it looks at the workspace: the views, the consumer's own, its strides
+template <class Consumer>
+static int check_on_views(const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, const Consumer &c)
+{
+    int rc = check_views(cams, n_views, opts);
+    if (!rc) rc = c.check(&cams[0], opts);
+    return rc ? rc : c.check_view_strides(view_plane_pixels(cams[0], *opts), n_views);
+}
+
+// behind them: the frame's checks for the slices, the plan, and the consumer's launch on the lists of n gaussians in every slice
+template <class Consumer>
+static int on_view_lists(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                         size_t workspace_bytes, void *stream, const Consumer &c)
 {
     Workspace ws;
     const int rc = check_view_slices(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, &ws);
     if (rc) return rc;
-    return launch(cams[0], *opts, ws, plan_frame(ws, *opts), static_cast<hipStream_t>(stream));
+    const FramePlan plan = plan_frame(ws, *opts);
+    return c.launch(Lists{cams[0], *opts, ws, plan, static_cast<hipStream_t>(stream)});
+}
+
+template <class Consumer>
+static int run_on_view_lists(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
+                             size_t workspace_bytes, void *stream, const Consumer &c)
+{
+    const int rc = check_on_views(cams, n_views, opts, c);
+    return rc ? rc : on_view_lists(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream, c);
 }
 }  // extern "C++"
-
-static int check_channels_views(const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, const float *features, int32_t channels,
-                                int64_t feature_stride, const float *out_maps, int64_t map_stride, const float *out_final_T, int64_t T_stride)
-{
-    int rc = check_views(cams, n_views, opts);
-    if (rc) return rc;
-    rc = check_channels(&cams[0], opts, features, channels, feature_stride, out_maps);
-    if (rc) return rc;
-    const int64_t plane = view_plane_pixels(cams[0], *opts);
-    rc = check_view_stride("map_stride", map_stride, plane * channels, n_views, "a view's map");
-    if (rc) return rc;
-    return out_final_T ? check_view_stride("T_stride", T_stride, plane, n_views, "a view's final-T plane") : GSR_OK;
-}
 
 int gsr_blend_channels_views(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                              size_t workspace_bytes, const float *features, int32_t channels, int64_t feature_stride, float *out_maps,
                              int64_t map_stride, float *out_final_T, int64_t T_stride, void *stream)
 {
-    const int rc = check_channels_views(cams, n_views, opts, features, channels, feature_stride, out_maps, map_stride, out_final_T, T_stride);
-    if (rc) return rc;
     return run_on_view_lists(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_channels(c, o, ws, plan, features, channels, feature_stride, out_maps, out_final_T, s, map_stride, T_stride);
-        });
+                             Channels{features, channels, feature_stride, out_maps, out_final_T, map_stride, T_stride});
 }
 
 int gsr_blend_channels_backward_views(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs,
                                       void *workspace, size_t workspace_bytes, const float *grad_maps, int64_t map_stride, int32_t channels,
                                       float *grad_features, int64_t grad_stride, void *stream)
 {
-    int rc = check_views(cams, n_views, opts);
-    if (rc) return rc;
-    rc = check_channels_backward(&cams[0], opts, grad_maps, channels, grad_features, grad_stride);
-    if (rc) return rc;
-    rc = check_view_stride("map_stride", map_stride, view_plane_pixels(cams[0], *opts) * channels, n_views, "a view's gradient map");
-    if (rc) return rc;
     return run_on_view_lists(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-            return launch_blend_channels_backward(c, o, ws, plan, grad_maps, channels, grad_features, grad_stride, s, map_stride);
-        });
+                             ChannelsBackward{grad_maps, channels, grad_features, grad_stride, map_stride});
 }
 
 int gsr_blend_gaussian_stats_views(int64_t n, const GsrCamera *cams, int32_t n_views, const GsrOptions *opts, int64_t max_pairs,
@@ -974,23 +981,8 @@ int gsr_blend_gaussian_stats_views(int64_t n, const GsrCamera *cams, int32_t n_v
                                    float *weight_sum, float *weight_max, uint32_t *pixels, uint32_t *view_hits, uint32_t *view_bits,
                                    void *stream)
 {
-    int rc = check_views(cams, n_views, opts);
-    if (rc) return rc;
-    if (!weight_sum && !weight_max && !pixels && !view_hits) { set_error("null statistics outputs: all four"); return GSR_ERR_BAD_ARG; }
-    if (view_hits && !view_bits) { set_error("view_hits needs the view_bits scratch"); return GSR_ERR_BAD_ARG; }
-    if (!view_hits && view_bits) { set_error("a view_bits scratch without view_hits"); return GSR_ERR_BAD_ARG; }
-    rc = check_gaussian_stats_options(opts);
-    if (rc) return rc;
-    if (pixel_masks) {
-        rc = check_view_stride("mask_stride", mask_stride, view_plane_pixels(cams[0], *opts), n_views, "a view's mask plane");
-        if (rc) return rc;
-    }
     return run_on_view_lists(n, cams, n_views, opts, max_pairs, workspace, workspace_bytes, stream,
-        [&](const GsrCamera &c, const GsrOptions &o, const Workspace &ws, const FramePlan &plan, hipStream_t s) -> int {
-            // the scratch is this launch sequence's: bit v = view v has counted the gaussian
-            if (view_hits && ws.n > 0) GSR_HIP(hipMemsetAsync(view_bits, 0, sizeof(uint32_t) * (size_t)ws.n, s));
-            return launch_blend_gstats(c, o, ws, plan, pixel_masks, weight_sum, weight_max, pixels, s, mask_stride, view_hits, view_bits);
-        });
+                             GaussianStats{pixel_masks, weight_sum, weight_max, pixels, mask_stride, view_hits, view_bits, true});
 }
 
 int gsr_render_channels_batch(const GsrScene *scene, const GsrCamera *cams, int32_t n_cams, const GsrOptions *opts, int64_t max_pairs,
@@ -1003,32 +995,20 @@ int gsr_render_channels_batch(const GsrScene *scene, const GsrCamera *cams, int3
     if (!opts) { set_error("null options"); return GSR_ERR_BAD_ARG; }
     if (n_cams < 0) { set_error("bad camera count %d", (int)n_cams); return GSR_ERR_BAD_ARG; }
     if (n_cams == 0) return GSR_OK;
-    for (int32_t i = 1; i < n_cams; ++i)  // every camera against the first, whatever the group it falls into
-        if (cams[i].width != cams[0].width || cams[i].height != cams[0].height) {
-            set_error("views of a launch sequence must share one frame size"); return GSR_ERR_BAD_ARG;
-        }
+    rc = check_one_frame_size(cams, n_cams, VIEWS_OF_TWO_SIZES);  // every camera against the first, whatever the group it falls into
+    if (rc) return rc;
     // (a group's own checks, on a group as large as any: the strides are asked for whenever there is a second camera)
-    rc = check_channels_views(cams, std::min<int32_t>(n_cams, 2), opts, features, channels, feature_stride, out_maps, map_stride, out_final_T, T_stride);
+    const Channels c{features, channels, feature_stride, out_maps, out_final_T, map_stride, T_stride};
+    rc = check_on_views(cams, std::min<int32_t>(n_cams, 2), opts, c);
     if (rc) return rc;
     rc = check_sizes(scene->n, cams[0].width, cams[0].height, max_pairs);
     if (rc) return rc;
-    const int K = views_per_launch(scene, &cams[0], opts, max_pairs, workspace_bytes, n_cams);
-    for (int32_t i = 0; i < n_cams; i += std::max(K, 1)) {
-        // K = 0: the workspace does not hold one view — the group's checks report it.  A slice's first view clears its whole control
-        // block, its later views (i >= K) keep the batch-sticky overflow words, as in gsr_render_batch
-        const int k = std::max(1, std::min<int32_t>(K, n_cams - i));
-        rc = lists_views(scene, &cams[i], k, opts, max_pairs, workspace, workspace_bytes, stream, i > 0);
-        if (rc) return rc;
-        float *maps = out_maps + (size_t)i * (size_t)map_stride, *Ts = out_final_T ? out_final_T + (size_t)i * (size_t)T_stride : nullptr;
-        GsrOptions o = *opts;
-        o.colour_stage = 0;
-        rc = run_on_view_lists(scene->n, &cams[i], k, &o, max_pairs, workspace, workspace_bytes, stream,
-            [&](const GsrCamera &c, const GsrOptions &oo, const Workspace &ws, const FramePlan &plan, hipStream_t s) {
-                return launch_blend_channels(c, oo, ws, plan, features, channels, feature_stride, maps, Ts, s, map_stride, T_stride);
-            });
-        if (rc) return rc;
-    }
-    return GSR_OK;
+    GsrOptions o = *opts;
+    o.colour_stage = 0;
+    return for_view_groups(n_cams, views_per_launch(scene, &cams[0], opts, max_pairs, workspace_bytes, n_cams), [&](int32_t first, int count, int32_t g) {
+        const int lists_rc = lists_views(scene, &cams[first], count, opts, max_pairs, workspace, workspace_bytes, stream, g > 0);
+        return lists_rc ? lists_rc : on_view_lists(scene->n, &cams[first], count, &o, max_pairs, workspace, workspace_bytes, stream, c.from_view(first));
+    });
 }
 
 int gsr_read_stats(void *workspace, size_t workspace_bytes, GsrStats *out, void *stream)

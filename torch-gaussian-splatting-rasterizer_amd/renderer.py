@@ -555,7 +555,7 @@ class Rasterizer:
 
     def _chained(self, opts: GsrOptions) -> GsrOptions:
         """Slice 0 holds unchecked frames: a single view adds to their record (keep_flags; a copy, the caller's struct is never
-        written).  enqueue_batch has a rule of its own (to_reset), FramesInFlight.render_batch clears the flag on purpose."""
+        written).  Batches have a rule of their own (_enqueue_group), FramesInFlight.render_batch clears the flag on purpose."""
         if not self.unchecked.slices or opts.keep_flags:
             return opts
         o = GsrOptions.from_buffer_copy(opts)
@@ -603,6 +603,23 @@ class Rasterizer:
             return self._enqueue_lists(cam, o)
 
         return _render_checked([self], [None], opts, attempt, 8, what)
+
+    def _accumulate_view(self, cam: GsrCamera, opts: GsrOptions, what: str, own, render_entry, blend_entry, *args) -> None:
+        """A single view's per-gaussian sums into the buffers whose addresses stand in `args`, the arguments both entries take
+        between the workspace and the stream.  own = the buffers when they are this call's: zeroed on every attempt, then ONE
+        gsr_render_X under _render_checked — an incomplete walk is thrown away with them.  own = None, the caller's buffers:
+        _checked_lists first, then one gsr_blend_X that adds."""
+        if own is None:
+            o = self._checked_lists(cam, opts, what)
+            self._blend_lists(cam, o, blend_entry, *args)
+            return
+
+        def attempt(o):  # a re-run after an overflow starts from zero again
+            for b in own:
+                b.zero_()
+            self._enqueue_view(cam, o, render_entry, None, *args)
+
+        _render_checked([self], [None], opts, attempt, 8, what)
 
     # -- one frame ------------------------------------------------------------------------------
     def enqueue(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None,
@@ -778,6 +795,25 @@ class Rasterizer:
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "feature map")
 
     # -- the gradient of a feature map with respect to the features -------------------------------------------------------------
+    def _gradient_request(self, cam: GsrCamera, opts: GsrOptions, grad_map: torch.Tensor, out: Optional[torch.Tensor],
+                          name: str = "grad_map", lead=()):
+        """feature_gradient's argument checks (feature_gradient_batch's: name="grad_maps", lead=(B,), any of the cameras), before any
+        workspace or buffer is made: (the map, contiguous float32; its channels)."""
+        dev, n, most = self.scene.device, self.scene.n, _lib.GSR_MAX_FEATURE_CHANNELS
+        _require_cuda(grad_map, name)
+        want = tuple(lead) + tuple(self._out_shape(cam, opts)[0][:2])
+        d = len(want)
+        if grad_map.dim() != d + 1 or tuple(grad_map.shape[:d]) != want or not 1 <= grad_map.shape[d] <= most:
+            raise ValueError(f"{name} must have shape {want} + (1 <= C <= {most},), got {tuple(grad_map.shape)}")
+        if grad_map.device != dev:
+            raise ValueError(f"{name} must live on the scene's device")
+        n_ch = int(grad_map.shape[d])
+        if out is not None:
+            if tuple(out.shape) != (n, n_ch) or out.dtype != torch.float32 or out.device != dev or (
+                    n and (out.stride(1) != 1 or out.stride(0) < n_ch)):
+                raise ValueError(f"out must be a float32 tensor of shape [{n}, {n_ch}] on the scene's device with unit element stride")
+        return grad_map.detach().to(torch.float32).contiguous(), n_ch
+
     def feature_gradient(self, cam: GsrCamera, grad_map: torch.Tensor, opts: Optional[GsrOptions] = None,
                          out: Optional[torch.Tensor] = None, scene_order: bool = False) -> torch.Tensor:
         """The transpose of render_features under the same camera and options: [n, C] with row i = sum_p w_i(p) grad_map[p]
@@ -789,34 +825,15 @@ class Rasterizer:
         between two calls."""
         opts = opts or make_options()
         dev, n = self.scene.device, self.scene.n
-        _require_cuda(grad_map, "grad_map")
-        shape, _ = self._out_shape(cam, opts)
-        if grad_map.dim() != 3 or tuple(grad_map.shape[:2]) != shape[:2] or not 1 <= grad_map.shape[2] <= _lib.GSR_MAX_FEATURE_CHANNELS:
-            raise ValueError(f"grad_map must have shape {shape[:2]} + (1 <= C <= {_lib.GSR_MAX_FEATURE_CHANNELS},), got {tuple(grad_map.shape)}")
-        if grad_map.device != dev:
-            raise ValueError("grad_map must live on the scene's device")
-        n_ch = int(grad_map.shape[2])
-        gm = grad_map.detach().to(torch.float32).contiguous()
-        if out is not None:
-            if tuple(out.shape) != (n, n_ch) or out.dtype != torch.float32 or out.device != dev or (
-                    n and (out.stride(1) != 1 or out.stride(0) < n_ch)):
-                raise ValueError(f"out must be a float32 tensor of shape [{n}, {n_ch}] on the scene's device with unit element stride")
+        gm, n_ch = self._gradient_request(cam, opts, grad_map, out)
         # nothing to draw, or a shard that owns no tile row: the gradient is zero.  Here and in view_stats no workspace is made for
         # that and the shard leaves no mark in `unchecked`, unlike the map calls (_enqueue_view).
         if n == 0 or gm.numel() == 0:
             return out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
-        if out is None:
-            buf = torch.empty((n, n_ch), dtype=torch.float32, device=dev)
-
-            def attempt(o):  # a re-run after an overflow starts from zero again
-                buf.zero_()
-                self._enqueue_view(cam, o, lib.gsr_render_channels_backward, buf, gm.data_ptr(), n_ch, buf.data_ptr(), n_ch)
-
-            _render_checked([self], [None], opts, attempt, 8, "feature gradient")
-            return buf if scene_order else file_order_gradient(buf, self.scene.order_t)
-        o = self._checked_lists(cam, opts, "feature gradient")
-        self._blend_lists(cam, o, lib.gsr_blend_channels_backward, gm.data_ptr(), n_ch, out.data_ptr(), int(out.stride(0)))
-        return out
+        buf = out if out is not None else torch.empty((n, n_ch), dtype=torch.float32, device=dev)
+        self._accumulate_view(cam, opts, "feature gradient", None if out is not None else [buf], lib.gsr_render_channels_backward,
+                              lib.gsr_blend_channels_backward, gm.data_ptr(), n_ch, buf.data_ptr(), int(buf.stride(0)))
+        return buf if out is not None or scene_order else file_order_gradient(buf, self.scene.order_t)
 
     # -- the gradient of a feature map with respect to opacity and the 2-D splat ----------------------------------------------------
     def splat_gradient(self, cam: GsrCamera, features: torch.Tensor, grad_map: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
@@ -867,18 +884,10 @@ class Rasterizer:
         rows = self._feature_rows(features.detach(), scene_order)
         tail = (rows.data_ptr(), int(rows.stride(0)), n_ch, gm.data_ptr(), gt.data_ptr() if gt is not None else None, float(min_T),
                 int(bool(abs_mean)))
-        if out is None:
-            buf = torch.empty((n, 8), dtype=torch.float32, device=dev)
-
-            def attempt(o):  # a re-run after an overflow starts from zero again
-                buf.zero_()
-                self._enqueue_view(cam, o, lib.gsr_render_splat_backward, buf, *tail, buf.data_ptr())
-
-            _render_checked([self], [None], opts, attempt, 8, "splat gradient")
-            return result(buf, scene_order)
-        o = self._checked_lists(cam, opts, "splat gradient")
-        self._blend_lists(cam, o, lib.gsr_blend_splat_backward, *tail, out.data_ptr())
-        return result(out, True)
+        buf = out if out is not None else torch.empty((n, 8), dtype=torch.float32, device=dev)
+        self._accumulate_view(cam, opts, "splat gradient", None if out is not None else [buf], lib.gsr_render_splat_backward,
+                              lib.gsr_blend_splat_backward, *tail, buf.data_ptr())
+        return result(buf, out is not None or scene_order)
 
     def blend_weights(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[n]: every gaussian's blend weight summed over the drawn pixels of this view, sum_p w_i(p) — feature_gradient of a
@@ -955,17 +964,8 @@ class Rasterizer:
         if n == 0 or 0 in self._out_shape(cam, opts)[1]:  # nothing to draw, or a shard that owns no tile row
             return result()
         ptrs = [mptr] + [b.data_ptr() if b is not None else None for b in bufs]
-        if not given:
-            def attempt(o):  # a re-run after an overflow starts from zero again
-                for b in bufs:
-                    if b is not None:
-                        b.zero_()
-                self._enqueue_view(cam, o, lib.gsr_render_gaussian_stats, None, *ptrs)
-
-            _render_checked([self], [None], opts, attempt, 8, "view statistics")
-            return result()
-        o = self._checked_lists(cam, opts, "view statistics")
-        self._blend_lists(cam, o, lib.gsr_blend_gaussian_stats, *ptrs)
+        self._accumulate_view(cam, opts, "view statistics", None if given else [b for b in bufs if b is not None],
+                              lib.gsr_render_gaussian_stats, lib.gsr_blend_gaussian_stats, *ptrs)
         return result()
 
     def visible_ids(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1156,16 +1156,20 @@ class Rasterizer:
         k = self._views_per_launch(opts, len(cams))
         return [(i, (GsrCamera * len(cams[i:i + k]))(*cams[i:i + k])) for i in range(0, len(cams), k)]
 
-    def _enqueue_lists_views(self, arr, opts: GsrOptions) -> GsrOptions:
-        """gsr_lists_views for one group (view j in slice j) on the current stream, unchecked like enqueue_batch() and with its rule
-        for the slices' records; returns the options the call ran with."""
+    def _enqueue_group(self, arr, opts: GsrOptions, entry, *args) -> GsrOptions:
+        """_enqueue_view for the cameras of `arr`: one entry that takes them through the slices, `views` per launch sequence and view j
+        of a sequence in slice j (gsr_render_batch, gsr_render_channels_batch; gsr_lists_views for one group — all share the prefix
+        scene, cameras, how many, opts, max_pairs, workspace; `args` lie between it and the stream), on the current stream and
+        unchecked.  A slice's first view starts a new record (libgsr chains the later ones) unless slice 0 holds unchecked frames:
+        then all keep theirs, and the slices that held none start from an empty one.  Returns the options the entry ran with."""
         ws = self._workspace(arr[0].width, arr[0].height)
-        self._reset_slices(self.unchecked.to_reset(len(arr)))
+        k = self._views_per_launch(opts, len(arr))
+        self._reset_slices(self.unchecked.to_reset(k))
         o = GsrOptions.from_buffer_copy(opts)
         o.keep_flags = 1 if (self.unchecked.slices or opts.keep_flags) else 0
         sc = self.scene.c_struct()
-        check(lib.gsr_lists_views(C.byref(sc), arr, len(arr), C.byref(o), self.max_pairs, ws.data_ptr(), ws.numel(), _stream_ptr(self.scene.device)))
-        self.unchecked.wrote(len(arr))
+        check(entry(C.byref(sc), arr, len(arr), C.byref(o), self.max_pairs, ws.data_ptr(), ws.numel(), *args, _stream_ptr(self.scene.device)))
+        self.unchecked.wrote(k)
         return o
 
     def _checked_lists_views(self, arr, opts: GsrOptions, what: str) -> GsrOptions:
@@ -1174,7 +1178,7 @@ class Rasterizer:
         def attempt(o):
             o = GsrOptions.from_buffer_copy(o)
             o.colour_stage = 0
-            return self._enqueue_lists_views(arr, o)
+            return self._enqueue_group(arr, o, lib.gsr_lists_views)
 
         return _render_checked([self], [None], opts, attempt, 8, what)
 
@@ -1210,16 +1214,8 @@ class Rasterizer:
                 out.zero_()
                 self.unchecked.wrote(0)
                 return (out, T) if return_T else out
-            ws = self._workspace(cams[0].width, cams[0].height)
-            k = self._views_per_launch(o, B)
-            self._reset_slices(self.unchecked.to_reset(k))
-            o = GsrOptions.from_buffer_copy(o)
-            o.keep_flags = 1 if (self.unchecked.slices or o.keep_flags) else 0
-            sc = self.scene.c_struct()
-            check(lib.gsr_render_channels_batch(C.byref(sc), arr, B, C.byref(o), self.max_pairs, ws.data_ptr(), ws.numel(), rows.data_ptr(),
-                                                n_ch, int(rows.stride(0)), out.data_ptr(), out[0].numel(), T.data_ptr() if return_T else None,
-                                                T[0].numel() if return_T else 0, _stream_ptr(self.scene.device)))
-            self.unchecked.wrote(k)
+            self._enqueue_group(arr, o, lib.gsr_render_channels_batch, rows.data_ptr(), n_ch, int(rows.stride(0)), out.data_ptr(),
+                                out[0].numel(), T.data_ptr() if return_T else None, T[0].numel() if return_T else 0)
             return (out, T) if return_T else out
 
         return _render_checked([self], [None], opts, attempt, 4, "feature map batch")
@@ -1234,19 +1230,8 @@ class Rasterizer:
         Float atomic sums may differ in the last bits between two calls."""
         opts = opts or make_options()
         cams = self._view_list(cams, opts)
-        dev, n, B = self.scene.device, self.scene.n, len(cams)
-        _require_cuda(grad_maps, "grad_maps")
-        shape, _ = self._out_shape(cams[0], opts)
-        if grad_maps.dim() != 4 or tuple(grad_maps.shape[:3]) != (B,) + tuple(shape[:2]) or not 1 <= grad_maps.shape[3] <= _lib.GSR_MAX_FEATURE_CHANNELS:
-            raise ValueError(f"grad_maps must have shape {(B,) + tuple(shape[:2])} + (1 <= C <= {_lib.GSR_MAX_FEATURE_CHANNELS},), got {tuple(grad_maps.shape)}")
-        if grad_maps.device != dev:
-            raise ValueError("grad_maps must live on the scene's device")
-        n_ch = int(grad_maps.shape[3])
-        gm = grad_maps.detach().to(torch.float32).contiguous()
-        if out is not None:
-            if tuple(out.shape) != (n, n_ch) or out.dtype != torch.float32 or out.device != dev or (
-                    n and (out.stride(1) != 1 or out.stride(0) < n_ch)):
-                raise ValueError(f"out must be a float32 tensor of shape [{n}, {n_ch}] on the scene's device with unit element stride")
+        dev, n = self.scene.device, self.scene.n
+        gm, n_ch = self._gradient_request(cams[0], opts, grad_maps, out, "grad_maps", (len(cams),))
         if n == 0 or gm.numel() == 0:  # nothing to draw, or a shard that owns no tile row: no workspace (feature_gradient's rule)
             return out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
         buf = out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
@@ -1353,17 +1338,7 @@ class Rasterizer:
         if out.numel() == 0:  # a shard that owns no tile row
             self.unchecked.wrote(0)
             return out
-        arr = (GsrCamera * len(cams))(*cams)
-        ws = self._workspace(cams[0].width, cams[0].height)
-        k = self._views_per_launch(opts, len(cams))
-        # a slice's first view starts a new record (libgsr chains the later ones) unless slice 0 holds unchecked frames: then all keep theirs
-        self._reset_slices(self.unchecked.to_reset(k))
-        o = GsrOptions.from_buffer_copy(opts)
-        o.keep_flags = 1 if (self.unchecked.slices or opts.keep_flags) else 0
-        sc = self.scene.c_struct()
-        check(lib.gsr_render_batch(C.byref(sc), arr, len(cams), C.byref(o), self.max_pairs, ws.data_ptr(), ws.numel(),
-                                   out.data_ptr(), stride, _stream_ptr(self.scene.device)))
-        self.unchecked.wrote(k)
+        self._enqueue_group((GsrCamera * len(cams))(*cams), opts, lib.gsr_render_batch, out.data_ptr(), stride)
         return out
 
     def render_batch(self, cams, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
