@@ -9,120 +9,77 @@ rule 24).  Stages 1-2 run once, then per round, each between two events on the s
   C   gsr_blend_slab, 3 channels, far = 1.05 x render_median_depth where a surface was found, +inf elsewhere: the stop rule
   D   gsr_blend_slab, 3 channels, near = that plane (-inf where no surface was found): the skip
 Median, min, max and spread over the rounds, the ratios to A, each call's wave_entries / fetched_entries, and whether B's maps are
-A's bit for bit.  Appends what it prints to profiles/slab_ab.txt (--out), under --label.
+A's bit for bit.  Appends what it prints to profiles/slab_ab.txt (--out), under --label.  The measurement runs in a child process
+under a time limit (--timeout seconds; tools/ab_harness.py).
 The kernels without the chunk-level bypass of the per-lane depth compares are the analysis build of the library:
   make -C torch-gaussian-splatting-rasterizer_amd/csrc ../../tools/libgsr_slab_nobypass.so
   GSR_LIB_PATH=tools/libgsr_slab_nobypass.so tools/slab_ab.py --label "no bypass"
-usage: tools/slab_ab.py [--workload bicycle] [--rounds 30] [--early-out-T 0] [--label bypass]"""
-import argparse
+usage: tools/slab_ab.py [--workload bicycle] [--rounds 30] [--early-out-T 0] [--label bypass] [--timeout 420]"""
 import ctypes as C
 import os
-import sys
 
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
-import numpy as np
-import torch
+import ab_harness as ab
 
-import bench
-import gsr_amd  # noqa: F401
-from gsr_amd import _lib, renderer, utils
-from gsr_amd._lib import check, lib
-
-#        entry, channels, near, far
-RUNS = {"A": ("channels", 3, None, None), "A8": ("channels", 8, None, None), "A16": ("channels", 16, None, None),
-        "B4": ("slab", 3, None, None), "B8": ("slab", 8, None, None), "B16": ("slab", 16, None, None),
-        "C": ("slab", 3, None, "surface"), "D": ("slab", 3, "surface", None)}
+#        entry, channels, near, far, what
+RUNS = {"A": ("channels", 3, None, None, "gsr_blend_channels, 3 channels"), "A8": ("channels", 8, None, None, "gsr_blend_channels, 8 channels"),
+        "A16": ("channels", 16, None, None, "gsr_blend_channels, 16 channels"),
+        "B4": ("slab", 3, None, None, "gsr_blend_slab, 3 channels, open limits"), "B8": ("slab", 8, None, None, "gsr_blend_slab, 8 channels, open limits"),
+        "B16": ("slab", 16, None, None, "gsr_blend_slab, 16 channels, open limits"),
+        "C": ("slab", 3, None, "surface", "gsr_blend_slab, 3 channels, far = 1.05 x median depth"),
+        "D": ("slab", 3, "surface", None, "gsr_blend_slab, 3 channels, near = 1.05 x median depth")}
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="bicycle")
-    ap.add_argument("--gaussians", type=int, default=0)
-    ap.add_argument("--rounds", type=int, default=30)
-    ap.add_argument("--early-out-T", type=float, default=0.0)
-    ap.add_argument("--camera", type=int, default=0)
-    ap.add_argument("--camera-set", default="single")
-    ap.add_argument("--label", default="bypass")
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "slab_ab.txt"))
-    a = ap.parse_args()
-    dev = torch.device("cuda", 0)
-    cols, cam_list, n, W, H, _ = bench.build_workload(a.workload, a, a.gaussians)
-    scene = renderer.GaussianScene.from_packed(utils.pack_gaussians(cols), device=dev)
-    del cols
-    cam = renderer.make_camera(*cam_list[0])
-    R = renderer.Rasterizer(scene)
-    R.fit_pairs(cam)
-    zm = R.render_median_depth(cam)  # (its own stages 1-3, before the lists below are built)
+def arguments(argv=None):
+    return ab.arguments("slab_ab", rounds=30, label="bypass", argv=argv)
+
+
+def worker(a):
+    import torch
+
+    f = ab.bench_frame(a)
+    from gsr_amd import _lib, renderer
+    from gsr_amd._lib import check, lib
+
+    n, W, H, dev, sp = f.n, f.W, f.H, f.dev, f.sp
+    zm = f.R.render_median_depth(f.cam)  # (its own stages 1-3, before the lists below are built)
     found = zm > 0
     inf = float("inf")
     planes = {("surface", "far"): torch.where(found, 1.05 * zm, torch.full_like(zm, inf)).contiguous(),
               ("surface", "near"): torch.where(found, 1.05 * zm, torch.full_like(zm, -inf)).contiguous()}
-    ws = R._workspace(W, H)
-    sc = scene.c_struct()
-    stream = torch.cuda.current_stream(dev)
-    sp = int(stream.cuda_stream)
     feats = torch.rand((n, 16), generator=torch.Generator().manual_seed(1)).to(dev)
-    feats[:, :3] = R._depth_features(cam)
+    feats[:, :3] = f.R._depth_features(f.cam)
     o = renderer.make_options(early_out_T=a.early_out_T, colour_stage=0)
-    maps = {r: torch.empty((H, W, ch), dtype=torch.float32, device=dev) for r, (_, ch, _, _) in RUNS.items()}
+    maps = {r: torch.empty((H, W, run[1]), dtype=torch.float32, device=dev) for r, run in RUNS.items()}
     final_T = {r: torch.empty((H, W), dtype=torch.float32, device=dev) for r in RUNS}
-    wp, wn, mp = ws.data_ptr(), ws.numel(), R.max_pairs
-    check(lib.gsr_preprocess(C.byref(sc), C.byref(cam), C.byref(o), wp, wn, None, sp))
-    check(lib.gsr_bin_sort(n, C.byref(cam), C.byref(o), mp, wp, wn, sp))
+    f.make_lists(o)
 
     def run(r):
-        entry, ch, near, far = RUNS[r]
+        entry, ch, near, far, _ = RUNS[r]
         if entry == "channels":
-            check(lib.gsr_blend_channels(n, C.byref(cam), C.byref(o), mp, wp, wn, feats.data_ptr(), ch, 16, maps[r].data_ptr(),
-                                         final_T[r].data_ptr(), sp))
+            check(lib.gsr_blend_channels(*f.lists(o), feats.data_ptr(), ch, 16, maps[r].data_ptr(), final_T[r].data_ptr(), sp))
         else:
-            check(lib.gsr_blend_slab(C.byref(sc), n, C.byref(cam), C.byref(o), mp, wp, wn, feats.data_ptr(), ch, 16,
+            check(lib.gsr_blend_slab(C.byref(f.sc), *f.lists(o), feats.data_ptr(), ch, 16,
                                      planes[near, "near"].data_ptr() if near else None, planes[far, "far"].data_ptr() if far else None,
                                      maps[r].data_ptr(), final_T[r].data_ptr(), sp))
 
-    times, stats = {r: [] for r in RUNS}, {}
-    for rnd in range(a.rounds + 2):  # the first two rounds warm up (code objects, the launch-order hint)
-        for r in RUNS:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            run(r)
-            e1.record(stream)
-            torch.cuda.synchronize(dev)
-            if rnd >= 2:
-                times[r].append(e0.elapsed_time(e1))
-            if rnd == 1:
-                stats[r] = R.stats()
-    lines = [f"[{a.label}] {os.path.basename(_lib.LIB_PATH)}  {a.workload}: {n} gaussians, {W}x{H}, {a.rounds} interleaved rounds after 2 warm-up "
+    times, stats = ab.interleaved([(r, (lambda r=r: run(r))) for r in RUNS], a.rounds, "events", stats=f.R.stats)
+    lines = [f"{os.path.basename(_lib.LIB_PATH)}  {a.workload}: {n} gaussians, {W}x{H}, {a.rounds} interleaved rounds after 2 warm-up "
              f"rounds (blend stage alone, tile-order kernel included), early_out_T {a.early_out_T}; a median surface on "
              f"{float(found.float().mean()) * 100:.1f} % of the pixels"]
-    what = {"A": "gsr_blend_channels, 3 channels", "A8": "gsr_blend_channels, 8 channels", "A16": "gsr_blend_channels, 16 channels",
-            "B4": "gsr_blend_slab, 3 channels, open limits", "B8": "gsr_blend_slab, 8 channels, open limits",
-            "B16": "gsr_blend_slab, 16 channels, open limits", "C": "gsr_blend_slab, 3 channels, far = 1.05 x median depth",
-            "D": "gsr_blend_slab, 3 channels, near = 1.05 x median depth"}
     med = {}
     for r in RUNS:
-        t = np.array(times[r])
-        med[r] = float(np.median(t))
-        lines.append(f"  {r:3}: median {np.median(t):.4f} ms  min {t.min():.4f} ms  max {t.max():.4f} ms  spread (max - min) / median "
-                     f"{(t.max() - t.min()) / np.median(t) * 100:.1f} %   wave_entries {stats[r]['wave_entries']} fetched_entries "
-                     f"{stats[r]['fetched_entries']}   [{what[r]}]")
-    lines.append("  ratios at the median: " + "   ".join(f"{r} / A {med[r] / med['A']:.3f}" for r in RUNS if r != "A")
-                 + f"   B8 / A8 {med['B8'] / med['A8']:.3f}   B16 / A16 {med['B16'] / med['A16']:.3f}")
+        line, med[r] = ab.summary(f"{r:3}", times[r], stats[r], RUNS[r][4])
+        lines.append(line)
+    lines.append("  ratios at the median: " + ab.ratios(med, "A") + "   " + ab.ratios(med, "A8", ["B8"]) + "   " + ab.ratios(med, "A16", ["B16"]))
     lines.append("  wave_entries / fetched_entries to A's: " + "   ".join(
         f"{r} {stats[r]['wave_entries'] / max(stats['A']['wave_entries'], 1):.3f} / {stats[r]['fetched_entries'] / max(stats['A']['fetched_entries'], 1):.3f}"
         for r in ("C", "D")))
     same = all(torch.equal(maps[b], maps[p]) and torch.equal(final_T[b], final_T[p]) for b, p in (("B4", "A"), ("B8", "A8"), ("B16", "A16")))
-    counters = all(stats[b][k] == stats["A"][k] for b in ("B4", "B8", "B16") for k in ("wave_entries", "fetched_entries"))
+    counters = all(ab.same_counters(stats, b, "A") for b in ("B4", "B8", "B16"))
     lines.append(f"  B's maps and T == A's: {same};  B's counters are A's: {counters};  mean T: A {float(final_T['A'].mean()):.4f}  "
                  f"C {float(final_T['C'].mean()):.4f}  D {float(final_T['D'].mean()):.4f}")
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "a") as f:
-            f.write(text + "\n")
+    ab.report(lines, a.out, a.label, append=True)
 
 
 if __name__ == "__main__":
-    main()
+    ab.main(__file__, arguments(), worker)

@@ -10,58 +10,31 @@ Python call over all 25 cameras (stages 1-2, the walks, the counters' read-backs
 synchronisations), reported as ms per view: median, min, max and spread over the rounds, and the ratio A / B at the median.
 --dispatches N: instead of timing, run N rounds of ONE leg (--leg forward-A, stats-B8, ...) after one warm-up round, for a kernel
 trace around this process to count: dispatches per view = (count at N = 2 - count at N = 1) / 25.
-The measurement runs in a child process of its own under a time limit (--timeout seconds); this process never opens the GPU.
-Writes what it prints to profiles/views_ab.txt (--out).
+Writes what it prints to profiles/views_ab.txt (--out).  The measurement runs in a child process under a time limit (--timeout
+seconds; tools/ab_harness.py).
 usage: tools/views_ab.py [--workload bicycle] [--rounds 15] [--timeout 540]"""
-import argparse
-import os
-import subprocess
-import sys
-import time
-
-REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, REPO)
+import ab_harness as ab
 
 CHANNELS = 16
 
 
-def arguments():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", default="bicycle")
-    ap.add_argument("--gaussians", type=int, default=0)
-    ap.add_argument("--rounds", type=int, default=15)
-    ap.add_argument("--camera", type=int, default=0)
-    ap.add_argument("--camera-set", default="all")
-    ap.add_argument("--timeout", type=int, default=540)
+def flags(ap):
     ap.add_argument("--dispatches", type=int, default=0)
     ap.add_argument("--leg", default="")
-    ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "views_ab.txt"))
-    return ap.parse_args()
+
+
+def arguments(argv=None):
+    return ab.arguments("views_ab", timeout=540, camera_set="all", early_out=False, extra=flags, argv=argv)
 
 
 def worker(a):
-    import numpy as np
     import torch
 
-    import bench
-    import gsr_amd  # noqa: F401
-    from gsr_amd import renderer, utils
+    f = ab.bench_frame(a, views=(4, 8))
+    from gsr_amd import renderer
 
-    dev = torch.device("cuda", 0)
-    cols, cam_list, n, W, H, _ = bench.build_workload(a.workload, a, a.gaussians)
-    scene = renderer.GaussianScene.from_packed(utils.pack_gaussians(cols), device=dev)
-    del cols
-    cams = [renderer.make_camera(*c) for c in cam_list]
+    n, W, H, dev, R, cams = f.n, f.W, f.H, f.dev, f.R, f.cams
     B = len(cams)
-    R = {1: renderer.Rasterizer(scene), 4: renderer.Rasterizer(scene, views=4), 8: renderer.Rasterizer(scene, views=8)}
-    need = 0
-    for cam in cams:  # one pair bound for all: the worst view's
-        R[1].render(cam)
-        need = max(need, int(R[1].last_stats["n_pairs_bbox"]))
-    for r in R.values():
-        r.max_pairs = int(1.25 * need) + 4096
-        r.sort_passes = R[1].sort_passes
     gen = torch.Generator().manual_seed(3)
     F = torch.randn((n, CHANNELS), generator=gen).to(dev)
     Gm = torch.randn((B, H, W, CHANNELS), generator=gen).to(dev)
@@ -86,41 +59,16 @@ def worker(a):
             torch.cuda.synchronize(dev)
         return
 
-    times = {k: [] for k in legs}
-    for rnd in range(a.rounds + 2):  # the first two rounds warm up (code objects, the allocator, the workspaces)
-        for name, run in legs.items():
-            torch.cuda.synchronize(dev)
-            t0 = time.perf_counter()
-            run()
-            torch.cuda.synchronize(dev)
-            if rnd >= 2:
-                times[name].append((time.perf_counter() - t0) * 1e3 / B)
+    times, _ = ab.interleaved(list(legs.items()), a.rounds, "wall", scale=1.0 / B)
     lines = [f"{a.workload}: {n} gaussians, {W}x{H}, {B} cameras, C = {CHANNELS}, {a.rounds} interleaved rounds after 2 warm-up rounds; ms per view"]
     med = {}
     for name in legs:
-        t = np.array(times[name])
-        med[name] = float(np.median(t))
-        lines.append(f"  {name:12s} median {np.median(t):.4f}  min {t.min():.4f}  max {t.max():.4f}  spread (max - min) / median "
-                     f"{(t.max() - t.min()) / np.median(t) * 100:.1f} %")
+        line, med[name] = ab.summary(name, times[name])
+        lines.append(line)
     for kind in ("forward", "backward", "stats"):
         lines.append(f"  {kind}: A / B4 {med[kind + '-A'] / med[kind + '-B4']:.3f}   A / B8 {med[kind + '-A'] / med[kind + '-B8']:.3f}")
-    text = "\n".join(lines)
-    print(text)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write(text + "\n")
-
-
-def main():
-    a = arguments()
-    if a.worker:
-        return worker(a)
-    # the one GPU step, in a process of its own and under its own time limit
-    rc = subprocess.run(["timeout", "-k", "10", str(a.timeout), sys.executable, os.path.abspath(__file__), "--worker"] + sys.argv[1:]).returncode
-    if rc:
-        sys.exit(f"views_ab: the measurement ended with status {rc}" + (" (time limit)" if rc in (124, 137) else ""))
+    ab.report(lines, a.out)
 
 
 if __name__ == "__main__":
-    main()
+    ab.main(__file__, arguments(), worker)
