@@ -36,7 +36,8 @@ extern "C" {
                             gsr_blend_channels_views / gsr_blend_channels_backward_views / gsr_blend_gaussian_stats_views / gsr_render_channels_batch — feature maps, their gradient and the
                             statistics for several views per launch sequence, with view_hits, the exact number of views that reach a gaussian; gsr_blend_splat_backward /
                             gsr_render_splat_backward — the gradient of a feature map and of the final T with respect to the 2-D splat: opacity, 2-D mean, inverse 2-D covariance, and the
-                            per-pixel absolute mean gradients): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            per-pixel absolute mean gradients; gsr_project_backward — that gradient chained through the projection to the scene's means, log-scales,
+                            quaternions and opacity logits): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -383,6 +384,43 @@ int gsr_render_splat_backward(const GsrScene *scene, const GsrCamera *cam, const
                               int64_t feature_stride, int32_t channels, const float *grad_map /* [.., channels] */,
                               const float *grad_T /* may be NULL */, float min_T, int32_t want_abs, float *grad_splat /* [n][8], ADDS */,
                               void *stream);
+
+/* The projection backward: the splat gradient of a view chained to what the SCENE stores.  Row i of grad_splat ([n][8] float32, as
+ * gsr_blend_splat_backward writes it; columns 0-5 = d L / d opacity, mean_x, mean_y, s0, s1, s2 are read, columns 6 and 7 are
+ * ignored) is carried through the transpose of gsr_preprocess' geometry for gaussian i under this camera, and the result is ADDED
+ * into four arrays laid out like the scene's: grad_means [n,3], grad_log_scales [n,3], grad_quats [n,4] (w, x, y, z as stored, not
+ * normalised), grad_opacity_logit [n].  Any of the four may be NULL (not all): a NULL output and the work feeding only it are
+ * skipped, and each output is bit for bit what it is in a call with all four.  One thread per gaussian, no atomics: two calls with
+ * the same input give the same bits, and adding a row twice doubles it exactly.
+ * The forward is recomputed in fp32 from the expressions of gsr_preprocess, in their operation order, so the chain linearises the
+ * values the forward used.  Stage by stage, last to first:
+ *   sigmas <- cov2d        s0 = c / det, s1 = a / det, s2 = -b01 / det, det = a c - b10 b01, with a, b01, b10, c four separate inputs;
+ *   cov2d <- (T, cov3d)    cov2d = T cov3d T^T + 0.3 I with T = J A^T (A = w2c[:3,:3]); the low-pass is a constant;
+ *   J <- cam_mean          J = [[fx / z, 0, -fx u / z], [0, fy / z, -fy v / z]], u = clamp(x / z, +-lim_x), v likewise;
+ *   cam_mean <- mean       through w2c;
+ *   screen_mean <- mean    through full_proj, the divide 1 / (w + 1e-7) and the NDC -> pixel map (means are in pixels);
+ *   cov3d <- M             cov3d = M M^T, M = R diag(exp(log_scales));
+ *   R <- quaternion        through the normalisation q / max(|q|, 1e-12) (at the floor the divisor is a constant);
+ *   opacity <- logit       sigmoid(x) sigmoid(-x), which keeps its digits where 1 - sigmoid(x) has lost them.
+ * Clamp rule: where the ray clamp is active the derivative in x / z is 0, and t_x = +-lim_x z still depends on z (likewise y).
+ * Held fixed: the tile rect, the footprint, the 1/255 threshold and the cull — the support gsr_blend_splat_backward already holds
+ * fixed.  No colour term: nothing flows through the SH evaluation (the view direction's part of d / d mean is not included).
+ * Skip rule: a gaussian whose six values are all zero is not touched — its rows of the outputs are neither read nor written, and
+ * a wave of 64 consecutive such gaussians reads nothing but their rows of grad_splat.  A gaussian contributes nothing either when
+ * the forward culls it (z_cam < GSR_CULL_Z), when its det is 0, when a conic entry is not finite, or, with reference_compat,
+ * when a conic entry is 0 (the reference never draws it): whatever its row holds.
+ * Needs no workspace and no lists; depends on the scene, the camera and opts->reference_compat only.  The scene's arrays are read,
+ * never written: a caller that updates a resident scene in place must rebuild what was derived from it (block_bounds, the order).
+ *   - grad_splat must be finite where it is not zero.
+ *   - No output may alias grad_splat (refused), another output or an array of the scene (not checked: the caller's to keep);
+ *     grad_splat and grad_quats must be 16-byte aligned.
+ * GSR_ERR_BAD_ARG, before any HIP call, for a null scene, camera, options or grad_splat, all four outputs NULL, an output that
+ * aliases grad_splat, a misaligned grad_splat or grad_quats, a scene gsr_preprocess refuses (sh_dtype), output_dtype = 1,
+ * accum_dtype = 1.  Single views: sum over cameras by calling it once per view into the same outputs. */
+int gsr_project_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts,
+                         const float *grad_splat /* [n][8], columns 0-5 read */,
+                         float *grad_means /* [n,3] ADDS, may be NULL */, float *grad_log_scales /* [n,3] */,
+                         float *grad_quats /* [n,4] */, float *grad_opacity_logit /* [n] */, void *stream);
 
 /* Stage 3 for what no blended channel can hold — per pixel p, over the same depth-ordered lists and with the same weights
  * w_i = alpha_i T_i (and the same T, bit for bit) as gsr_blend_features (no reference counterpart):

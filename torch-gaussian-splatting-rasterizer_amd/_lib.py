@@ -138,6 +138,7 @@ EXPORTS = [
     "gsr_lists_views", "gsr_blend_channels_views", "gsr_blend_channels_backward_views", "gsr_blend_gaussian_stats_views",
     "gsr_render_channels_batch",
     "gsr_blend_splat_backward", "gsr_render_splat_backward",
+    "gsr_project_backward",
 ]
 
 
@@ -175,6 +176,8 @@ def _load() -> C.CDLL:
     splat = [vp, i64, i32, vp, vp, C.c_float, i32, vp, vp]  # features, their stride, channels, grad_map, grad_T, min_T, want_abs, grad_splat [n][8], stream
     L.gsr_blend_splat_backward.argtypes = lists + splat
     L.gsr_render_splat_backward.argtypes = view + splat
+    # scene, camera, options, grad_splat [n][8], grad_means, grad_log_scales, grad_quats, grad_opacity_logit (each may be NULL), stream
+    L.gsr_project_backward.argtypes = [scene_p, cam_p, opts_p, vp, vp, vp, vp, vp, vp]
     L.gsr_render_batch.argtypes = [scene_p, cam_p, i32, opts_p, i64, vp, sz, vp, i64, vp]
     views = [cam_p, i32, opts_p, i64, vp, sz]        # gsr_*_views: cameras [host], how many, options, max_pairs, workspace, its bytes
     L.gsr_lists_views.argtypes = [scene_p] + views + [vp]

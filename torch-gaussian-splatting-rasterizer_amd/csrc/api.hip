@@ -845,6 +845,35 @@ int gsr_render_splat_backward(const GsrScene *scene, const GsrCamera *cam, const
                            SplatBackward{features, feature_stride, channels, grad_map, grad_T, min_T, want_abs, grad_splat});
 }
 
+// The splat gradient of a view chained to the scene's parameters: no workspace, no lists — the scene, the camera and reference_compat
+int gsr_project_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, const float *grad_splat, float *grad_means,
+                         float *grad_log_scales, float *grad_quats, float *grad_opacity_logit, void *stream)
+{
+    if (!scene) { set_error("null scene"); return GSR_ERR_BAD_ARG; }
+    int rc = check_camera_options(cam, opts);
+    if (rc) return rc;
+    if (!grad_splat) { set_error("null splat gradient"); return GSR_ERR_BAD_ARG; }
+    if (!grad_means && !grad_log_scales && !grad_quats && !grad_opacity_logit) { set_error("null geometry gradients: all four"); return GSR_ERR_BAD_ARG; }
+    const size_t rows = scene->n > 0 ? (size_t)scene->n : 0;
+    const uintptr_t gs = reinterpret_cast<uintptr_t>(grad_splat);
+    const struct { const float *p; size_t floats; const char *name; } outs[4] = {
+        {grad_means, 3, "grad_means"}, {grad_log_scales, 3, "grad_log_scales"}, {grad_quats, 4, "grad_quats"}, {grad_opacity_logit, 1, "grad_opacity_logit"}};
+    for (const auto &o : outs) {
+        const uintptr_t b = reinterpret_cast<uintptr_t>(o.p);
+        if (b && (b == gs || (b < gs + 32 * rows && gs < b + 4 * o.floats * rows))) {
+            set_error("%s aliases grad_splat", o.name); return GSR_ERR_BAD_ARG;
+        }
+    }
+    if (reinterpret_cast<uintptr_t>(grad_splat) % 16 != 0) { set_error("grad_splat must be 16-byte aligned"); return GSR_ERR_BAD_ARG; }
+    if (reinterpret_cast<uintptr_t>(grad_quats) % 16 != 0) { set_error("grad_quats must be 16-byte aligned"); return GSR_ERR_BAD_ARG; }
+    rc = check_scene(scene);
+    if (rc) return rc;
+    rc = refuse_bf16(opts, "geometry gradients are float32", "geometry gradients are");
+    if (rc) return rc;
+    return launch_project_backward(*scene, *cam, *opts, grad_splat, grad_means, grad_log_scales, grad_quats, grad_opacity_logit,
+                                   static_cast<hipStream_t>(stream));
+}
+
 int gsr_blend_gaussian_stats(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                              size_t workspace_bytes, const uint8_t *pixel_mask, float *weight_sum, float *weight_max, uint32_t *pixels,
                              void *stream)

@@ -206,6 +206,17 @@ struct FramePlan {
 };
 FramePlan plan_frame(const Workspace &ws, const GsrOptions &opts);  // ws: after check_frame, with ws.views set
 
+// A view's camera as the per-gaussian kernels hold it (preprocess.hip, project_backward.hip): a kernel argument
+struct Cam {
+    float V[16];
+    float F[16];
+    float cc[3];
+    float fx, fy, limx, limy;
+    float w_sigma2;  // largest eigenvalue of A^T A, A = w2c[:3,:3] (1 for a unit qvec), padded: bounds |J A| in the shard kernel's phase 1
+    int W, H;
+};
+Cam make_cam(const GsrCamera &c);  // preprocess.hip
+
 // ---- kernels' host launchers (each returns GSR_OK / GSR_ERR_HIP) --------------------------------
 // cams: ws.views cameras (one frame size); ctrl_reset_words: how much of each view's control block the frame clears
 int launch_preprocess(const GsrScene &scene, const GsrCamera *cams, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
@@ -279,6 +290,10 @@ int launch_blend_gstats(const GsrCamera &cam, const GsrOptions &opts, const Work
 int launch_blend_splat_backward(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan,
                                 const float *features, int64_t stride, int channels, const float *grad_map, const float *grad_T,
                                 float min_T, bool want_abs, float *grad_splat, hipStream_t s);
+// The transpose of stage 1's geometry (project_backward.hip): row i of grad_splat [n][8] (columns 0-5) chained to gaussian i's mean,
+// log-scales, quaternion and opacity logit, ADDED into the four arrays that are not null; no workspace, no lists
+int launch_project_backward(const GsrScene &scene, const GsrCamera &cam, const GsrOptions &opts, const float *grad_splat, float *grad_means,
+                            float *grad_log_scales, float *grad_quats, float *grad_opacity_logit, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

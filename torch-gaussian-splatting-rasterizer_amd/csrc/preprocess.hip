@@ -19,15 +19,6 @@
 
 namespace gsr {
 
-struct Cam {
-    float V[16];
-    float F[16];
-    float cc[3];
-    float fx, fy, limx, limy;
-    float w_sigma2;  // largest eigenvalue of A^T A, A = w2c[:3,:3] (1 for a unit qvec), padded: bounds |J A| in the shard kernel's phase 1
-    int W, H;
-};
-
 // What the geometry half of the per-gaussian work hands on (to the colour half and to whoever writes the outputs).
 struct GeoOut {
     bool visible;     // enters this rank's depth sort with a non-empty tile rect
@@ -742,7 +733,7 @@ __global__ __launch_bounds__(256) void shard_compact_kernel(const uint32_t *__re
     if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_records = before;
 }
 
-static Cam make_cam(const GsrCamera &c)
+Cam make_cam(const GsrCamera &c)
 {
     Cam k;
     for (int j = 0; j < 16; ++j) { k.V[j] = c.w2c[j]; k.F[j] = c.full_proj[j]; }

@@ -397,6 +397,64 @@ def opacity_logit_gradient(scene: "GaussianScene", g: SplatGradient, scene_order
     return g.opacity * chain
 
 
+class GeometryGradient(NamedTuple):
+    """project_backward / Rasterizer.geometry_gradient: per gaussian, the gradient with respect to what the scene stores, laid out
+    like its arrays — means [n, 3], log_scales [n, 3], quats [n, 4] (w, x, y, z as stored, not normalised), opacity_logit [n].
+    All float32; a field that was left out of `out` is None."""
+    means: Optional[torch.Tensor]
+    log_scales: Optional[torch.Tensor]
+    quats: Optional[torch.Tensor]
+    opacity_logit: Optional[torch.Tensor]
+
+
+def _geometry_buffers(scene: "GaussianScene", out: Optional[GeometryGradient]) -> list:
+    """The four tensors a projection backward adds into: new zeroed ones, or those of `out` once they are what it takes."""
+    dev, n = scene.device, scene.n
+    shapes = ((n, 3), (n, 3), (n, 4), (n,))
+    if out is None:
+        return [torch.zeros(s, dtype=torch.float32, device=dev) for s in shapes]
+    bufs = list(out)
+    if len(bufs) != 4 or all(b is None for b in bufs):
+        raise ValueError("out must be a GeometryGradient with at least one tensor")
+    for name, b, s in zip(GeometryGradient._fields, bufs, shapes):
+        if b is not None and (tuple(b.shape) != s or b.dtype != torch.float32 or b.device != dev or not b.is_contiguous()):
+            raise ValueError(f"out.{name} must be a contiguous float32 tensor of shape {list(s)} on the scene's device")
+    return bufs
+
+
+def project_backward(scene: "GaussianScene", cam: GsrCamera, splat_rows: torch.Tensor, opts: Optional[GsrOptions] = None,
+                     out: Optional[GeometryGradient] = None, scene_order: bool = False) -> GeometryGradient:
+    """The splat gradient of a view chained through the preprocess' projection to the scene's own parameters
+    (gsr_project_backward): one pass, one thread per gaussian, the forward recomputed in fp32 from the preprocess' expressions.
+    splat_rows: [n, 8] float32 contiguous on the scene's device, in the SCENE's order, columns (opacity, mean x, y, s0, s1, s2, -,
+    -) as splat_gradient(out=) fills them; columns 6 and 7 are ignored.  A row of six zeros is skipped: the gaussian's gradients are
+    not touched.  Gaussians the view culls (z_cam < 0.2), or whose 2-D covariance is singular, contribute nothing whatever their row
+    holds.  Held fixed: the tile rect, the footprint, the 1/255 threshold and the cull; where the ray clamp is active the derivative
+    in x / z is 0.  No colour term (the SH view direction's part of d / d mean is not included).
+    Returns a GeometryGradient in the order of the file the scene was loaded from (scene_order=True: of the scene's resident
+    arrays).  With `out` — a GeometryGradient of float32 contiguous tensors on the scene's device, in the SCENE's order; a field that
+    is None is not computed — the gradient is ACCUMULATED into its tensors and `out` is returned: summing over a camera set needs
+    no temporary.  No atomics: two calls give the same bits.
+    The scene's arrays are read, never written.  A caller that steps a resident scene's tensors in place must rebuild what was
+    derived from them: the block bounds (GaussianScene.build_bounds()), and the Morton order goes stale as the means move."""
+    opts = opts or make_options()
+    dev, n = scene.device, scene.n
+    _require_cuda(splat_rows, "splat_rows")
+    if tuple(splat_rows.shape) != (n, 8) or splat_rows.dtype != torch.float32 or splat_rows.device != dev or not splat_rows.is_contiguous():
+        raise ValueError(f"splat_rows must be a contiguous float32 tensor of shape [{n}, 8] on the scene's device")
+    bufs = _geometry_buffers(scene, out)
+    if n:
+        sc = scene.c_struct()
+        with torch.cuda.device(dev):
+            check(lib.gsr_project_backward(C.byref(sc), C.byref(cam), C.byref(opts), splat_rows.data_ptr(),
+                                           *[b.data_ptr() if b is not None else None for b in bufs], _stream_ptr(dev)))
+    if out is not None:
+        return out
+    if scene_order:
+        return GeometryGradient(*bufs)
+    return GeometryGradient(*[file_order_gradient(b, scene.order_t) for b in bufs])
+
+
 TOPK_SELECT = {"heaviest": _lib.GSR_TOPK_HEAVIEST, "nearest": _lib.GSR_TOPK_NEAREST}
 
 
@@ -500,6 +558,7 @@ class Rasterizer:
         self.unchecked = UncheckedFrames()
         self.last_stats: Optional[Dict[str, int]] = None
         self.last_slice_stats: list = []   # stats() per slice: the last view each slice rendered
+        self._splat_rows: Optional[torch.Tensor] = None  # geometry_gradient's [n, 8] scratch, zeroed on every call
 
     # -- workspace ------------------------------------------------------------------------------
     def _workspace(self, width: int, height: int) -> torch.Tensor:
@@ -888,6 +947,27 @@ class Rasterizer:
         self._accumulate_view(cam, opts, "splat gradient", None if out is not None else [buf], lib.gsr_render_splat_backward,
                               lib.gsr_blend_splat_backward, *tail, buf.data_ptr())
         return result(buf, out is not None or scene_order)
+
+    # -- the gradient of a feature map with respect to the scene's geometry ---------------------------------------------------------
+    def geometry_gradient(self, cam: GsrCamera, features: torch.Tensor, grad_map: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
+                          opts: Optional[GsrOptions] = None, min_T: float = 0.0, out: Optional[GeometryGradient] = None,
+                          scene_order: bool = False) -> GeometryGradient:
+        """The gradient of L = <grad_map, render_features(cam, features)> + <grad_T, final T> with respect to every gaussian's mean,
+        log-scales, quaternion and opacity logit: splat_gradient (checked and re-run like any frame) into an [n, 8] scratch kept on
+        this Rasterizer and zeroed on every call, then project_backward under the same camera and options.  Arguments as
+        splat_gradient's (scene_order applies to the features and to the result); what is held fixed, the clamp rule and the missing
+        colour term are project_backward's.  Returns a GeometryGradient in the file's order (scene_order=True: the scene's).  With
+        `out` (project_backward's: tensors in the SCENE's order, None = not computed) the view's gradient is ACCUMULATED into it, as
+        feature_gradient(out=) does: a camera set is one call per view.  The splat gradient's float atomic sums may differ in the
+        last bits between two calls; the projection adds nothing to that."""
+        n, dev = self.scene.n, self.scene.device
+        if out is not None:
+            _geometry_buffers(self.scene, out)  # refused before the splat gradient runs, not after
+        if self._splat_rows is None or tuple(self._splat_rows.shape) != (n, 8):
+            self._splat_rows = torch.empty((n, 8), dtype=torch.float32, device=dev)
+        rows = self._splat_rows.zero_()
+        self.splat_gradient(cam, features, grad_map, grad_T, opts, min_T, abs_mean=False, out=rows, scene_order=scene_order)
+        return project_backward(self.scene, cam, rows, opts, out, scene_order)
 
     def blend_weights(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[n]: every gaussian's blend weight summed over the drawn pixels of this view, sum_p w_i(p) — feature_gradient of a
