@@ -1,10 +1,12 @@
 """CPU: what the test_*_abi.py files state in common about a pair of entry points added to ABI 0.6.0.  The per-entry tables —
 argument positions and types, prototype tails, refusal cases and their words, header sentences, whose recipe a kernel's must
 equal — stay in those files; this is the scaffold around them.  A plain module next to the tests; gsr_amd is imported inside the
-functions, like in the tests that call them."""
+functions, like in the tests that call them.  Also theirs: a Rasterizer without a workspace, for the checks a call makes before it
+reaches for one."""
 import ctypes as C
 import os
 import re
+import types
 
 from conftest import REPO
 
@@ -93,3 +95,32 @@ def assert_own_translation_unit(stem):
     mk = open(os.path.join(CSRC, "Makefile")).read()
     assert os.path.exists(os.path.join(CSRC, stem + ".hip"))
     assert re.search(rf"^OBJS\s*=.*\b{re.escape(stem)}\.o\b", mk, flags=re.M)
+
+
+class NoWorkspace(Exception):
+    pass
+
+
+def rasterizer(n=5, views=4, order_t=None):
+    """A Rasterizer on a scene that lives nowhere: whatever reaches for a workspace or the library raises."""
+    import torch
+
+    from gsr_amd import renderer
+
+    R = renderer.Rasterizer.__new__(renderer.Rasterizer)
+    R.scene = types.SimpleNamespace(n=n, device=torch.device("cpu"), order_t=order_t)
+    R.unchecked, R.sort_passes, R.max_pairs, R.views = renderer.UncheckedFrames(), 0, 1 << 20, views
+
+    def no_workspace(*a, **k):
+        raise NoWorkspace()
+
+    R._workspace = no_workspace
+    return R
+
+
+def cam(w=40, h=24):
+    from gsr_amd import _lib
+
+    c = _lib.GsrCamera()
+    c.width, c.height = w, h
+    return c

@@ -42,9 +42,14 @@ CALLS = {
     "gradient": ((), ("gsr_render_channels_backward",), ()),
     "weights": ((), ("gsr_render_channels_backward",), ()),
     "view_stats": ((), ("gsr_render_gaussian_stats",), ()),
+    "splat": ((), ("gsr_render_splat_backward",), ()),
     "gradient_out": ((), LISTS, ("gsr_blend_channels_backward",)),
     "weights_out": ((), LISTS, ("gsr_blend_channels_backward",)),
     "view_stats_out": ((), LISTS, ("gsr_blend_gaussian_stats",)),
+    "splat_out": ((), LISTS, ("gsr_blend_splat_backward",)),
+    # geometry_gradient: the splat gradient into the rasterizer's own [n, 8] scratch, as into any caller's `out`, then the projection
+    "geometry": ((), LISTS, ("gsr_blend_splat_backward", "gsr_project_backward")),
+    "geometry_out": ((), LISTS, ("gsr_blend_splat_backward", "gsr_project_backward")),
     "render_batch": ((), ("gsr_render_batch",), ()),
     "features_batch5": ((), ("gsr_render_channels_batch",), ()),
     "gradient_batch": ((), ("gsr_lists_views",), ("gsr_blend_channels_backward_views",)),
@@ -53,8 +58,9 @@ CALLS = {
     "view_stats_batch_out": ((), ("gsr_lists_views",), ("gsr_blend_gaussian_stats_views",)),
 }
 BATCH = tuple(name for name in CALLS if "batch" in name)  # three cameras through a Rasterizer(views=2); for these the triple is per group
-# outputs that are float atomic sums, by position in the result
-ATOMIC = {"gradient": (0,), "weights": (0,), "view_stats": (0,), "gradient_batch": (0,), "view_stats_batch": (0,)}
+# outputs that are float atomic sums (or, the geometry gradient, derived from them), by position in the result
+ATOMIC = {"gradient": (0,), "weights": (0,), "view_stats": (0,), "gradient_batch": (0,), "view_stats_batch": (0,),
+          "splat": (0, 1, 2), "geometry": (0, 1, 2, 3)}
 
 
 class _Recorder:
@@ -125,7 +131,7 @@ def _flat(res):
 
 def _run(S, R, name, o, outs=None):
     """One public call by its CALLS name -> the list of tensors it returns.  `outs`: the buffers of an accumulating call."""
-    cam, rows, VS = S.cam, _rows(S, o), S.renderer.ViewStats
+    cam, rows, VS, GG = S.cam, _rows(S, o), S.renderer.ViewStats, S.renderer.GeometryGradient
     cams = [cam] * 3
     plane = lambda v: torch.full((rows, cam.width), v, dtype=torch.float32, device="cuda")
     if name.endswith("_out") and outs is None:
@@ -144,9 +150,13 @@ def _run(S, R, name, o, outs=None):
         "gradient": lambda: R.feature_gradient(cam, S.G[:rows], o, scene_order=True),
         "weights": lambda: R.blend_weights(cam, o),
         "view_stats": lambda: R.view_stats(cam, o, scene_order=True),
+        "splat": lambda: R.splat_gradient(cam, S.F, S.G[:rows], opts=o, scene_order=True),
+        "geometry": lambda: R.geometry_gradient(cam, S.F, S.G[:rows], opts=o, scene_order=True),
         "gradient_out": lambda: R.feature_gradient(cam, S.G[:rows], o, out=outs[0]),
         "weights_out": lambda: R.blend_weights(cam, o, out=outs[0]),
         "view_stats_out": lambda: R.view_stats(cam, o, out=VS(*outs)),
+        "splat_out": lambda: _splat_rows_of(R.splat_gradient(cam, S.F, S.G[:rows], opts=o, out=outs[0], scene_order=True), outs[0]),
+        "geometry_out": lambda: R.geometry_gradient(cam, S.F, S.G[:rows], opts=o, out=GG(*outs), scene_order=True),
         "render_batch": lambda: R.render_batch(cams, o),
         "features_batch5": lambda: R.render_features_batch(cams, S.F, o, return_T=True),
         "gradient_batch": lambda: R.feature_gradient_batch(cams, S.G3[:, :rows], o, scene_order=True),
@@ -157,8 +167,20 @@ def _run(S, R, name, o, outs=None):
     return _flat(call())
 
 
+def _splat_rows_of(g, rows):
+    """splat_gradient(out=rows) returns views of `rows`, columns (opacity, mean x, y, s0, s1, s2, -, -): the buffer itself."""
+    assert g.abs_mean2d is None and [(t.data_ptr() - rows.data_ptr()) // 4 for t in g[:3]] == [1, 3, 0]
+    assert (tuple(g.mean2d.shape), tuple(g.sigmas.shape), tuple(g.opacity.shape)) == ((len(rows), 2), (len(rows), 3), (len(rows),))
+    assert all(t.stride(0) == 8 for t in g[:3]) or len(rows) == 0
+    return rows
+
+
 def _zero_outs(S, name):
     n = S.scene.n
+    if name == "splat_out":
+        return [torch.zeros((n, 8), device="cuda")]
+    if name == "geometry_out":
+        return [torch.zeros(s, device="cuda") for s in ((n, 3), (n, 3), (n, 4), (n,))]
     if name in ("gradient_out", "gradient_batch_out"):
         return [torch.zeros((n, 5), device="cuda")]
     if name == "weights_out":
@@ -178,8 +200,9 @@ def _sequence(name, attempts):
 
 
 def _adds_after_the_check(name):
-    """The call's blend adds into a buffer, so it runs after its lists were checked: with `out`, and the two batches always."""
-    return name.endswith("_out") or name in ("gradient_batch", "view_stats_batch")
+    """The call's blend adds into a buffer, so it runs after its lists were checked: with `out`, the two batches always, and
+    geometry_gradient, whose splat gradient goes into a scratch as into an `out`."""
+    return name.endswith("_out") or name in ("gradient_batch", "view_stats_batch", "geometry")
 
 
 def _rasterizer(S, name):
@@ -187,8 +210,10 @@ def _rasterizer(S, name):
 
 
 def _check_closing_blend(rec, name):
-    """An accumulating call's blend runs once, after the last check, with colour_stage = 0 and the depth-sort bound its lists got."""
-    (blend, bo), (sort, so) = rec.calls[-1], rec.calls[-3]
+    """An accumulating call's blend runs once, after the last check (first of the entries that follow it), with colour_stage = 0 and
+    the depth-sort bound its lists got."""
+    k = len(CALLS[name][2])
+    (blend, bo), (sort, so) = rec.calls[-k], rec.calls[-k - 2]
     assert blend == CALLS[name][2][0] and sort == ("gsr_lists_views" if name in BATCH else "gsr_bin_sort"), rec.names()
     assert bo["colour_stage"] == 0 and bo["depth_sort_passes"] == so["depth_sort_passes"], (name, bo, so)
 
@@ -260,7 +285,9 @@ def test_an_overflowed_attempt_is_run_again_and_leaves_no_trace(S, rec, name):
     if name == "weights_out":  # blend_weights without `out` answers in file order, `out` is in the scene's
         o_t = S.scene.order_t
         ref = ref if o_t is None else [ref[0].index_select(0, o_t)]
-    outs = [ref[0].clone()]
+    if name == "splat_out":  # the [n, 8] rows of the three fields; columns 6 and 7 stay as they are without abs_mean
+        ref = [torch.cat([ref[2][:, None], ref[0], ref[1], torch.zeros_like(ref[0])], 1)]
+    outs = [r.clone() for r in ref] if name in ("splat_out", "geometry_out") else [ref[0].clone()]
     if name in ("view_stats_out", "view_stats_batch_out"):
         mid = float(ref[1][ref[1] > 0].median())
         outs += [torch.full_like(ref[1], mid)] + [torch.full_like(r, 7) for r in ref[2:]]
@@ -269,7 +296,78 @@ def test_an_overflowed_attempt_is_run_again_and_leaves_no_trace(S, rec, name):
     assert small.max_pairs > 64
     _check_closing_blend(rec, name)
     assert all(g is o for g, o in zip(got, outs))
-    _bar(f"{name} sum after a retry", outs[0].cpu().numpy(), 2.0 * ref[0].double().cpu().numpy())
+    for k in range(len(outs) if name in ("splat_out", "geometry_out") else 1):
+        _bar(f"{name}[{k}] sum after a retry", outs[k].cpu().numpy(), 2.0 * ref[k].double().cpu().numpy())
     if name in ("view_stats_out", "view_stats_batch_out"):
         assert bool((ref[1] > mid).any()) and bool(((ref[1] > 0) & (ref[1] < mid)).any())
         assert torch.equal(outs[1], torch.clamp(ref[1], min=mid)) and all(torch.equal(o, r + 7) for o, r in zip(outs[2:], ref[2:]))
+
+
+def test_the_per_gaussian_calls_refuse_before_they_allocate_and_an_empty_shard_reaches_no_workspace(S, rec):
+    """The accumulating calls a CPU stub cannot reach (their first look is whether a tensor lives on the GPU): a bad `out`, grad_T or
+    splat_rows is refused with ValueError, good arguments get as far as the workspace, and a shard without tile rows gets zeros —
+    or `out` back, bit for bit as it was — without one.  A five-gaussian scene in file order, 40 x 24; no kernel of the render path
+    runs (gsr_project_backward over rows of zeros may: it adds nothing)."""
+    renderer, cam, GG = S.renderer, S.cam, S.renderer.GeometryGradient
+    gen = torch.Generator().manual_seed(5)
+    q = torch.randn((5, 4), generator=gen)
+    packed = dict(means=torch.tensor([[0.0, 0.0, 2.0]]) + 0.1 * torch.randn((5, 3), generator=gen), log_scales=torch.full((5, 3), -3.0),
+                  quats=q / q.norm(dim=1, keepdim=True), opacity_logit=torch.zeros(5), sh=torch.zeros((5, 16, 3)))
+    scene = renderer.GaussianScene.from_packed({k: v.numpy() for k, v in packed.items()}, spatial_order=False)
+    R = renderer.Rasterizer(scene, views=2)
+
+    class NoWorkspace(Exception):
+        pass
+
+    def no_workspace(*a, **k):
+        raise NoWorkspace()
+
+    R._workspace = no_workspace
+    z = lambda *shape, **kw: torch.zeros(shape, device="cuda", **kw)
+    F, G, T = z(5, 2), z(24, 40, 2), z(24, 40)
+    geo = GG(z(5, 3), z(5, 3), z(5, 4), z(5))
+    calls = {  # name -> (the call with `out`, a good out, bad ones)
+        "gradient": (lambda o, out: R.feature_gradient(cam, G[:_rows(S, o)], o, out=out), z(5, 2),
+                     [z(5, 3), z(4, 2), z(5, 2, dtype=torch.float64), torch.zeros((5, 2)), z(2, 5).t(), z(10)]),
+        "gradient_batch": (lambda o, out: R.feature_gradient_batch([cam] * 3, z(3, 24, 40, 2)[:, :_rows(S, o)], o, out=out), z(5, 8)[:, 2:4],
+                           [z(5, 3), z(5, 2, dtype=torch.float16), torch.zeros((5, 2)), z(5, 4)[:, ::2]]),
+        "splat": (lambda o, out: R.splat_gradient(cam, F, G[:_rows(S, o)], T[:_rows(S, o)], o, out=out), z(5, 8),
+                  [z(5, 7), z(8, 5), z(5, 8, dtype=torch.float64), torch.zeros((5, 8)), z(5, 16)[:, ::2], z(8, 5).t()]),
+        "geometry": (lambda o, out: R.geometry_gradient(cam, F, G[:_rows(S, o)], T[:_rows(S, o)], o, out=out), geo,
+                     [GG(None, None, None, None), tuple(geo)[:3], geo._replace(means=z(5, 4)), geo._replace(quats=z(5, 4, dtype=torch.float64)),
+                      geo._replace(log_scales=torch.zeros((5, 3))), geo._replace(opacity_logit=z(10)[::2]), geo._replace(quats=z(4, 5).t())]),
+    }
+    mk = renderer.make_options
+    empty = mk(tile_row_begin=2, tile_row_step=3, output_layout=2)  # two tile rows, the third of three shards
+    for name, (call, good, bad) in calls.items():
+        for out in bad:
+            with pytest.raises(ValueError, match="out"):
+                call(mk(), out)
+        for out in (None, good):
+            with pytest.raises(NoWorkspace):
+                call(mk(), out)
+        res = _flat(call(empty, None))
+        assert res and all(t.shape[0] == 5 and t.is_cuda and not t.any() for t in res), name
+        outs = _flat(good)
+        for t in outs:
+            t.fill_(3.0)
+        got = _flat(call(empty, good))
+        held = {t.untyped_storage().data_ptr() for t in outs}
+        assert all(bool((t == 3.0).all()) for t in outs) and all(g.untyped_storage().data_ptr() in held for g in got), name
+        assert R.unchecked.slices == 0 and not R.unchecked.empty, name  # the shard left no mark
+    # grad_T and the splat rows
+    for bad_T in (z(40, 24), torch.zeros((24, 40)), z(24, 40, 1), 1.0):
+        with pytest.raises(ValueError, match="grad_T"):
+            R.splat_gradient(cam, F, G, bad_T)
+        with pytest.raises(ValueError, match="grad_T"):
+            R.geometry_gradient(cam, F, G, bad_T)
+    for bad_rows in (z(5, 7), z(4, 8), z(5, 8, dtype=torch.float64), z(5, 16)[:, ::2], z(8, 5).t()):
+        with pytest.raises(ValueError, match="splat_rows"):
+            renderer.project_backward(scene, cam, bad_rows)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        renderer.project_backward(scene, cam, torch.zeros((5, 8)))
+    for out in calls["geometry"][2]:
+        with pytest.raises(ValueError, match="out"):
+            renderer.project_backward(scene, cam, z(5, 8), out=out)
+    assert set(rec.names()) <= {"gsr_project_backward"}, rec.names()
+    assert R._ws is None

@@ -86,31 +86,10 @@ def test_the_new_kernel_has_a_translation_unit_of_its_own():
     assert [d for d in rule[0].split() if d != "blend_gstats.hip"] == [d for d in grad[0].split() if d != "blend_channels_backward.hip"]
 
 
-class _NoWorkspace(Exception):
-    pass
-
-
-def _rasterizer(n=5):
-    """A Rasterizer on a scene that lives nowhere: whatever reaches for a workspace or the library raises."""
+def test_view_stats_refuses_bad_arguments_before_it_allocates():
     from gsr_amd import renderer
 
-    R = renderer.Rasterizer.__new__(renderer.Rasterizer)
-    R.scene = types.SimpleNamespace(n=n, device=torch.device("cpu"), order_t=None)
-    R.unchecked, R.sort_passes, R.max_pairs = renderer.UncheckedFrames(), 0, 1 << 20
-
-    def no_workspace(*a, **k):
-        raise _NoWorkspace()
-
-    R._workspace = no_workspace
-    return R
-
-
-def test_view_stats_refuses_bad_arguments_before_it_allocates():
-    from gsr_amd import _lib, renderer
-
-    R = _rasterizer()
-    cam = _lib.GsrCamera()
-    cam.width, cam.height = 40, 24
+    R, cam = abi.rasterizer(views=1), abi.cam()
     VS = renderer.ViewStats
     good_mask = torch.ones((24, 40), dtype=torch.bool)
     good_out = VS(torch.zeros(5), torch.zeros(5), torch.zeros(5, dtype=torch.int32))
@@ -136,10 +115,10 @@ def test_view_stats_refuses_bad_arguments_before_it_allocates():
     for kw in (dict(mask=good_mask), dict(mask=good_mask.to(torch.uint8)), dict(out=good_out),
                dict(mask=good_mask.t().contiguous(), opts=renderer.make_options(output_layout=1)),
                dict(out=VS(None, good_out.weight_max, None), want=("max",)), dict(want=["pixels"])):
-        with pytest.raises(_NoWorkspace):
+        with pytest.raises(abi.NoWorkspace):
             R.view_stats(cam, **kw)
     # nothing to draw: zeros, or `out` as it is, without a workspace
-    E = _rasterizer(0)
+    E = abi.rasterizer(0, views=1)
     st = E.view_stats(cam, want=("max", "pixels"))
     assert st.weight_sum is None and st.weight_max.shape == (0,) and st.pixels.dtype == torch.int32
     empty = renderer.make_options(tile_row_begin=2, tile_row_step=3, output_layout=2)  # two tile rows, the third of three shards

@@ -178,43 +178,16 @@ def test_the_refusal_of_several_views_stays_where_it_was():
         assert "WalkViews::Several" not in src[f], f
 
 
-class _NoWorkspace(Exception):
-    pass
-
-
-def _rasterizer(n=5, views=4):
-    """A Rasterizer on a scene that lives nowhere: whatever reaches for a workspace or the library raises."""
-    from gsr_amd import renderer
-
-    R = renderer.Rasterizer.__new__(renderer.Rasterizer)
-    R.scene = types.SimpleNamespace(n=n, device=torch.device("cpu"), order_t=None)
-    R.unchecked, R.sort_passes, R.max_pairs, R.views = renderer.UncheckedFrames(), 0, 1 << 20, views
-
-    def no_workspace(*a, **k):
-        raise _NoWorkspace()
-
-    R._workspace = no_workspace
-    return R
-
-
-def _cam(w=40, h=24):
-    from gsr_amd import _lib
-
-    cam = _lib.GsrCamera()
-    cam.width, cam.height = w, h
-    return cam
-
-
 def test_view_stats_batch_refuses_bad_arguments_before_it_allocates():
     from gsr_amd import renderer
 
-    R, VS = _rasterizer(), renderer.ViewStats
-    cams = [_cam(), _cam(), _cam()]
+    R, VS = abi.rasterizer(), renderer.ViewStats
+    cams = [abi.cam(), abi.cam(), abi.cam()]
     m = torch.ones((24, 40), dtype=torch.bool)
     vs = VS(torch.zeros(5), torch.zeros(5), torch.zeros(5, dtype=torch.int32))
     views = torch.zeros(5, dtype=torch.int32)
     bad = [
-        dict(cams=[]), dict(cams=[_cam(), _cam(40, 32)]), dict(opts=renderer.make_options(output_layout=1)),
+        dict(cams=[]), dict(cams=[abi.cam(), abi.cam(40, 32)]), dict(opts=renderer.make_options(output_layout=1)),
         dict(masks=[m, None]),                                           # one entry per camera
         dict(masks=[m, None, torch.ones((40, 24), dtype=torch.bool)]),   # the transposed shape
         dict(masks=[m, m.float(), None]), dict(masks=[m, [[1] * 40] * 24, None]),
@@ -229,10 +202,10 @@ def test_view_stats_batch_refuses_bad_arguments_before_it_allocates():
             R.view_stats_batch(kw.pop("cams", cams), **kw)
     for kw in (dict(), dict(masks=[m, None, m.to(torch.uint8)]), dict(out=(vs, views)), dict(want=["views"]),
                dict(out=(VS(None, None, None), views), want=("views",)), dict(out=(VS(None, vs.weight_max, None), None), want=("max",))):
-        with pytest.raises(_NoWorkspace):
+        with pytest.raises(abi.NoWorkspace):
             R.view_stats_batch(cams, **kw)
     # nothing to draw: zeros, or `out` as it is, without a workspace
-    st, v = _rasterizer(0).view_stats_batch(cams, want=("max", "views"))
+    st, v = abi.rasterizer(0).view_stats_batch(cams, want=("max", "views"))
     assert st.weight_sum is None and st.pixels is None and st.weight_max.shape == (0,) and v.dtype == torch.int32
     empty = renderer.make_options(tile_row_begin=2, tile_row_step=3, output_layout=2)  # two tile rows, the third of three shards
     st, v = R.view_stats_batch(cams, empty)
@@ -245,19 +218,19 @@ def test_view_stats_batch_refuses_bad_arguments_before_it_allocates():
 def test_the_map_and_gradient_batches_refuse_bad_views_before_they_allocate():
     from gsr_amd import renderer
 
-    R = _rasterizer()
+    R = abi.rasterizer()
     F = torch.zeros((5, 6))
-    for cams, opts in (([], None), ([_cam(), _cam(40, 32)], None), ([_cam()], renderer.make_options(output_layout=1))):
+    for cams, opts in (([], None), ([abi.cam(), abi.cam(40, 32)], None), ([abi.cam()], renderer.make_options(output_layout=1))):
         with pytest.raises(ValueError):
             R.render_features_batch(cams, F, opts)
         with pytest.raises(ValueError):
             R.feature_gradient_batch(cams, torch.zeros((len(cams), 24, 40, 6)), opts)
     with pytest.raises(RuntimeError, match="must live on the GPU"):
-        R.render_features_batch([_cam()], F)  # good views: the features are looked at next (there is no CPU path)
+        R.render_features_batch([abi.cam()], F)  # good views: the features are looked at next (there is no CPU path)
     # groups: `views` cameras at a time, fewer with batch_views or in the last group
-    sizes = lambda opts, b: [len(a) for _, a in R._view_groups([_cam()] * b, opts)]
+    sizes = lambda opts, b: [len(a) for _, a in R._view_groups([abi.cam()] * b, opts)]
     assert sizes(renderer.make_options(), 9) == [4, 4, 1] and sizes(renderer.make_options(batch_views=2), 5) == [2, 2, 1]
-    assert sizes(renderer.make_options(), 3) == [3] and [len(a) for _, a in _rasterizer(views=1)._view_groups([_cam()] * 3, renderer.make_options())] == [1, 1, 1]
+    assert sizes(renderer.make_options(), 3) == [3] and [len(a) for _, a in abi.rasterizer(views=1)._view_groups([abi.cam()] * 3, renderer.make_options())] == [1, 1, 1]
 
 
 def test_accumulate_view_stats_hands_a_rasterizer_with_slices_all_cameras_at_once():

@@ -326,6 +326,36 @@ def _render_checked(rasterizers, streams, opts: GsrOptions, attempt, slack_div: 
     raise type(e)(e.code, f"{what} still incomplete after {MAX_RETRIES} re-renders: {st}")
 
 
+def _check_tensor(name: str, t, shape, dtype=None, device=None, layout: str = "contiguous", note: str = "") -> None:
+    """The one check of a caller's tensor argument: `name` must be a [contiguous] `dtype` tensor of shape `shape` on `device` (the
+    scene's).  shape: per dimension an int, or (lo, hi) for lo <= size <= hi (hi None: no upper limit).  dtype: one, a tuple of
+    them, or None (any: the call converts).  layout: "contiguous"; "rows" — rows (of a batch: frames) contiguous in themselves and
+    at least their own length apart, which libgsr takes with a stride; "any" — the call copies if it has to.  ValueError naming
+    the argument, what was expected and what came."""
+    dtypes = () if dtype is None else dtype if isinstance(dtype, tuple) else (dtype,)
+
+    def refusal(got: str) -> ValueError:  # (worded only when something is refused: the calls are on every frame's path)
+        kind = ("contiguous " if layout == "contiguous" else "") + " or ".join(str(d)[6:] for d in dtypes) + (" " if dtypes else "")
+        dims = ", ".join(str(s) if isinstance(s, int) else f"{s[0]}..{'' if s[1] is None else s[1]}" for s in shape)
+        rows = ", its rows contiguous and at least their length apart" if layout == "rows" else ""
+        return ValueError(f"{name} must be a {kind}tensor of shape [{dims}]{note}{rows}, got {got}")
+
+    if not isinstance(t, torch.Tensor):
+        raise refusal(type(t).__name__)
+    fits = t.dim() == len(shape) and all(z == s if isinstance(s, int) else s[0] <= z and (s[1] is None or z <= s[1])
+                                         for z, s in zip(t.shape, shape))
+    if not fits or (dtypes and t.dtype not in dtypes):
+        raise refusal(f"{t.dtype} {tuple(t.shape)}")
+    if device is not None and t.device != device:
+        raise ValueError(f"{name} must live on the scene's device ({device}), got {t.device}")
+    if layout == "rows" and t.numel():  # (a single row is any distance from the next)
+        laid_out = t.stride(-1) == 1 and t[0].is_contiguous() and (t.shape[0] == 1 or t.stride(0) >= t[0].numel())
+    else:
+        laid_out = layout == "any" or t.is_contiguous()
+    if not laid_out:
+        raise refusal(f"strides {tuple(t.stride())}")
+
+
 def file_order_gradient(buf: torch.Tensor, order_t: Optional[torch.Tensor]) -> torch.Tensor:
     """A per-gaussian gradient in the scene's order -> in the order of the file the scene was loaded from: the transpose of the
     gather `rows = features.index_select(0, order_t)` (row j of the scene is row order_t[j] of the file).  order_t=None: the scene
@@ -343,6 +373,45 @@ def file_order_ids(ids: torch.Tensor, order_t: Optional[torch.Tensor]) -> torch.
         return ids
     file_ids = order_t.to(ids.dtype)[ids.clamp(min=0).long()]
     return torch.where(ids < 0, ids, file_ids)
+
+
+class _PerGaussianOut:
+    """The result side of a call that sums per-gaussian values over a view's pixels.  fields: per buffer (name
+    of the caller's tensor for it, shape behind [n], dtype, wanted).  `out` — the caller's tensors, one per field, in the SCENE's
+    order — is checked first, before any buffer is made; a field that is not wanted is not looked at and stays None.  With `out`
+    the call adds into the caller's tensors and answers with them; else into buffers of its own, which come back in the file's
+    order unless scene_order.  zeroed: nothing else clears own buffers (False: _accumulate_view does, on every attempt)."""
+
+    def __init__(self, scene: "GaussianScene", fields, out, scene_order: bool, zeroed: bool, layout: str = "contiguous"):
+        n, dev = scene.n, scene.device
+        if isinstance(out, torch.Tensor):  # a call with one field takes the tensor itself
+            out = (out,)
+        if out is not None:
+            if len(out) != len(fields):
+                raise ValueError(f"out must hold a tensor (or None) for each of {', '.join(f[0] for f in fields)}, got {len(out)}")
+            for (name, shape, dtype, wanted), t in zip(fields, out):
+                if wanted:
+                    _check_tensor(name, t, (n,) + tuple(shape), dtype, dev, layout)
+            self.bufs = [t if f[3] else None for f, t in zip(fields, out)]
+        else:
+            new = torch.zeros if zeroed else torch.empty
+            self.bufs = [new((n,) + tuple(shape), dtype=dtype, device=dev) if wanted else None for _, shape, dtype, wanted in fields]
+        self.ptrs = [b.data_ptr() if b is not None else None for b in self.bufs]    # None for a field that is not wanted
+        self.own = None if out is not None else [b for b in self.bufs if b is not None]  # what _accumulate_view clears
+        self._order_t = None if out is not None or scene_order else scene.order_t
+
+    def result(self) -> list:
+        """The tensors to return, one per field: the caller's own objects, or this call's in the order that was asked for."""
+        return [None if b is None else file_order_gradient(b, self._order_t) for b in self.bufs]
+
+
+def _wanted(want, names) -> tuple:
+    """`want`, a sequence of names out of `names`, as one flag per name."""
+    if isinstance(want, str) or not all(isinstance(w, str) for w in want):
+        raise ValueError(f"want must be a sequence of names from {names}, got {want!r}")
+    if not len(want) or any(w not in names for w in want):
+        raise ValueError(f"want must name at least one of {names} and nothing else, got {tuple(want)!r}")
+    return tuple(name in want for name in names)
 
 
 class PickMaps(NamedTuple):
@@ -372,6 +441,9 @@ class ViewStats(NamedTuple):
 
 
 VIEW_STATS = ("sum", "max", "pixels")  # the names `want` takes, in ViewStats' field order
+# ... and what view_stats / view_stats_batch add them up in: ViewStats' fields, then the batch's view count (_PerGaussianOut's fields)
+_STATS_FIELDS = (("out.weight_sum", (), torch.float32), ("out.weight_max", (), torch.float32), ("out.pixels", (), torch.int32),
+                 ("out's views", (), torch.int32))
 
 
 class SplatGradient(NamedTuple):
@@ -407,19 +479,14 @@ class GeometryGradient(NamedTuple):
     opacity_logit: Optional[torch.Tensor]
 
 
-def _geometry_buffers(scene: "GaussianScene", out: Optional[GeometryGradient]) -> list:
-    """The four tensors a projection backward adds into: new zeroed ones, or those of `out` once they are what it takes."""
-    dev, n = scene.device, scene.n
-    shapes = ((n, 3), (n, 3), (n, 4), (n,))
-    if out is None:
-        return [torch.zeros(s, dtype=torch.float32, device=dev) for s in shapes]
-    bufs = list(out)
-    if len(bufs) != 4 or all(b is None for b in bufs):
+def _geometry_out(scene: "GaussianScene", out: Optional[GeometryGradient], scene_order: bool) -> _PerGaussianOut:
+    """The four tensors a projection backward adds into: new zeroed ones (no entry clears them), or those of `out` that are not
+    None, once they are what it takes."""
+    if out is not None and (len(out) != 4 or all(b is None for b in out)):
         raise ValueError("out must be a GeometryGradient with at least one tensor")
-    for name, b, s in zip(GeometryGradient._fields, bufs, shapes):
-        if b is not None and (tuple(b.shape) != s or b.dtype != torch.float32 or b.device != dev or not b.is_contiguous()):
-            raise ValueError(f"out.{name} must be a contiguous float32 tensor of shape {list(s)} on the scene's device")
-    return bufs
+    fields = [(f"out.{name}", shape, torch.float32, out is None or out[k] is not None)
+              for k, (name, shape) in enumerate(zip(GeometryGradient._fields, ((3,), (3,), (4,), ())))]
+    return _PerGaussianOut(scene, fields, out, scene_order, zeroed=True)
 
 
 def project_backward(scene: "GaussianScene", cam: GsrCamera, splat_rows: torch.Tensor, opts: Optional[GsrOptions] = None,
@@ -437,22 +504,14 @@ def project_backward(scene: "GaussianScene", cam: GsrCamera, splat_rows: torch.T
     no temporary.  No atomics: two calls give the same bits.
     The scene's arrays are read, never written.  A caller that steps a resident scene's tensors in place must rebuild what was
     derived from them: the block bounds (GaussianScene.build_bounds()), and the Morton order goes stale as the means move."""
-    opts = opts or make_options()
-    dev, n = scene.device, scene.n
     _require_cuda(splat_rows, "splat_rows")
-    if tuple(splat_rows.shape) != (n, 8) or splat_rows.dtype != torch.float32 or splat_rows.device != dev or not splat_rows.is_contiguous():
-        raise ValueError(f"splat_rows must be a contiguous float32 tensor of shape [{n}, 8] on the scene's device")
-    bufs = _geometry_buffers(scene, out)
-    if n:
-        sc = scene.c_struct()
-        with torch.cuda.device(dev):
-            check(lib.gsr_project_backward(C.byref(sc), C.byref(cam), C.byref(opts), splat_rows.data_ptr(),
-                                           *[b.data_ptr() if b is not None else None for b in bufs], _stream_ptr(dev)))
-    if out is not None:
-        return out
-    if scene_order:
-        return GeometryGradient(*bufs)
-    return GeometryGradient(*[file_order_gradient(b, scene.order_t) for b in bufs])
+    _check_tensor("splat_rows", splat_rows, (scene.n, 8), torch.float32, scene.device)
+    res = _geometry_out(scene, out, scene_order)
+    if scene.n:
+        opts, sc = opts or make_options(), scene.c_struct()
+        with torch.cuda.device(scene.device):
+            check(lib.gsr_project_backward(C.byref(sc), C.byref(cam), C.byref(opts), splat_rows.data_ptr(), *res.ptrs, _stream_ptr(scene.device)))
+    return out if out is not None else GeometryGradient(*res.result())
 
 
 TOPK_SELECT = {"heaviest": _lib.GSR_TOPK_HEAVIEST, "nearest": _lib.GSR_TOPK_NEAREST}
@@ -691,8 +750,8 @@ class Rasterizer:
         dtype = torch.bfloat16 if opts.output_dtype == 1 else torch.float32
         if out is None:
             out = self._new(opts, shape, dtype)
-        elif tuple(out.shape) != shape or out.dtype != dtype or not out.is_contiguous() or not out.is_cuda:
-            raise ValueError(f"out must be a contiguous {dtype} CUDA tensor of shape {shape}")
+        else:
+            _check_tensor("out", out, shape, dtype, self.scene.device)
         self._enqueue_view(cam, opts, lib.gsr_render_forward, out, out.data_ptr(), final_T.data_ptr() if final_T is not None else None)
         return out
 
@@ -733,10 +792,7 @@ class Rasterizer:
     # -- feature, depth and alpha maps -----------------------------------------------------------------
     def _check_features(self, features: torch.Tensor, max_channels: Optional[int] = None) -> None:
         _require_cuda(features, "features")
-        if features.dim() != 2 or features.shape[0] != self.scene.n or features.shape[1] < 1 or features.dtype != torch.float32:
-            raise ValueError(f"features must be a float32 tensor of shape [{self.scene.n}, C >= 1], got {features.dtype} {tuple(features.shape)}")
-        if features.device != self.scene.device:
-            raise ValueError("features must live on the scene's device")
+        _check_tensor("features", features, (self.scene.n, (1, None)), torch.float32, self.scene.device, "any")
         if max_channels is not None and features.shape[1] > max_channels:
             raise ValueError(f"at most {max_channels} channels per call, got {features.shape[1]}")
 
@@ -854,24 +910,20 @@ class Rasterizer:
         return _render_checked([self], [None], opts or make_options(), attempt, 8, "feature map")
 
     # -- the gradient of a feature map with respect to the features -------------------------------------------------------------
-    def _gradient_request(self, cam: GsrCamera, opts: GsrOptions, grad_map: torch.Tensor, out: Optional[torch.Tensor],
+    def _gradient_request(self, cam: GsrCamera, opts: GsrOptions, grad_map: torch.Tensor, out, scene_order: bool, in_one_view: bool,
                           name: str = "grad_map", lead=()):
         """feature_gradient's argument checks (feature_gradient_batch's: name="grad_maps", lead=(B,), any of the cameras), before any
-        workspace or buffer is made: (the map, contiguous float32; its channels)."""
-        dev, n, most = self.scene.device, self.scene.n, _lib.GSR_MAX_FEATURE_CHANNELS
+        workspace or buffer is made: (the map, contiguous float32 — None when there is nothing to draw; the [n, C] result, whose
+        own buffer is zeros unless one view's _accumulate_view is going to clear it)."""
         _require_cuda(grad_map, name)
         want = tuple(lead) + tuple(self._out_shape(cam, opts)[0][:2])
-        d = len(want)
-        if grad_map.dim() != d + 1 or tuple(grad_map.shape[:d]) != want or not 1 <= grad_map.shape[d] <= most:
-            raise ValueError(f"{name} must have shape {want} + (1 <= C <= {most},), got {tuple(grad_map.shape)}")
-        if grad_map.device != dev:
-            raise ValueError(f"{name} must live on the scene's device")
-        n_ch = int(grad_map.shape[d])
-        if out is not None:
-            if tuple(out.shape) != (n, n_ch) or out.dtype != torch.float32 or out.device != dev or (
-                    n and (out.stride(1) != 1 or out.stride(0) < n_ch)):
-                raise ValueError(f"out must be a float32 tensor of shape [{n}, {n_ch}] on the scene's device with unit element stride")
-        return grad_map.detach().to(torch.float32).contiguous(), n_ch
+        _check_tensor(name, grad_map, want + ((1, _lib.GSR_MAX_FEATURE_CHANNELS),), None, self.scene.device, "any")
+        # nothing to draw, or a shard that owns no tile row: the gradient is zero.  Here and in view_stats no workspace is made for
+        # that and the shard leaves no mark in `unchecked`, unlike the map calls (_enqueue_view).
+        drawn = self.scene.n != 0 and grad_map.numel() != 0
+        res = _PerGaussianOut(self.scene, [("out", (int(grad_map.shape[-1]),), torch.float32, True)], out, scene_order,
+                              zeroed=not (drawn and in_one_view), layout="rows")
+        return (grad_map.detach().to(torch.float32).contiguous() if drawn else None), res
 
     def feature_gradient(self, cam: GsrCamera, grad_map: torch.Tensor, opts: Optional[GsrOptions] = None,
                          out: Optional[torch.Tensor] = None, scene_order: bool = False) -> torch.Tensor:
@@ -883,16 +935,12 @@ class Rasterizer:
         temporary.  Stages 1-2 are re-run on every call and checked like any frame; float atomic sums may differ in the last bits
         between two calls."""
         opts = opts or make_options()
-        dev, n = self.scene.device, self.scene.n
-        gm, n_ch = self._gradient_request(cam, opts, grad_map, out)
-        # nothing to draw, or a shard that owns no tile row: the gradient is zero.  Here and in view_stats no workspace is made for
-        # that and the shard leaves no mark in `unchecked`, unlike the map calls (_enqueue_view).
-        if n == 0 or gm.numel() == 0:
-            return out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
-        buf = out if out is not None else torch.empty((n, n_ch), dtype=torch.float32, device=dev)
-        self._accumulate_view(cam, opts, "feature gradient", None if out is not None else [buf], lib.gsr_render_channels_backward,
-                              lib.gsr_blend_channels_backward, gm.data_ptr(), n_ch, buf.data_ptr(), int(buf.stride(0)))
-        return buf if out is not None or scene_order else file_order_gradient(buf, self.scene.order_t)
+        gm, res = self._gradient_request(cam, opts, grad_map, out, scene_order, True)
+        if gm is not None:
+            buf = res.bufs[0]
+            self._accumulate_view(cam, opts, "feature gradient", res.own, lib.gsr_render_channels_backward,
+                                  lib.gsr_blend_channels_backward, gm.data_ptr(), int(buf.shape[1]), buf.data_ptr(), int(buf.stride(0)))
+        return res.result()[0]
 
     # -- the gradient of a feature map with respect to opacity and the 2-D splat ----------------------------------------------------
     def splat_gradient(self, cam: GsrCamera, features: torch.Tensor, grad_map: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
@@ -916,37 +964,29 @@ class Rasterizer:
         SplatGradient returned holds views of it, in the scene's order: stages 1-2 are checked and re-run first and only then does
         the blend add.  Float atomic sums may differ in the last bits between two calls."""
         opts = opts or make_options()
-        dev, n = self.scene.device, self.scene.n
+        dev = self.scene.device
         self._check_features(features, _lib.GSR_MAX_FEATURE_CHANNELS)
         n_ch = int(features.shape[1])
         _require_cuda(grad_map, "grad_map")
         shape, tshape = self._out_shape(cam, opts)
-        if tuple(grad_map.shape) != tuple(shape[:2]) + (n_ch,) or grad_map.device != dev:
-            raise ValueError(f"grad_map must have shape {tuple(shape[:2]) + (n_ch,)} on the scene's device, got {tuple(grad_map.shape)}")
-        if grad_T is not None and (not isinstance(grad_T, torch.Tensor) or tuple(grad_T.shape) != tuple(tshape) or grad_T.device != dev):
-            raise ValueError(f"grad_T must be a tensor of shape {tuple(tshape)} (the layout of the final T) on the scene's device")
+        _check_tensor("grad_map", grad_map, tuple(shape[:2]) + (n_ch,), None, dev, "any")
+        if grad_T is not None:
+            _check_tensor("grad_T", grad_T, tshape, None, dev, "any", " (the layout of the final T)")
         if not (float(min_T) >= 0.0 and float(min_T) < float("inf")):
             raise ValueError(f"min_T must be finite and >= 0, got {min_T}")
         if abs_mean and n_ch > 16:
             raise ValueError(f"abs_mean takes at most 16 channels (the absolute sums are not linear in them), got {n_ch}")
-        if out is not None and (tuple(out.shape) != (n, 8) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous float32 tensor of shape [{n}, 8] on the scene's device")
-        gm = grad_map.detach().to(torch.float32).contiguous()
-        gt = grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None
-
-        def result(buf, in_scene_order):
-            g = buf if in_scene_order else file_order_gradient(buf, self.scene.order_t)
-            return SplatGradient(g[:, 1:3], g[:, 3:6], g[:, 0], g[:, 6:8] if abs_mean else None)
-
-        if n == 0 or gm.numel() == 0:  # nothing to draw, or a shard that owns no tile row
-            return result(out if out is not None else torch.zeros((n, 8), dtype=torch.float32, device=dev), out is not None or scene_order)
-        rows = self._feature_rows(features.detach(), scene_order)
-        tail = (rows.data_ptr(), int(rows.stride(0)), n_ch, gm.data_ptr(), gt.data_ptr() if gt is not None else None, float(min_T),
-                int(bool(abs_mean)))
-        buf = out if out is not None else torch.empty((n, 8), dtype=torch.float32, device=dev)
-        self._accumulate_view(cam, opts, "splat gradient", None if out is not None else [buf], lib.gsr_render_splat_backward,
-                              lib.gsr_blend_splat_backward, *tail, buf.data_ptr())
-        return result(buf, out is not None or scene_order)
+        drawn = self.scene.n != 0 and grad_map.numel() != 0  # else nothing to draw, or a shard that owns no tile row
+        res = _PerGaussianOut(self.scene, [("out", (8,), torch.float32, True)], out, scene_order, zeroed=not drawn)
+        if drawn:
+            gm = grad_map.detach().to(torch.float32).contiguous()
+            gt = grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None
+            rows = self._feature_rows(features.detach(), scene_order)
+            self._accumulate_view(cam, opts, "splat gradient", res.own, lib.gsr_render_splat_backward, lib.gsr_blend_splat_backward,
+                                  rows.data_ptr(), int(rows.stride(0)), n_ch, gm.data_ptr(), gt.data_ptr() if gt is not None else None,
+                                  float(min_T), int(bool(abs_mean)), *res.ptrs)
+        g = res.result()[0]
+        return SplatGradient(g[:, 1:3], g[:, 3:6], g[:, 0], g[:, 6:8] if abs_mean else None)
 
     # -- the gradient of a feature map with respect to the scene's geometry ---------------------------------------------------------
     def geometry_gradient(self, cam: GsrCamera, features: torch.Tensor, grad_map: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
@@ -962,7 +1002,7 @@ class Rasterizer:
         last bits between two calls; the projection adds nothing to that."""
         n, dev = self.scene.n, self.scene.device
         if out is not None:
-            _geometry_buffers(self.scene, out)  # refused before the splat gradient runs, not after
+            _geometry_out(self.scene, out, scene_order)  # refused before the splat gradient runs, not after
         if self._splat_rows is None or tuple(self._splat_rows.shape) != (n, 8):
             self._splat_rows = torch.empty((n, 8), dtype=torch.float32, device=dev)
         rows = self._splat_rows.zero_()
@@ -974,44 +1014,24 @@ class Rasterizer:
         one-channel map of ones; the importance score pruning works with.  Returned in the file's order; with `out` ([n] float32,
         contiguous, in the SCENE's order) the weights are accumulated into it, e.g. over a camera set."""
         opts = opts or make_options()
+        if out is not None:
+            _check_tensor("out", out, (self.scene.n,), torch.float32, self.scene.device)
         shape, _ = self._out_shape(cam, opts)
         ones = torch.ones(shape[:2] + (1,), dtype=torch.float32, device=self.scene.device)
         if out is not None:
-            if out.dim() != 1 or not out.is_contiguous():
-                raise ValueError("out must be a contiguous [n] tensor")
             self.feature_gradient(cam, ones, opts, out=out.unsqueeze(1))
             return out
         return self.feature_gradient(cam, ones, opts).squeeze(1)
 
     # -- per-gaussian statistics of a view ---------------------------------------------------------------------------------------
-    def _stats_request(self, cam: GsrCamera, opts: GsrOptions, mask, out, want):
-        """view_stats' argument checks, before any workspace or buffer is made: (wanted flags, mask as gsr_render_gaussian_stats
-        reads it or None)."""
-        if isinstance(want, str) or not all(isinstance(w, str) for w in want):
-            raise ValueError(f"want must be a sequence of names from {VIEW_STATS}, got {want!r}")
-        bad = [w for w in want if w not in VIEW_STATS]
-        if bad or not len(want):
-            raise ValueError(f"want must name at least one of {VIEW_STATS} and nothing else, got {tuple(want)!r}")
-        flags = tuple(name in want for name in VIEW_STATS)
-        dev, n = self.scene.device, self.scene.n
-        tshape = tuple(self._out_shape(cam, opts)[1])
-        if mask is not None:
-            if not isinstance(mask, torch.Tensor) or mask.dtype not in (torch.bool, torch.uint8) or tuple(mask.shape) != tshape:
-                got = f"{mask.dtype} {tuple(mask.shape)}" if isinstance(mask, torch.Tensor) else type(mask).__name__
-                raise ValueError(f"mask must be a bool or uint8 tensor of shape {tshape} (the layout of the final T), got {got}")
-            if mask.device != dev:
-                raise ValueError(f"mask must live on the scene's device ({dev}), got {mask.device}")
-            mask = mask.detach().contiguous()
-            mask = mask.view(torch.uint8) if mask.dtype == torch.bool else mask  # one byte per pixel, non-zero = counted
-        if out is not None:
-            if not isinstance(out, tuple) or len(out) != 3:
-                raise ValueError("out must be a ViewStats (weight_sum, weight_max, pixels)")
-            for name, wanted, t, dtype in zip(VIEW_STATS, flags, out, (torch.float32, torch.float32, torch.int32)):
-                if not wanted:
-                    continue
-                if not isinstance(t, torch.Tensor) or tuple(t.shape) != (n,) or t.dtype != dtype or t.device != dev or not t.is_contiguous():
-                    raise ValueError(f"out's {name!r} field must be a contiguous {dtype} tensor of shape [{n}] on the scene's device")
-        return flags, mask
+    def _count_mask(self, cam: GsrCamera, opts: GsrOptions, mask) -> Optional[torch.Tensor]:
+        """A mask of view_stats as gsr_render_gaussian_stats reads it (None stays None): one byte per pixel, non-zero = counted."""
+        if mask is None:
+            return None
+        _check_tensor("mask", mask, self._out_shape(cam, opts)[1], (torch.bool, torch.uint8), self.scene.device, "any",
+                      " (the layout of the final T)")
+        mask = mask.detach().contiguous()
+        return mask.view(torch.uint8) if mask.dtype == torch.bool else mask
 
     def view_stats(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, mask: Optional[torch.Tensor] = None,
                    out: Optional[ViewStats] = None, scene_order: bool = False, want=VIEW_STATS) -> ViewStats:
@@ -1029,24 +1049,14 @@ class Rasterizer:
         are returned: stages 1-2 are checked and re-run first and only then does the blend add, so that an incomplete walk never
         reaches `out`.  Checked and re-rendered on overflow like render(); sets last_stats."""
         opts = opts or make_options()
-        flags, mask = self._stats_request(cam, opts, mask, out, want)
-        dev, n = self.scene.device, self.scene.n
-        dtypes = (torch.float32, torch.float32, torch.int32)
-        given = out is not None
-        bufs = [((out[k] if given else torch.zeros(n, dtype=dtypes[k], device=dev)) if flags[k] else None) for k in range(3)]
-        mptr = mask.data_ptr() if mask is not None else None
-
-        def result():
-            if given or scene_order:
-                return ViewStats(*bufs)
-            return ViewStats(*[None if b is None else file_order_gradient(b, self.scene.order_t) for b in bufs])
-
-        if n == 0 or 0 in self._out_shape(cam, opts)[1]:  # nothing to draw, or a shard that owns no tile row
-            return result()
-        ptrs = [mptr] + [b.data_ptr() if b is not None else None for b in bufs]
-        self._accumulate_view(cam, opts, "view statistics", None if given else [b for b in bufs if b is not None],
-                              lib.gsr_render_gaussian_stats, lib.gsr_blend_gaussian_stats, *ptrs)
-        return result()
+        flags = _wanted(want, VIEW_STATS)
+        mask = self._count_mask(cam, opts, mask)
+        drawn = self.scene.n != 0 and 0 not in self._out_shape(cam, opts)[1]  # else nothing to draw, or a shard that owns no tile row
+        res = _PerGaussianOut(self.scene, [f + (w,) for f, w in zip(_STATS_FIELDS, flags)], out, scene_order, zeroed=not drawn)
+        if drawn:
+            self._accumulate_view(cam, opts, "view statistics", res.own, lib.gsr_render_gaussian_stats, lib.gsr_blend_gaussian_stats,
+                                  mask.data_ptr() if mask is not None else None, *res.ptrs)
+        return ViewStats(*res.result())
 
     def visible_ids(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int64 ids, ascending, in the order of the file the scene was loaded from, of the gaussians that reach at least one counted
@@ -1079,11 +1089,7 @@ class Rasterizer:
         """A limit plane of render_slab as gsr_render_slab reads it (None stays None): float32 `shape` on the scene's device."""
         if plane is None:
             return None
-        if not isinstance(plane, torch.Tensor) or plane.dtype != torch.float32 or tuple(plane.shape) != tuple(shape):
-            got = f"{plane.dtype} {tuple(plane.shape)}" if isinstance(plane, torch.Tensor) else type(plane).__name__
-            raise ValueError(f"{name} must be a float32 tensor of shape {tuple(shape)} (the layout of the final T), got {got}")
-        if plane.device != self.scene.device:
-            raise ValueError(f"{name} must live on the scene's device ({self.scene.device}), got {plane.device}")
+        _check_tensor(name, plane, shape, torch.float32, self.scene.device, "any", " (the layout of the final T)")
         return plane.detach().contiguous()
 
     def render_slab(self, cam: GsrCamera, features: torch.Tensor, near: Optional[torch.Tensor] = None, far: Optional[torch.Tensor] = None,
@@ -1310,41 +1316,14 @@ class Rasterizer:
         Float atomic sums may differ in the last bits between two calls."""
         opts = opts or make_options()
         cams = self._view_list(cams, opts)
-        dev, n = self.scene.device, self.scene.n
-        gm, n_ch = self._gradient_request(cams[0], opts, grad_maps, out, "grad_maps", (len(cams),))
-        if n == 0 or gm.numel() == 0:  # nothing to draw, or a shard that owns no tile row: no workspace (feature_gradient's rule)
-            return out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
-        buf = out if out is not None else torch.zeros((n, n_ch), dtype=torch.float32, device=dev)
-        for i, arr in self._view_groups(cams, opts):
-            o = self._checked_lists_views(arr, opts, "feature gradient batch")
-            self._blend_lists_views(arr, o, lib.gsr_blend_channels_backward_views, gm[i].data_ptr(), gm[0].numel(), n_ch, buf.data_ptr(),
-                                    int(buf.stride(0)))
-        if out is not None or scene_order:
-            return buf
-        return file_order_gradient(buf, self.scene.order_t)
-
-    def _stats_batch_request(self, cams, opts: GsrOptions, masks, out, want):
-        """view_stats_batch's argument checks, before any workspace or buffer is made: (wanted flags of VIEW_STATS_BATCH, the masks as
-        they came with each checked and made one byte per pixel — or None when no camera has one)."""
-        if isinstance(want, str) or not all(isinstance(w, str) for w in want):
-            raise ValueError(f"want must be a sequence of names from {VIEW_STATS_BATCH}, got {want!r}")
-        if not len(want) or any(w not in VIEW_STATS_BATCH for w in want):
-            raise ValueError(f"want must name at least one of {VIEW_STATS_BATCH} and nothing else, got {tuple(want)!r}")
-        flags = tuple(name in want for name in VIEW_STATS_BATCH)
-        masks = [None] * len(cams) if masks is None else list(masks)
-        if len(masks) != len(cams):
-            raise ValueError(f"masks must hold one entry per camera: {len(masks)} for {len(cams)} cameras")
-        masks = [self._stats_request(cams[0], opts, m, None, VIEW_STATS)[1] for m in masks]  # (None stays None)
-        if out is not None:
-            if not isinstance(out, tuple) or len(out) != 2 or not isinstance(out[0], tuple):
-                raise ValueError("out must be (ViewStats, views), as view_stats_batch returns them")
-            if any(flags[:3]):
-                self._stats_request(cams[0], opts, None, out[0], [w for w in VIEW_STATS if w in want])
-            v, n = out[1], self.scene.n
-            if flags[3] and (not isinstance(v, torch.Tensor) or tuple(v.shape) != (n,) or v.dtype != torch.int32
-                             or v.device != self.scene.device or not v.is_contiguous()):
-                raise ValueError(f"out's views must be a contiguous {torch.int32} tensor of shape [{n}] on the scene's device")
-        return flags, (masks if any(m is not None for m in masks) else None)
+        gm, res = self._gradient_request(cams[0], opts, grad_maps, out, scene_order, False, "grad_maps", (len(cams),))
+        if gm is not None:  # (else no workspace: feature_gradient's rule)
+            buf = res.bufs[0]
+            for i, arr in self._view_groups(cams, opts):
+                o = self._checked_lists_views(arr, opts, "feature gradient batch")
+                self._blend_lists_views(arr, o, lib.gsr_blend_channels_backward_views, gm[i].data_ptr(), gm[0].numel(), int(buf.shape[1]),
+                                        buf.data_ptr(), int(buf.stride(0)))
+        return res.result()[0]
 
     def view_stats_batch(self, cams, opts: Optional[GsrOptions] = None, masks=None, out=None, scene_order: bool = False,
                          want=VIEW_STATS_BATCH):
@@ -1359,36 +1338,32 @@ class Rasterizer:
         every slice is complete, and only then the blend that adds.  Sets last_stats."""
         opts = opts or make_options()
         cams = self._view_list(cams, opts)
-        flags, masks = self._stats_batch_request(cams, opts, masks, out, want)
+        flags = _wanted(want, VIEW_STATS_BATCH)
+        masks = [None] * len(cams) if masks is None else list(masks)
+        if len(masks) != len(cams):
+            raise ValueError(f"masks must hold one entry per camera: {len(masks)} for {len(cams)} cameras")
+        masks = [self._count_mask(cams[0], opts, m) for m in masks]
+        if out is not None:
+            if not isinstance(out, tuple) or len(out) != 2 or not isinstance(out[0], tuple):
+                raise ValueError("out must be (ViewStats, views), as view_stats_batch returns them")
+            out = tuple(out[0]) + (out[1],)
         dev, n = self.scene.device, self.scene.n
-        dtypes = (torch.float32, torch.float32, torch.int32, torch.int32)
-        given = out is not None
-        have = (tuple(out[0]) + (out[1],)) if given else (None,) * 4
-        bufs = [((have[k] if given else torch.zeros(n, dtype=dtypes[k], device=dev)) if flags[k] else None) for k in range(4)]
-
-        def result():
-            if given or scene_order:
-                return ViewStats(*bufs[:3]), bufs[3]
-            back = [None if b is None else file_order_gradient(b, self.scene.order_t) for b in bufs]
-            return ViewStats(*back[:3]), back[3]
-
         tshape = tuple(self._out_shape(cams[0], opts)[1])
-        if n == 0 or 0 in tshape:  # nothing to draw, or a shard that owns no tile row: no workspace (view_stats' rule)
-            return result()
-        stacked = None
-        if masks is not None:
-            stacked = torch.ones((len(cams),) + tshape, dtype=torch.uint8, device=dev)
-            for j, m in enumerate(masks):
-                if m is not None:
-                    stacked[j] = m
-        bits = torch.empty(n, dtype=torch.int32, device=dev) if flags[3] else None  # libgsr's scratch: cleared by every call
-        ptrs = [b.data_ptr() if b is not None else None for b in bufs] + [bits.data_ptr() if bits is not None else None]
-        plane = tshape[0] * tshape[1]
-        for i, arr in self._view_groups(cams, opts):
-            o = self._checked_lists_views(arr, opts, "view statistics batch")
-            self._blend_lists_views(arr, o, lib.gsr_blend_gaussian_stats_views, stacked[i].data_ptr() if stacked is not None else None,
-                                    plane, *ptrs)
-        return result()
+        res = _PerGaussianOut(self.scene, [f + (w,) for f, w in zip(_STATS_FIELDS, flags)], out, scene_order, zeroed=True)
+        if n != 0 and 0 not in tshape:  # else nothing to draw, or a shard that owns no tile row: no workspace (view_stats' rule)
+            stacked = None
+            if any(m is not None for m in masks):
+                stacked = torch.ones((len(cams),) + tshape, dtype=torch.uint8, device=dev)
+                for j, m in enumerate(masks):
+                    if m is not None:
+                        stacked[j] = m
+            bits = torch.empty(n, dtype=torch.int32, device=dev) if flags[3] else None  # libgsr's scratch: cleared by every call
+            for i, arr in self._view_groups(cams, opts):
+                o = self._checked_lists_views(arr, opts, "view statistics batch")
+                self._blend_lists_views(arr, o, lib.gsr_blend_gaussian_stats_views, stacked[i].data_ptr() if stacked is not None else None,
+                                        tshape[0] * tshape[1], *res.ptrs, bits.data_ptr() if bits is not None else None)
+        back = res.result()
+        return ViewStats(*back[:3]), back[3]
 
     def _batch_out(self, cams, opts: GsrOptions, out: Optional[torch.Tensor]):
         """(out, frame_stride in elements) of a batch: whole frames [B,H,W,3], or with a tile-row shard (output_layout = 2) the
@@ -1401,10 +1376,8 @@ class Rasterizer:
         frame = shape[0] * shape[1] * shape[2]
         if out is None:
             out = self._new(opts, full, dtype)
-        elif (tuple(out.shape) != full or out.dtype != dtype or not out.is_cuda or (frame and not out[0].is_contiguous())
-              or (len(cams) > 1 and out.stride(0) < frame)):
-            # (consecutive frames may lie further apart than a frame: the strips of a padded wire buffer, dist.FrameGather)
-            raise ValueError(f"out must be a {dtype} CUDA tensor of shape {full} whose frames are contiguous")
+        else:  # (consecutive frames may lie further apart than a frame: the strips of a padded wire buffer, dist.FrameGather)
+            _check_tensor("out", out, full, dtype, self.scene.device, "rows")
         return out, (out.stride(0) if len(cams) > 1 and frame else frame)
 
     def enqueue_batch(self, cams, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1462,12 +1435,8 @@ class Rasterizer:
         sc = self.scene.c_struct()
         check(lib.gsr_preprocess(C.byref(sc), C.byref(cam), C.byref(opts), ws.data_ptr(), ws.numel(), C.byref(dbg),
                                  _stream_ptr(dev)))
-        if self.scene.order_t is not None:  # the library works in scene order; callers (and the reference's helpers) index by file order
-            for k, v in out.items():
-                back = torch.empty_like(v)
-                back[self.scene.order_t] = v
-                out[k] = back
-        return out
+        # the library works in scene order; callers (and the reference's helpers) index by file order
+        return {k: file_order_gradient(v, self.scene.order_t) for k, v in out.items()}
 
 
 def accumulate_view_stats(R: "Rasterizer", cams, opts: Optional[GsrOptions] = None, masks=None):
@@ -1571,8 +1540,8 @@ class FramesInFlight:
         dtype = torch.bfloat16 if opts.output_dtype == 1 else torch.float32
         if out is None:
             out = torch.empty((len(cams), H, W, 3), dtype=dtype, device=dev)
-        elif tuple(out.shape) != (len(cams), H, W, 3) or out.dtype != dtype or not out.is_contiguous() or not out.is_cuda:
-            raise ValueError(f"out must be a contiguous {dtype} CUDA tensor of shape {(len(cams), H, W, 3)}")
+        else:
+            _check_tensor("out", out, (len(cams), H, W, 3), dtype, dev)
         sc = self.scene.c_struct()
         n = len(self.rasterizers)
         cur = torch.cuda.current_stream(dev)
