@@ -37,7 +37,8 @@ extern "C" {
                             statistics for several views per launch sequence, with view_hits, the exact number of views that reach a gaussian; gsr_blend_splat_backward /
                             gsr_render_splat_backward — the gradient of a feature map and of the final T with respect to the 2-D splat: opacity, 2-D mean, inverse 2-D covariance, and the
                             per-pixel absolute mean gradients; gsr_project_backward — that gradient chained through the projection to the scene's means, log-scales,
-                            quaternions and opacity logits): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            quaternions and opacity logits; gsr_sh_backward — the transpose of gsr_sh_to_rgb: a view's colour gradient carried to the SH coefficients
+                            and, through the view direction, to the means): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -404,7 +405,8 @@ int gsr_render_splat_backward(const GsrScene *scene, const GsrCamera *cam, const
  *   opacity <- logit       sigmoid(x) sigmoid(-x), which keeps its digits where 1 - sigmoid(x) has lost them.
  * Clamp rule: where the ray clamp is active the derivative in x / z is 0, and t_x = +-lim_x z still depends on z (likewise y).
  * Held fixed: the tile rect, the footprint, the 1/255 threshold and the cull — the support gsr_blend_splat_backward already holds
- * fixed.  No colour term: nothing flows through the SH evaluation (the view direction's part of d / d mean is not included).
+ * fixed.  No colour term HERE: nothing flows through the SH evaluation; the view direction's part of d / d mean is what
+ * gsr_sh_backward adds into the same grad_means.
  * Skip rule: a gaussian whose six values are all zero is not touched — its rows of the outputs are neither read nor written, and
  * a wave of 64 consecutive such gaussians reads nothing but their rows of grad_splat.  A gaussian contributes nothing either when
  * the forward culls it (z_cam < GSR_CULL_Z), when its det is 0, when a conic entry is not finite, or, with reference_compat,
@@ -421,6 +423,35 @@ int gsr_project_backward(const GsrScene *scene, const GsrCamera *cam, const GsrO
                          const float *grad_splat /* [n][8], columns 0-5 read */,
                          float *grad_means /* [n,3] ADDS, may be NULL */, float *grad_log_scales /* [n,3] */,
                          float *grad_quats /* [n,4] */, float *grad_opacity_logit /* [n] */, void *stream);
+
+/* The SH colour backward: the exact transpose of gsr_sh_to_rgb at scene->sh_degree and cam->cam_center.  Row i of grad_rgb
+ * (d L / d colour of gaussian i; columns 0-2 of rows grad_rgb_stride floats apart are read, so a column window of a wider array is
+ * read where it lies) is carried to the gaussian's SH coefficients and, through the view direction, to its mean.  No cull: the
+ * operator has none because gsr_sh_to_rgb has none.  Per gaussian, with d = mean - cam_center, r = |d|, u = d / r and
+ * v_c = sum_k b_k(u) sh[k][c] + 0.5 the value before the clamp:
+ *   Clamp mask   m_c = 1 where 0 <= v_c <= 1, else 0: the edges pass, as the forward's v < 0 ? 0 : (v > 1 ? 1 : v) passes them.
+ *                v_c is recomputed by the forward's own function on the same fp32 values: the decision is the forward's, bit for bit.
+ *   grad_sh      [n,16,3] float32: grad_sh[i][k][c] += b_k(u) m_c g_c for k < (degree + 1)^2; coefficients k >= (degree + 1)^2 are
+ *                neither read nor written.  With sh_dtype = 1 (fp16 storage) it is the gradient in the widened values, still float32.
+ *   grad_means   [n,3]: grad_means[i] += (I - u u^T) / r  sum_k grad_u b_k(u) (sum_c m_c g_c sh[k][c]).  Zero at degree 0: it is
+ *                then neither computed nor written.
+ *   r == 0       (a mean on the camera centre) makes the forward NaN above degree 0; the gaussian then contributes nothing.
+ * Both outputs are ADDED into; either may be NULL (not both), and the other is bit for bit what it is in a call with both.  One
+ * thread per gaussian, no atomics: two calls with the same input give the same bits, and adding a row twice doubles it exactly.
+ * Skip rule: a gaussian whose three values are all zero is not touched — its rows of the outputs, its mean and its SH row are
+ * neither read nor written — and a wave of 64 consecutive such gaussians reads nothing but their 12 B of grad_rgb each; a gaussian
+ * all of whose channels with a nonzero value are clamped writes nothing either.
+ * Needs no workspace, no lists and no options; the scene's arrays are read, never written.
+ *   - grad_rgb must be finite where it is not zero.
+ *   - No output may alias grad_rgb (refused), the other output or an array of the scene (not checked: the caller's to keep);
+ *     grad_sh must be 16-byte aligned.
+ * GSR_ERR_BAD_ARG, before any HIP call, for a null scene, camera or grad_rgb, both outputs NULL, grad_rgb_stride < 3, an output that
+ * aliases grad_rgb, a misaligned grad_sh, a scene gsr_preprocess refuses (sh_dtype, sh_degree).  n = 0 is GSR_OK.  Single views: sum
+ * over cameras by calling it once per view into the same outputs. */
+int gsr_sh_backward(const GsrScene *scene, const GsrCamera *cam,
+                    const float *grad_rgb /* [n] rows, columns 0-2 read */, int64_t grad_rgb_stride /* floats, >= 3 */,
+                    float *grad_sh /* [n,16,3] fp32, ADDS, may be NULL */, float *grad_means /* [n,3] ADDS, may be NULL */,
+                    void *stream);
 
 /* Stage 3 for what no blended channel can hold — per pixel p, over the same depth-ordered lists and with the same weights
  * w_i = alpha_i T_i (and the same T, bit for bit) as gsr_blend_features (no reference counterpart):

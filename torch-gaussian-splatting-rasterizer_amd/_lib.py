@@ -138,7 +138,7 @@ EXPORTS = [
     "gsr_lists_views", "gsr_blend_channels_views", "gsr_blend_channels_backward_views", "gsr_blend_gaussian_stats_views",
     "gsr_render_channels_batch",
     "gsr_blend_splat_backward", "gsr_render_splat_backward",
-    "gsr_project_backward",
+    "gsr_project_backward", "gsr_sh_backward",
 ]
 
 
@@ -178,6 +178,8 @@ def _load() -> C.CDLL:
     L.gsr_render_splat_backward.argtypes = view + splat
     # scene, camera, options, grad_splat [n][8], grad_means, grad_log_scales, grad_quats, grad_opacity_logit (each may be NULL), stream
     L.gsr_project_backward.argtypes = [scene_p, cam_p, opts_p, vp, vp, vp, vp, vp, vp]
+    # scene, camera, grad_rgb rows, their stride in floats, grad_sh [n][16][3], grad_means [n][3] (either may be NULL), stream
+    L.gsr_sh_backward.argtypes = [scene_p, cam_p, vp, i64, vp, vp, vp]
     L.gsr_render_batch.argtypes = [scene_p, cam_p, i32, opts_p, i64, vp, sz, vp, i64, vp]
     views = [cam_p, i32, opts_p, i64, vp, sz]        # gsr_*_views: cameras [host], how many, options, max_pairs, workspace, its bytes
     L.gsr_lists_views.argtypes = [scene_p] + views + [vp]

@@ -874,6 +874,31 @@ int gsr_project_backward(const GsrScene *scene, const GsrCamera *cam, const GsrO
                                    static_cast<hipStream_t>(stream));
 }
 
+// The colour gradient of a view chained to the scene's SH coefficients and means: no workspace, no lists, no options
+int gsr_sh_backward(const GsrScene *scene, const GsrCamera *cam, const float *grad_rgb, int64_t grad_rgb_stride, float *grad_sh,
+                    float *grad_means, void *stream)
+{
+    if (!scene) { set_error("null scene"); return GSR_ERR_BAD_ARG; }
+    if (!cam) { set_error("null camera"); return GSR_ERR_BAD_ARG; }
+    if (!grad_rgb) { set_error("null colour gradient"); return GSR_ERR_BAD_ARG; }
+    if (!grad_sh && !grad_means) { set_error("null outputs: both grad_sh and grad_means"); return GSR_ERR_BAD_ARG; }
+    if (grad_rgb_stride < 3) { set_error("bad grad_rgb_stride %lld: rows of 3 channels overlap", (long long)grad_rgb_stride); return GSR_ERR_BAD_ARG; }
+    const size_t rows = scene->n > 0 ? (size_t)scene->n : 0;
+    const uintptr_t gr = reinterpret_cast<uintptr_t>(grad_rgb);
+    const size_t gr_bytes = rows ? 4 * ((rows - 1) * (size_t)grad_rgb_stride + 3) : 0;
+    const struct { const float *p; size_t floats; const char *name; } outs[2] = {{grad_sh, 48, "grad_sh"}, {grad_means, 3, "grad_means"}};
+    for (const auto &o : outs) {
+        const uintptr_t b = reinterpret_cast<uintptr_t>(o.p);
+        if (b && (b == gr || (b < gr + gr_bytes && gr < b + 4 * o.floats * rows))) {
+            set_error("%s aliases grad_rgb", o.name); return GSR_ERR_BAD_ARG;
+        }
+    }
+    if (reinterpret_cast<uintptr_t>(grad_sh) % 16 != 0) { set_error("grad_sh must be 16-byte aligned"); return GSR_ERR_BAD_ARG; }
+    const int rc = check_scene(scene);
+    if (rc) return rc;
+    return launch_sh_backward(*scene, *cam, grad_rgb, grad_rgb_stride, grad_sh, grad_means, static_cast<hipStream_t>(stream));
+}
+
 int gsr_blend_gaussian_stats(int64_t n, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs, void *workspace,
                              size_t workspace_bytes, const uint8_t *pixel_mask, float *weight_sum, float *weight_max, uint32_t *pixels,
                              void *stream)

@@ -40,7 +40,9 @@ __device__ __forceinline__ void cov3d_of(const float ls[3], const float4 q, floa
 // colours inside a 64-VGPR kernel); per channel the operations and their association are the reference's:
 //   col = sh0 c0;  col += ((-c1 y) sh1 + (c1 z) sh2) - (c1 x) sh3;  col += (((t4 + t5) + t6) + t7) + t8;  col += ((...(t9 + t10) ... ) + t15)
 // with t_k = basis_k sh_k, basis_k written exactly as spherical_harmonics.py:45-65 writes it; + 0.5, clamp to [0, 1] (:69-71, Q7).
-template <typename Get>
+// CLAMP = false leaves the value BEFORE the clamp in rgb: what the colour backward (sh_backward.hip) decides its clamp mask on, so
+// that the decision is the forward's own.
+template <bool CLAMP = true, typename Get>
 __device__ __forceinline__ void sh_eval_with(const float p[3], Get get, const float cc[3], int degree, float rgb[3])
 {
 #pragma clang fp contract(off)  // also where the including file is built with contraction on (blend.hip evaluates deferred colours)
@@ -104,7 +106,7 @@ __device__ __forceinline__ void sh_eval_with(const float p[3], Get get, const fl
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float v = col[c] + 0.5f;                        // :69
-        rgb[c] = v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);     // :71 (Q7)
+        rgb[c] = !CLAMP ? v : v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v);  // :71 (Q7)
     }
 }
 

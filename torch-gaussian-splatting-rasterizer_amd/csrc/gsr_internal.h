@@ -294,6 +294,10 @@ int launch_blend_splat_backward(const GsrCamera &cam, const GsrOptions &opts, co
 // log-scales, quaternion and opacity logit, ADDED into the four arrays that are not null; no workspace, no lists
 int launch_project_backward(const GsrScene &scene, const GsrCamera &cam, const GsrOptions &opts, const float *grad_splat, float *grad_means,
                             float *grad_log_scales, float *grad_quats, float *grad_opacity_logit, hipStream_t s);
+// The transpose of sh_to_rgb (sh_backward.hip): row i of grad_rgb (columns 0-2, rows grad_stride floats apart) carried to gaussian
+// i's SH coefficients and, through the view direction, to its mean; ADDED into the two arrays that are not null; no workspace
+int launch_sh_backward(const GsrScene &scene, const GsrCamera &cam, const float *grad_rgb, int64_t grad_stride, float *grad_sh,
+                       float *grad_means, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

@@ -497,7 +497,8 @@ def project_backward(scene: "GaussianScene", cam: GsrCamera, splat_rows: torch.T
     -) as splat_gradient(out=) fills them; columns 6 and 7 are ignored.  A row of six zeros is skipped: the gaussian's gradients are
     not touched.  Gaussians the view culls (z_cam < 0.2), or whose 2-D covariance is singular, contribute nothing whatever their row
     holds.  Held fixed: the tile rect, the footprint, the 1/255 threshold and the cull; where the ray clamp is active the derivative
-    in x / z is 0.  No colour term (the SH view direction's part of d / d mean is not included).
+    in x / z is 0.  No colour term in this call: the SH view direction's part of d / d mean is sh_backward's, which adds it into the
+    same `means` (Rasterizer.colour_gradient runs both).
     Returns a GeometryGradient in the order of the file the scene was loaded from (scene_order=True: of the scene's resident
     arrays).  With `out` — a GeometryGradient of float32 contiguous tensors on the scene's device, in the SCENE's order; a field that
     is None is not computed — the gradient is ACCUMULATED into its tensors and `out` is returned: summing over a camera set needs
@@ -512,6 +513,66 @@ def project_backward(scene: "GaussianScene", cam: GsrCamera, splat_rows: torch.T
         with torch.cuda.device(scene.device):
             check(lib.gsr_project_backward(C.byref(sc), C.byref(cam), C.byref(opts), splat_rows.data_ptr(), *res.ptrs, _stream_ptr(scene.device)))
     return out if out is not None else GeometryGradient(*res.result())
+
+
+class ColourGradient(NamedTuple):
+    """sh_backward: per gaussian, the gradient with respect to its SH coefficients, sh [n, 16, 3] (float32 also where the scene
+    stores them as float16: the gradient in the widened values), and the part of the gradient with respect to its mean that comes
+    through the view direction, means [n, 3].  A field that was left out of `out` is None."""
+    sh: Optional[torch.Tensor]
+    means: Optional[torch.Tensor]
+
+
+class SceneGradient(NamedTuple):
+    """Rasterizer.colour_gradient: per gaussian, the gradient with respect to every array the scene stores, each laid out like
+    that array — means [n, 3], log_scales [n, 3], quats [n, 4] (w, x, y, z as stored), opacity_logit [n], sh [n, 16, 3].  All
+    float32; a field that was left out of `out` is None."""
+    means: Optional[torch.Tensor]
+    log_scales: Optional[torch.Tensor]
+    quats: Optional[torch.Tensor]
+    opacity_logit: Optional[torch.Tensor]
+    sh: Optional[torch.Tensor]
+
+
+_SCENE_SHAPES = {"means": (3,), "log_scales": (3,), "quats": (4,), "opacity_logit": (), "sh": (16, 3)}
+
+
+def _gradient_out(scene: "GaussianScene", kind, out, scene_order: bool) -> _PerGaussianOut:
+    """The tensors a ColourGradient or a SceneGradient (`kind`) is added into: new zeroed ones (no entry clears them), or those of
+    `out` that are not None, once they are what it takes."""
+    if out is not None and (len(out) != len(kind._fields) or all(b is None for b in out)):
+        raise ValueError(f"out must be a {kind.__name__} with at least one tensor")
+    fields = [(f"out.{name}", _SCENE_SHAPES[name], torch.float32, out is None or out[k] is not None)
+              for k, name in enumerate(kind._fields)]
+    return _PerGaussianOut(scene, fields, out, scene_order, zeroed=True)
+
+
+def _sh_backward_into(scene: "GaussianScene", cam: GsrCamera, grad_rgb: torch.Tensor, sh_ptr, means_ptr) -> None:
+    """One gsr_sh_backward on the scene's stream: grad_rgb's rows where they lie, into the outputs that are not None."""
+    sc = scene.c_struct()
+    stride = int(grad_rgb.stride(0)) if grad_rgb.shape[0] > 1 else int(grad_rgb.shape[1])  # (a single row is any distance from the next)
+    with torch.cuda.device(scene.device):
+        check(lib.gsr_sh_backward(C.byref(sc), C.byref(cam), grad_rgb.data_ptr(), stride, sh_ptr, means_ptr, _stream_ptr(scene.device)))
+
+
+def sh_backward(scene: "GaussianScene", cam: GsrCamera, grad_rgb: torch.Tensor, out: Optional[ColourGradient] = None,
+                scene_order: bool = False) -> ColourGradient:
+    """The gradient of a view's per-gaussian colours carried to the SH coefficients and, through the view direction, to the means
+    (gsr_sh_backward): the exact transpose of sh_to_rgb at the scene's degree and this camera's centre, one pass, one thread per
+    gaussian, no cull (sh_to_rgb has none).  grad_rgb: [n, C >= 3] float32 on the scene's device, in the SCENE's order, unit element
+    stride, rows at least C apart; columns 0-2 are read where they lie (a column window of a wider tensor included).  The clamp of
+    the colour to [0, 1] has derivative 0 where it is active and 1 on its edges; the decision is the forward's own.  A row of three
+    zeros is skipped: the gaussian's gradients are not touched.  Coefficients beyond the scene's degree get nothing, and at degree 0
+    the means get nothing.
+    Returns a ColourGradient in the order of the file the scene was loaded from (scene_order=True: of the scene's resident arrays).
+    With `out` — a ColourGradient of float32 contiguous tensors on the scene's device, in the SCENE's order; a field that is None is
+    not computed — the gradient is ACCUMULATED into its tensors and `out` is returned.  No atomics: two calls give the same bits."""
+    _require_cuda(grad_rgb, "grad_rgb")
+    _check_tensor("grad_rgb", grad_rgb, (scene.n, (3, None)), torch.float32, scene.device, "rows")
+    res = _gradient_out(scene, ColourGradient, out, scene_order)
+    if scene.n:
+        _sh_backward_into(scene, cam, grad_rgb, *res.ptrs)
+    return out if out is not None else ColourGradient(*res.result())
 
 
 TOPK_SELECT = {"heaviest": _lib.GSR_TOPK_HEAVIEST, "nearest": _lib.GSR_TOPK_NEAREST}
@@ -618,6 +679,7 @@ class Rasterizer:
         self.last_stats: Optional[Dict[str, int]] = None
         self.last_slice_stats: list = []   # stats() per slice: the last view each slice rendered
         self._splat_rows: Optional[torch.Tensor] = None  # geometry_gradient's [n, 8] scratch, zeroed on every call
+        self._colour_rows: Optional[torch.Tensor] = None  # colour_gradient's [n, 4] scratch (d L / d colour), zeroed on every call
 
     # -- workspace ------------------------------------------------------------------------------
     def _workspace(self, width: int, height: int) -> torch.Tensor:
@@ -995,8 +1057,9 @@ class Rasterizer:
         """The gradient of L = <grad_map, render_features(cam, features)> + <grad_T, final T> with respect to every gaussian's mean,
         log-scales, quaternion and opacity logit: splat_gradient (checked and re-run like any frame) into an [n, 8] scratch kept on
         this Rasterizer and zeroed on every call, then project_backward under the same camera and options.  Arguments as
-        splat_gradient's (scene_order applies to the features and to the result); what is held fixed, the clamp rule and the missing
-        colour term are project_backward's.  Returns a GeometryGradient in the file's order (scene_order=True: the scene's).  With
+        splat_gradient's (scene_order applies to the features and to the result); what is held fixed and the clamp rule are
+        project_backward's.  The features are the caller's, so nothing flows through the SH evaluation here: colour_gradient is the
+        call that differentiates the colour frame, SH term included.  Returns a GeometryGradient in the file's order (scene_order=True: the scene's).  With
         `out` (project_backward's: tensors in the SCENE's order, None = not computed) the view's gradient is ACCUMULATED into it, as
         feature_gradient(out=) does: a camera set is one call per view.  The splat gradient's float atomic sums may differ in the
         last bits between two calls; the projection adds nothing to that."""
@@ -1008,6 +1071,59 @@ class Rasterizer:
         rows = self._splat_rows.zero_()
         self.splat_gradient(cam, features, grad_map, grad_T, opts, min_T, abs_mean=False, out=rows, scene_order=scene_order)
         return project_backward(self.scene, cam, rows, opts, out, scene_order)
+
+    # -- the gradient of the colour frame with respect to everything the scene stores ---------------------------------------------------
+    def _zeroed_scratch(self, name: str, cols: int) -> torch.Tensor:
+        """An [n, cols] float32 scratch kept on this Rasterizer under `name`, zeroed."""
+        buf = getattr(self, name, None)
+        if buf is None or tuple(buf.shape) != (self.scene.n, cols):
+            buf = torch.empty((self.scene.n, cols), dtype=torch.float32, device=self.scene.device)
+            setattr(self, name, buf)
+        return buf.zero_()
+
+    def colour_gradient(self, cam: GsrCamera, grad_image: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
+                        opts: Optional[GsrOptions] = None, min_T: float = 0.0, out: Optional[SceneGradient] = None,
+                        scene_order: bool = False) -> SceneGradient:
+        """The gradient of L = <grad_image, render(cam)> + <grad_T, final T> with respect to every array the scene stores: means,
+        log-scales, quaternions, opacity logits and SH coefficients.  The view's colours (gsr_sh_to_rgb) are the features of the
+        feature blend; ONE pair of stages 1-2, checked and re-run like any frame, then over those same lists the feature gradient
+        (gsr_blend_channels_backward, d L / d colour) and the splat gradient (gsr_blend_splat_backward), each into a scratch kept on
+        this Rasterizer ([n, 4] and [n, 8], zeroed on every call); then project_backward, then sh_backward, which adds the view
+        direction's term into the same `means`.  grad_image: [H, W, 3] as render() lays the frame out (made contiguous float32);
+        grad_T: [H, W] in the layout of the final T, or None; min_T as splat_gradient's.  All finite.
+        Held fixed: what splat_gradient and project_backward hold fixed (the tile rect, the footprint, the 1/255 threshold, the cull;
+        the alpha cap and the ray clamp have derivative 0 where they are active), and the colour clamp to [0, 1]: derivative 0 where
+        it is active, 1 on its edges.
+        Returns a SceneGradient in the file's order (scene_order=True: the scene's).  With `out` — a SceneGradient of float32
+        contiguous tensors on the scene's device, in the SCENE's order; a field that is None is not computed — the view's gradient
+        is ACCUMULATED into it, as geometry_gradient(out=) does: a camera set is one call per view.  The blends' float atomic sums
+        may differ in the last bits between two calls; the projection and the SH transpose add nothing to that."""
+        opts = opts or make_options()
+        scene, dev = self.scene, self.scene.device
+        _require_cuda(grad_image, "grad_image")
+        shape, tshape = self._out_shape(cam, opts)
+        _check_tensor("grad_image", grad_image, tuple(shape), None, dev, "any")
+        if grad_T is not None:
+            _check_tensor("grad_T", grad_T, tshape, None, dev, "any", " (the layout of the final T)")
+        if not (float(min_T) >= 0.0 and float(min_T) < float("inf")):
+            raise ValueError(f"min_T must be finite and >= 0, got {min_T}")
+        res = _gradient_out(scene, SceneGradient, out, scene_order)  # refused before anything runs, not after
+        if scene.n and grad_image.numel():  # else nothing to draw, or a shard that owns no tile row: the gradient is zero
+            gm = grad_image.detach().to(torch.float32).contiguous()
+            gt = grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None
+            rgb = self._view_colours(cam)
+            g_rgb, rows = self._zeroed_scratch("_colour_rows", 4), self._zeroed_scratch("_splat_rows", 8)
+            o = self._checked_lists(cam, opts, "colour gradient")
+            self._blend_lists(cam, o, lib.gsr_blend_channels_backward, gm.data_ptr(), 3, g_rgb.data_ptr(), 4)
+            self._blend_lists(cam, o, lib.gsr_blend_splat_backward, rgb.data_ptr(), 3, 3, gm.data_ptr(),
+                              gt.data_ptr() if gt is not None else None, float(min_T), 0, rows.data_ptr())
+            sc = scene.c_struct()
+            if any(p is not None for p in res.ptrs[:4]):
+                with torch.cuda.device(dev):
+                    check(lib.gsr_project_backward(C.byref(sc), C.byref(cam), C.byref(opts), rows.data_ptr(), *res.ptrs[:4], _stream_ptr(dev)))
+            if res.ptrs[4] is not None or (res.ptrs[0] is not None and scene.sh_degree > 0):
+                _sh_backward_into(scene, cam, g_rgb, res.ptrs[4], res.ptrs[0])
+        return out if out is not None else SceneGradient(*res.result())
 
     def blend_weights(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[n]: every gaussian's blend weight summed over the drawn pixels of this view, sum_p w_i(p) — feature_gradient of a
