@@ -9,7 +9,7 @@
 //
 // What is added:
 //   - staging: the staging thread loads its gaussian's mean (12 B) and computes z = ((x V2 + y V6) + z V10) + V14 — the preprocess'
-//     operations in the preprocess' order (preprocess.hip, geometry_view; that file is built without contraction, here every product
+//     operations in the preprocess' order (gauss_math.h, cam_z; preprocess.hip is built without contraction, here every product
 //     passes through an empty asm statement before it is added, so no build flag can fuse it) — into a fifth LDS plane, sZ[256];
 //   - prologue: a lane reads its pixel's two limits; the quadrant's far_q = max far and near_q = min near over the pixels that can
 //     draw anything (not NaN, near < far) are reduced across the wave once;

@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void project_kernel(int64_t n, const float *__
     if (i >= n) return;
     const float p[3] = {means[3 * i], means[3 * i + 1], means[3 * i + 2]};
 #pragma unroll
-    for (int j = 0; j < 3; ++j) out[3 * i + j] = ((p[0] * V.m[0 + j] + p[1] * V.m[4 + j]) + p[2] * V.m[8 + j]) + V.m[12 + j];
+    for (int j = 0; j < 3; ++j) out[3 * i + j] = point_through(V.m, p, j);
 }
 
 // compute_2d_covariance, rasterize.py:201-252

@@ -58,12 +58,8 @@ __device__ __forceinline__ GeoIn geometry_load(const GsrScene &sc, int64_t i)
     return in;
 }
 
-// Is the gaussian at `p` behind the cull plane of this camera (rasterize.py:377)?  The same expression geometry_view evaluates.
-__device__ __forceinline__ bool culled_by(const Cam &cam, const float p[3])
-{
-    const float *V = cam.V;
-    return ((p[0] * V[2] + p[1] * V[6]) + p[2] * V[10]) + V[14] < GSR_CULL_Z;
-}
+// Is the gaussian at `p` behind the cull plane of this camera (rasterize.py:377)?  On the z geometry_view evaluates (gauss_math.h).
+__device__ __forceinline__ bool culled_by(const Cam &cam, const float p[3]) { return cam_z(cam.V, p) < GSR_CULL_Z; }
 
 // Can NO gaussian of a block be drawn in this view?  `bb` = the block's entry of GsrScene.block_bounds: {min xyz, max xyz, largest
 // log-scale, -}.  Evaluated once per block and view by block_flags_kernel (the frame's first kernel when the scene has bounds); the
@@ -139,22 +135,16 @@ __device__ __forceinline__ GeoOut geometry_view(const float p[3], const GeoIn &i
     const float *V = cam.V, *F = cam.F;
     // project_to_camera_space, rasterize.py:80-86
     float cm[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) cm[j] = ((p[0] * V[0 + j] + p[1] * V[4 + j]) + p[2] * V[8 + j]) + V[12 + j];
+    cam_mean(V, p, cm);
     const bool culled = cm[2] < GSR_CULL_Z;  // :377
     if (!DEBUG && culled) return g;
 
-    // clip-space point, :374, cull zeroing :378, perspective divide :381-382
-    float pt[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) pt[j] = ((p[0] * F[0 + j] + p[1] * F[4 + j]) + p[2] * F[8 + j]) + F[12 + j];
+    // clip-space point, :374, cull zeroing :378, perspective divide :381-382, NDC -> pixel :391
+    float pt[4], mx, my;
+    clip_point(F, p, pt);
     if (culled) pt[0] = pt[1] = pt[2] = pt[3] = 0.0f;
-    const float p_w = 1.0f / (pt[3] + 0.0000001f);
-    const float ndc_x = pt[0] * p_w, ndc_y = pt[1] * p_w;
-
-    // NDC -> pixel, :391
     const float Wf = (float)cam.W, Hf = (float)cam.H;
-    const float mx = ((ndc_x + 1.0f) * Wf - 1.0f) / 2.0f, my = ((ndc_y + 1.0f) * Hf - 1.0f) / 2.0f;
+    pixel_mean(pt, Wf, Hf, &mx, &my);
 
     const float (&C3)[3][3] = in.C3;
 
@@ -171,8 +161,8 @@ __device__ __forceinline__ GeoOut geometry_view(const float p[3], const GeoIn &i
     const float tb0 = tb[0], tb1 = tb[1], tb2 = tb[2], tb3 = tb[3];
 
     // conic, :395-411
-    const float det_inv = det == 0.0f ? 0.0f : 1.0f / det;
-    const float sx = c * det_inv, sy = a * det_inv, sxy = (-b01) * det_inv;
+    float sx, sy, sxy;
+    conic_of(det, a, b01, c, &sx, &sy, &sxy);
 
     // pixel rect, :415-419.  reference_compat clamps to W-1/H-1 (Q1); otherwise to W/H.
     const int xlim = compat ? cam.W - 1 : cam.W, ylim = compat ? cam.H - 1 : cam.H;
@@ -587,17 +577,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8, 8))) voi
     uint32_t cand = 0;  // bit r: gaussian i0 + r may reach one of this rank's tile rows
 #pragma unroll
     for (int r = 0; r < SHARD_PER; ++r) {
-        // the same expressions as geometry_view (this file is built with -ffp-contract=off)
-        float cm[3];
-#pragma unroll
-        for (int j = 0; j < 3; ++j) cm[j] = ((p[r][0] * V[0 + j] + p[r][1] * V[4 + j]) + p[r][2] * V[8 + j]) + V[12 + j];
+        // the camera-space mean and the pixel mean by geometry_view's own functions (gauss_math.h); the radius bound is this phase's
+        float cm[3], pt[4], mx, my;
+        cam_mean(V, p[r], cm);
         bool k = blk_live && i0 + r < sc.n && !(cm[2] < GSR_CULL_Z);
-        const float pt0 = ((p[r][0] * F[0] + p[r][1] * F[4]) + p[r][2] * F[8]) + F[12];
-        const float pt1 = ((p[r][0] * F[1] + p[r][1] * F[5]) + p[r][2] * F[9]) + F[13];
-        const float pt3 = ((p[r][0] * F[3] + p[r][1] * F[7]) + p[r][2] * F[11]) + F[15];
-        const float p_w = 1.0f / (pt3 + 0.0000001f);
-        const float ndc_x = pt0 * p_w, ndc_y = pt1 * p_w;
-        const float mx = ((ndc_x + 1.0f) * Wf - 1.0f) / 2.0f, my = ((ndc_y + 1.0f) * Hf - 1.0f) / 2.0f;
+        clip_point(F, p[r], pt);
+        pixel_mean(pt, Wf, Hf, &mx, &my);
         const float iz = 1.0f / cm[2];
         const float u = fminf(cam.limx, fmaxf(-cam.limx, cm[0] * iz)), vv = fminf(cam.limy, fmaxf(-cam.limy, cm[1] * iz));
         const float jx = cam.fx * iz, jy = cam.fy * iz;

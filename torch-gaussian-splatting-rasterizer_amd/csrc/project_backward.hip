@@ -2,11 +2,12 @@
 // 2-D mean, inverse 2-D covariance, as blend_splat_backward.hip leaves them) chained to what the scene stores — mean, log-scales,
 // quaternion, opacity logit.  project_backward_kernel: one thread per gaussian, no LDS, no atomics (a gaussian belongs to one thread).
 //
-// Built with -ffp-contract=off, like preprocess.hip: the forward is recomputed here from the SAME expressions in the same fp32
-// operation order (gauss_math.h's cov3d_of and ewa_cov2d, geometry_view's camera-space mean, clip point, divide, determinant and
-// conic), so that the backward linearises the values the forward actually used; the intermediates those functions keep to themselves
-// (s, the normalised quaternion, R, M; J, T, T cov3d) are restated beside the calls, expression for expression, and the compiler
-// merges the two.  Held fixed, as the splat gradient already holds them: the tile rect, the footprint, pthr and the cull.
+// Built with -ffp-contract=off, like preprocess.hip: the forward is recomputed here by the functions the preprocess itself calls
+// (gauss_math.h: cam_mean, cov3d_of, ewa_cov2d, cov2d_det, conic_of, clip_point, pixel_mean), so that the backward linearises the
+// values the forward actually used and takes the forward's own decisions (cull, ray clamp, det == 0); the intermediates the chain
+// needs (s, the normalised quaternion, M; x / z, y / z, J, T, T cov3d) come out of cov3d_of and ewa_cov2d through their keep-structs.
+// This file holds the load, the cull compare, those calls and the chain: no forward arithmetic of its own.
+// Held fixed, as the splat gradient already holds them: the tile rect, the footprint, pthr and the cull.
 //
 // Roofline: HBM.  32 B per gaussian for its row of grad_splat; a wave whose 64 rows are all zero leaves on that (most waves of a
 // Morton-ordered scene under one camera); a touched gaussian costs 44 B read (mean 12, log-scales 12, quaternion 16, logit 4) and
@@ -32,59 +33,30 @@ __global__ __launch_bounds__(PB_THREADS, 5) void project_backward_kernel(GsrScen
     if (__ballot(touched) == 0ull) return;  // wave-uniform: 32 B per gaussian and nothing else
     if (!touched) return;
 
-    // ---- the forward, as geometry_one / geometry_view evaluate it ---------------------------------------------------------------
+    // ---- the forward, by the functions geometry_one / geometry_view call (gauss_math.h) ------------------------------------------------
     const float *V = cam.V, *F = cam.F;
     const float p[3] = {sc.means[3 * i], sc.means[3 * i + 1], sc.means[3 * i + 2]};
     float cm[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) cm[j] = ((p[0] * V[0 + j] + p[1] * V[4 + j]) + p[2] * V[8 + j]) + V[12 + j];
+    cam_mean(V, p, cm);
     if (cm[2] < GSR_CULL_Z) return;  // culled: contributes nothing (after its 12-B mean, as in the preprocess)
 
     const float ls[3] = {sc.log_scales[3 * i], sc.log_scales[3 * i + 1], sc.log_scales[3 * i + 2]};
     const float4 q = reinterpret_cast<const float4 *>(sc.quats)[i];
-    // cov3d_of's intermediates
-    const float s[3] = {expf(ls[0]), expf(ls[1]), expf(ls[2])};
-    float nrm = sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
-    const bool nrm_floor = nrm < 1e-12f;
-    nrm = nrm_floor ? 1e-12f : nrm;
-    const float qw = q.x / nrm, qx = q.y / nrm, qy = q.z / nrm, qz = q.w / nrm;
-    float R[3][3], M[3][3], C3[3][3];
-    quat_to_rot(qw, qx, qy, qz, R);
-#pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int b = 0; b < 3; ++b) M[a][b] = R[a][b] * s[b];
-    cov3d_of(ls, q, C3);
-
-    // ewa_cov2d's intermediates (rows 0 and 1 of J, T and T cov3d: row 2 of J is zero)
-    const float fx = cam.fx, fy = cam.fy, limx = cam.limx, limy = cam.limy;
-    const float tz = cm[2];
-    const float txtz = cm[0] / tz, tytz = cm[1] / tz;
-    const float tx = fminf(limx, fmaxf(-limx, txtz)) * tz;
-    const float ty = fminf(limy, fmaxf(-limy, tytz)) * tz;
-    const float J00 = fx / tz, J02 = -(fx * tx) / (tz * tz), J11 = fy / tz, J12 = -(fy * ty) / (tz * tz);
-    float T[2][3], TV[2][3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        T[0][c] = (V[4 * c + 0] * J00 + V[4 * c + 1] * 0.0f) + V[4 * c + 2] * J02;
-        T[1][c] = (V[4 * c + 0] * 0.0f + V[4 * c + 1] * J11) + V[4 * c + 2] * J12;
-    }
-    const float vrk[3][3] = {{C3[0][0], C3[0][1], C3[0][2]}, {C3[0][1], C3[1][1], C3[1][2]}, {C3[0][2], C3[1][2], C3[2][2]}};
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) TV[r][c] = (T[r][0] * vrk[0][c] + T[r][1] * vrk[1][c]) + T[r][2] * vrk[2][c];
-    float c2[4];
-    ewa_cov2d(V, C3, cm, fx, fy, limx, limy, c2);
+    float C3[3][3], c2[4];
+    Cov3dKeep k3;
+    EwaKeep k2;
+    cov3d_of(ls, q, C3, &k3);
+    ewa_cov2d(V, C3, cm, cam.fx, cam.fy, cam.limx, cam.limy, c2, &k2);
     const float a = c2[0], b01 = c2[1], b10 = c2[2], c = c2[3];
-
-    // determinant and conic, geometry_view (covering_bbox's det)
-    const float det = a * c - b10 * b01;
-    if (det == 0.0f) return;
-    const float det_inv = 1.0f / det;
-    const float sx = c * det_inv, sy = a * det_inv, sxy = (-b01) * det_inv;
+    const float det = cov2d_det(a, b01, b10, c);
+    if (det == 0.0f) return;  // (geometry_view goes on with 0 for 1 / det and draws nothing)
+    float sx, sy, sxy;
+    const float det_inv = conic_of(det, a, b01, c, &sx, &sy, &sxy);
     if (!(fabsf(sx) < INFINITY) || !(fabsf(sy) < INFINITY) || !(fabsf(sxy) < INFINITY)) return;
     if (compat && (sx == 0.0f || sy == 0.0f || sxy == 0.0f)) return;  // Q2: the reference's loop never draws it
+    const float (&s)[3] = k3.s, (&M)[3][3] = k3.M, (&T)[3][3] = k2.T, (&TV)[3][3] = k2.TV;  // (rows 0 and 1 of T and T cov3d are read)
+    const float nrm = k3.nrm, qw = k3.q[0], qx = k3.q[1], qy = k3.q[2], qz = k3.q[3];
+    const float tz = cm[2], J00 = k2.J[0][0], J02 = k2.J[0][2], J11 = k2.J[1][1], J12 = k2.J[1][2];
 
     // ---- the chain ----------------------------------------------------------------------------------------------------------------------
     // sigmas <- cov2d: s0 = c / det, s1 = a / det, s2 = -b01 / det, det = a c - b10 b01, the four entries separate inputs.  Every
@@ -114,17 +86,16 @@ __global__ __launch_bounds__(PB_THREADS, 5) void project_backward_kernel(GsrScen
         // J <- cam_mean.  J00 = fx / z; J02 = -fx u / z with u = clamp(x / z): inside the clamp u = x / z (d/dx = -fx / z^2,
         // d/dz = -2 J02 / z); where it is active u is the constant +-lim, the derivative in x / z is 0 and tx = +-lim z still gives
         // d/dz = -J02 / z
-        const bool in_x = txtz > -limx && txtz < limx, in_y = tytz > -limy && tytz < limy;
+        const bool in_x = k2.txtz > -cam.limx && k2.txtz < cam.limx, in_y = k2.tytz > -cam.limy && k2.tytz < cam.limy;
         const float itz = 1.0f / tz;
         float gcm[3];
         gcm[0] = in_x ? -(gJ02 * J00) * itz : 0.0f;
         gcm[1] = in_y ? -(gJ12 * J11) * itz : 0.0f;
         gcm[2] = -(((gJ00 * J00 + gJ11 * J11) + (in_x ? 2.0f : 1.0f) * (gJ02 * J02)) + (in_y ? 2.0f : 1.0f) * (gJ12 * J12)) * itz;
         // screen_mean <- mean, through full_proj and 1 / (w + 1e-7): mx = ((x_clip p_w + 1) W - 1) / 2
-        const float pt0 = ((p[0] * F[0] + p[1] * F[4]) + p[2] * F[8]) + F[12];
-        const float pt1 = ((p[0] * F[1] + p[1] * F[5]) + p[2] * F[9]) + F[13];
-        const float pt3 = ((p[0] * F[3] + p[1] * F[7]) + p[2] * F[11]) + F[15];
-        const float p_w = 1.0f / (pt3 + 0.0000001f);
+        float pt[4], mx, my;
+        clip_point(F, p, pt);
+        const float p_w = pixel_mean(pt, (float)cam.W, (float)cam.H, &mx, &my), pt0 = pt[0], pt1 = pt[1];
         const float gnx = g_mx * (0.5f * (float)cam.W), gny = g_my * (0.5f * (float)cam.H);
         const float gpt0 = gnx * p_w, gpt1 = gny * p_w, gpt3 = -((gnx * pt0 + gny * pt1) * p_w) * p_w;
         // cam_mean <- mean and the clip point <- mean
@@ -161,7 +132,7 @@ __global__ __launch_bounds__(PB_THREADS, 5) void project_backward_kernel(GsrScen
             for (int k = 0; k < 3; ++k)
 #pragma unroll
                 for (int l = 0; l < 3; ++l) gR[k][l] = gM[k][l] * s[l];
-            // R <- the normalised quaternion (w, x, y, z), quat_to_rot
+            // R <- the normalised quaternion: the transpose of quat_to_rot(w, x, y, z, R), which cov3d_of calls
             const float gw = 2.0f * (((qz * (gR[1][0] - gR[0][1]) + qy * (gR[0][2] - gR[2][0])) + qx * (gR[2][1] - gR[1][2])));
             const float gx = 2.0f * ((((qy * (gR[0][1] + gR[1][0]) + qz * (gR[0][2] + gR[2][0])) + qw * (gR[2][1] - gR[1][2])) -
                                       2.0f * qx * (gR[1][1] + gR[2][2])));
@@ -170,7 +141,7 @@ __global__ __launch_bounds__(PB_THREADS, 5) void project_backward_kernel(GsrScen
             const float gz = 2.0f * ((((qx * (gR[0][2] + gR[2][0]) + qy * (gR[1][2] + gR[2][1])) + qw * (gR[1][0] - gR[0][1])) -
                                       2.0f * qz * (gR[0][0] + gR[1][1])));
             // normalised <- stored: n = q / max(|q|, 1e-12); at the floor the divisor is a constant
-            const float dot = nrm_floor ? 0.0f : ((qw * gw + qx * gx) + qy * gy) + qz * gz;
+            const float dot = k3.nrm_floor ? 0.0f : ((qw * gw + qx * gx) + qy * gy) + qz * gz;
             gq[0] = (gw - qw * dot) / nrm;
             gq[1] = (gx - qx * dot) / nrm;
             gq[2] = (gy - qy * dot) / nrm;

@@ -4,7 +4,8 @@
 //
 // Built with -ffp-contract=off, like preprocess.hip: the value before the clamp is recomputed by the forward's own function
 // (sh_eval_with<false>) on the same coefficients, so that the clamp mask m_c = [0 <= v_c <= 1] is the forward's decision bit for bit; the
-// basis values and their derivatives are restated here, expression for expression where the forward has one.
+// view direction and the basis values come from the functions that one calls (sh_dir, sh_band1 .. 3, with their constants).  Only
+// the derivatives of the basis, which the forward has no expression for, are written here.
 //
 // Roofline: HBM.  12 B per gaussian for its row of grad_rgb; a wave whose 64 rows are all zero leaves on that.  A touched gaussian
 // moves 12 (mean) + 192 (SH row; 96 as fp16) + 384 (its row of grad_sh read and written) + 24 (grad_means) B.  One thread per row
@@ -120,30 +121,17 @@ __global__ __launch_bounds__(SHB_THREADS, 4) void sh_backward_kernel(GsrScene sc
             active = active || (pass && g[c] != 0.0f);
         }
         if (active) {
-            // the direction and the basis, as sh_eval_with writes them
-            const float d0 = p[0] - cc[0], d1 = p[1] - cc[1], d2 = p[2] - cc[2];
-            const float n = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-            const float x = d0 / n, y = d1 / n, z = d2 / n;
-            const float c0 = 0.28209479177387814f, c1 = 0.4886025119029199f, nc1 = -0.4886025119029199f;
-            const float k20 = 1.0925484305920792f, k21 = -1.0925484305920792f, k22 = 0.31539156525252005f,
-                        k23 = -1.0925484305920792f, k24 = 0.5462742152960396f;
-            const float k30 = -0.5900435899266435f, k31 = 2.890611442640554f, k32 = -0.4570457994644658f,
-                        k33 = 0.3731763325901154f, k34 = -0.4570457994644658f, k35 = 1.445305721320277f,
-                        k36 = -0.5900435899266435f;
-            const float xx = x * x, yy = y * y;
-            B[0] = c0;
+            // the direction and the basis, by the functions sh_eval_with calls; B[3] with the sign the forward applies where it subtracts
+            float x, y, z;
+            const float n = sh_dir(p, cc, &x, &y, &z);
+            const float xx = x * x, yy = y * y;  // (for the derivatives)
+            B[0] = SH_C0;
             if (degree > 0) {
-                B[1] = nc1 * y; B[2] = c1 * z; B[3] = -(c1 * x);  // (the forward subtracts (c1 x) sh3)
+                sh_band1(x, y, z, B + 1);
+                B[3] = -B[3];
                 if (degree > 1) {
-                    B[4] = (k20 * x) * y; B[5] = (k21 * y) * z; B[6] = k22 * (((2.0f * z) * z - xx) - yy); B[7] = (k23 * x) * z;
-                    B[8] = k24 * (xx - yy);
-                    if (degree > 2) {
-                        B[9] = (k30 * y) * ((3.0f * x) * x - yy); B[10] = ((k31 * x) * y) * z;
-                        B[11] = (k32 * y) * (((4.0f * z) * z - xx) - yy);
-                        B[12] = (k33 * z) * (((2.0f * z) * z - (3.0f * x) * x) - (3.0f * y) * y);
-                        B[13] = (k34 * x) * (((4.0f * z) * z - xx) - yy); B[14] = (k35 * z) * (xx - yy);
-                        B[15] = (k36 * x) * (xx - (3.0f * y) * y);
-                    }
+                    sh_band2(x, y, z, B + 4);
+                    if (degree > 2) sh_band3(x, y, z, B + 9);
                 }
             }
             // ---- d / d mean: sum_k grad_u b_k(u) w_k with w_k = sum_c m_c g_c sh[k][c], then (I - u u^T) / r.  Zero at degree 0.
@@ -151,23 +139,23 @@ __global__ __launch_bounds__(SHB_THREADS, 4) void sh_backward_kernel(GsrScene sc
                 float w[16];
 #pragma unroll
                 for (int k = 1; k < 16; ++k) w[k] = (mg[0] * sh[3 * k] + mg[1] * sh[3 * k + 1]) + mg[2] * sh[3 * k + 2];
-                float gx = -(c1 * w[3]), gy = nc1 * w[1], gz = c1 * w[2];
+                float gx = -(SH_C1 * w[3]), gy = SH_NC1 * w[1], gz = SH_C1 * w[2];
                 if (degree > 1) {
                     const float zz = z * z;
-                    gx = gx + ((((k20 * y) * w[4] - ((2.0f * k22) * x) * w[6]) + (k23 * z) * w[7]) + ((2.0f * k24) * x) * w[8]);
-                    gy = gy + ((((k20 * x) * w[4] + (k21 * z) * w[5]) - ((2.0f * k22) * y) * w[6]) - ((2.0f * k24) * y) * w[8]);
-                    gz = gz + (((k21 * y) * w[5] + ((4.0f * k22) * z) * w[6]) + (k23 * x) * w[7]);
+                    gx = gx + ((((SH_K20 * y) * w[4] - ((2.0f * SH_K22) * x) * w[6]) + (SH_K23 * z) * w[7]) + ((2.0f * SH_K24) * x) * w[8]);
+                    gy = gy + ((((SH_K20 * x) * w[4] + (SH_K21 * z) * w[5]) - ((2.0f * SH_K22) * y) * w[6]) - ((2.0f * SH_K24) * y) * w[8]);
+                    gz = gz + (((SH_K21 * y) * w[5] + ((4.0f * SH_K22) * z) * w[6]) + (SH_K23 * x) * w[7]);
                     if (degree > 2) {
                         const float xy = x * y, q4 = (4.0f * zz - xx) - yy;
-                        gx = gx + (((((((6.0f * k30) * xy) * w[9] + ((k31 * y) * z) * w[10]) - ((2.0f * k32) * xy) * w[11]) -
-                                     (((6.0f * k33) * z) * x) * w[12]) + (k34 * (q4 - 2.0f * xx)) * w[13]) +
-                                   (((2.0f * k35) * z) * x) * w[14]) + ((3.0f * k36) * (xx - yy)) * w[15];
-                        gy = gy + (((((((3.0f * k30) * (xx - yy)) * w[9] + ((k31 * x) * z) * w[10]) + (k32 * (q4 - 2.0f * yy)) * w[11]) -
-                                     (((6.0f * k33) * z) * y) * w[12]) - ((2.0f * k34) * xy) * w[13]) -
-                                   (((2.0f * k35) * z) * y) * w[14]) - ((6.0f * k36) * xy) * w[15];
-                        gz = gz + ((((((k31 * xy) * w[10] + (((8.0f * k32) * y) * z) * w[11]) +
-                                      (k33 * ((6.0f * zz - 3.0f * xx) - 3.0f * yy)) * w[12]) + (((8.0f * k34) * x) * z) * w[13]) +
-                                    (k35 * (xx - yy)) * w[14]));
+                        gx = gx + (((((((6.0f * SH_K30) * xy) * w[9] + ((SH_K31 * y) * z) * w[10]) - ((2.0f * SH_K32) * xy) * w[11]) -
+                                     (((6.0f * SH_K33) * z) * x) * w[12]) + (SH_K34 * (q4 - 2.0f * xx)) * w[13]) +
+                                   (((2.0f * SH_K35) * z) * x) * w[14]) + ((3.0f * SH_K36) * (xx - yy)) * w[15];
+                        gy = gy + (((((((3.0f * SH_K30) * (xx - yy)) * w[9] + ((SH_K31 * x) * z) * w[10]) + (SH_K32 * (q4 - 2.0f * yy)) * w[11]) -
+                                     (((6.0f * SH_K33) * z) * y) * w[12]) - ((2.0f * SH_K34) * xy) * w[13]) -
+                                   (((2.0f * SH_K35) * z) * y) * w[14]) - ((6.0f * SH_K36) * xy) * w[15];
+                        gz = gz + ((((((SH_K31 * xy) * w[10] + (((8.0f * SH_K32) * y) * z) * w[11]) +
+                                      (SH_K33 * ((6.0f * zz - 3.0f * xx) - 3.0f * yy)) * w[12]) + (((8.0f * SH_K34) * x) * z) * w[13]) +
+                                    (SH_K35 * (xx - yy)) * w[14]));
                     }
                 }
                 const float dot = (gx * x + gy * y) + gz * z;
