@@ -250,6 +250,38 @@ def pick_case(G, name):
     return feature_case(G, name)
 
 
+# ---- comparisons against the oracle's camera and preprocess -------------------------------------------------------------------------
+def assert_same_camera(cam, ocam):
+    """gsr_camera_setup's struct against gsr_oracle_camera's, field for field and bit for bit (both run on the host)."""
+    for f in ("w2c", "full_proj", "cam_center"):
+        assert list(getattr(cam, f)) == list(getattr(ocam, f)), f
+    for f in ("focal_x", "focal_y", "lim_x", "lim_y", "tan_fov_x", "tan_fov_y", "width", "height"):
+        assert getattr(cam, f) == getattr(ocam, f), f
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return np.abs(a - b).max(initial=0.0) / max(np.abs(b).max(initial=0.0), 1e-30)
+
+
+def assert_preprocess_matches(dbg, pre, rects_on=None):
+    """Rasterizer.preprocess_debug (as numpy arrays) against orc.preprocess: the integer rects bit for bit — on every gaussian, or on
+    those of the mask `rects_on` — the zero pattern of the conics, and each float array within its tolerance of the array's largest
+    |value|; cov2d on the gaussians in front of the cull plane.  -> the worst share of a tolerance used."""
+    on = slice(None) if rects_on is None else rects_on
+    assert np.array_equal(dbg["tile_bboxes"][on], pre["tile_bboxes"][on])
+    assert np.array_equal(dbg["pixel_bboxes"][on], pre["pixel_bboxes"][on])
+    assert np.array_equal(dbg["sigmas"] == 0, pre["sigmas"] == 0)
+    worst = 0.0
+    for k, tol in (("cov3d", 1e-6), ("cam_means", 1e-6), ("rgb", 1e-6), ("opacity", 1e-6), ("screen_means", 1e-6),
+                   ("sigmas", 1e-5)):
+        assert _rel(dbg[k], pre[k]) < tol, k
+        worst = max(worst, _rel(dbg[k], pre[k]) / tol)
+    vis = pre["cam_means"][:, 2] >= 0.2
+    assert _rel(dbg["cov2d"][vis], pre["cov2d"][vis]) < 1e-5
+    return max(worst, _rel(dbg["cov2d"][vis], pre["cov2d"][vis]) / 1e-5)
+
+
 # ---- references -------------------------------------------------------------------------------------------------------------------
 def oracle_maps(G, c, feats, limit=-1):
     """The oracle's compositing loop over `feats` [n,3] in the place of the colours -> (map [H,W,3], T [H,W], drawn)."""

@@ -9,7 +9,8 @@ import pytest
 import torch
 
 from conftest import assert_frames_close, golden_columns, load_golden, psnr
-from gpu_cases import f5_case, fuzz_case, golden_cameras as _cams, medium_cameras as _medium, namespace
+from gpu_cases import (assert_preprocess_matches, assert_same_camera, f5_case, fuzz_case, golden_cameras as _cams,
+                       medium_cameras as _medium, namespace)
 
 pytestmark = pytest.mark.gpu
 
@@ -26,11 +27,7 @@ def _rel(a, b):
 
 def test_camera_setup_matches_oracle(G):
     g = load_golden("f1_unit.npz")
-    cam, ocam = _cams(G, g)
-    for f in ("w2c", "full_proj", "cam_center"):
-        assert list(getattr(cam, f)) == list(getattr(ocam, f))
-    for f in ("focal_x", "focal_y", "lim_x", "lim_y", "tan_fov_x", "tan_fov_y", "width", "height"):
-        assert getattr(cam, f) == getattr(ocam, f)
+    assert_same_camera(*_cams(G, g))
 
 
 @pytest.mark.parametrize("name,prefix", [("f1_unit.npz", ""), ("f3_edge.npz", "a_"), ("f3_edge.npz", "b_")])
@@ -42,15 +39,8 @@ def test_preprocess_intermediates(G, name, prefix):
     dbg = {k: v.cpu().numpy() for k, v in G.renderer.Rasterizer(scene).preprocess_debug(cam).items()}
     pre = G.orc.preprocess(G.utils.pack_gaussians(cols), ocam)
     # integer outputs: bit-exact against the oracle AND the reference
-    assert np.array_equal(dbg["tile_bboxes"], pre["tile_bboxes"])
-    assert np.array_equal(dbg["pixel_bboxes"], pre["pixel_bboxes"])
+    assert_preprocess_matches(dbg, pre)
     assert np.array_equal(dbg["pixel_bboxes"], g[prefix + "pixel_bboxes"])
-    assert np.array_equal(dbg["sigmas"] == 0, pre["sigmas"] == 0)
-    for k, tol in (("cov3d", 1e-6), ("cam_means", 1e-6), ("rgb", 1e-6), ("opacity", 1e-6), ("screen_means", 1e-6),
-                   ("sigmas", 1e-5)):
-        assert _rel(dbg[k], pre[k]) < tol, k
-    vis = pre["cam_means"][:, 2] >= 0.2
-    assert _rel(dbg["cov2d"][vis], pre["cov2d"][vis]) < 1e-5
     assert _rel(dbg["rgb"], g[prefix + "rgb"]) < 1e-6
 
 

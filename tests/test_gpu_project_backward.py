@@ -12,47 +12,17 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_cases import _tool, fuzz_case, namespace
+from backward_cases import (PINNED, ORDERS, check_project_end_to_end, check_project_operator_parity, dev as _dev, fm, pr,
+                            project_case as _case, project_expected as _expected, project_masked as _masked, project_rows as _rows)
+from gpu_cases import namespace
 from order_scenes import camera_args
 
 pytestmark = pytest.mark.gpu
-
-fm = _tool("fuzz_maps")
-sr = _tool("splat_reference")
-pr = _tool("projection_reference")
-PINNED = [s for s in fm.PINS if s not in fm.IDENTITIES_ONLY]
-ORDERS = ["file", "morton"]
 
 
 @pytest.fixture(scope="module")
 def G():
     return namespace()
-
-
-def _case(G, seed, order):
-    """The pinned case as a scene in `order` with its Rasterizer, cameras and reference, theta in the scene's order and in the
-    file's, the features and the upstream gradients; built once and only read."""
-    key = (seed, order)
-    if key not in G.cases:
-        c = fuzz_case(seed, fm.MAX_N)
-        scene = G.renderer.GaussianScene.from_packed(c["packed"], spatial_order=order == "morton")
-        assert (scene.order is None) == (order == "file")
-        assert ((c["W"] <= 160 and c["H"] <= 96) or (c["W"] <= 33 and c["H"] <= 360)) and c["n"] <= 4096  # small frames: quick cases
-        ref = fm.build_reference(G.orc, c["packed"], c["args"], scene.order)
-        G.cases[key] = dict(seed=seed, c=c, scene=scene, R=G.renderer.Rasterizer(scene), cam=G.renderer.make_camera(*c["args"]),
-                            ocam=G.orc.camera(*c["args"]), ref=ref, n=c["n"], theta=pr.theta_of(c["packed"], scene.order),
-                            theta_file=pr.theta_of(c["packed"]), F=fm.features_of(seed, c["n"]),
-                            Gm=fm.upstream_of(seed, c["H"], c["W"])[0], gT=sr.gT_of(seed, c["H"], c["W"]))
-    return G.cases[key]
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _rows(c):
-    """Seeded unit-normal rows [n, 8] in the scene's order, nonzero on the gaussians the oracle's loop draws."""
-    return pr.unit_rows(c["seed"], c["n"], c["ref"]["kept_in"])
 
 
 def _filled(n, seed=1):
@@ -69,19 +39,7 @@ def _into(G, c, rows, bufs):
 def test_operator_parity(G, seed, order):
     """project_backward on unit-normal rows against vjp64: |err| <= 1e-5 B per element; the file-order result is the scene-order
     one through scene.order_t."""
-    c = _case(G, seed, order)
-    rows = _rows(c)
-    got = G.renderer.project_backward(c["scene"], c["cam"], _dev(rows), scene_order=True)
-    want, B = pr.vjp64(c["theta"], c["ocam"], rows), pr.bound64(c["theta"], c["ocam"], rows)
-    pr.check_geometry(f"seed={seed} order={order} kind=operator", pr.as_dict(got), want, B)
-    untouched = ~rows.any(1)
-    for k in pr.FIELDS:
-        assert not getattr(got, k)[_dev(untouched)].any(), k
-        assert bool(getattr(got, k).any()) == bool(len(c["ref"]["kept_in"])), k
-    filed = G.renderer.project_backward(c["scene"], c["cam"], _dev(rows))
-    for k in pr.FIELDS:
-        a, b = getattr(filed, k), getattr(got, k)
-        assert torch.equal(a if c["scene"].order_t is None else a[c["scene"].order_t], b), k
+    check_project_operator_parity(G, _case(G, seed, order))
 
 
 @pytest.mark.parametrize("seed,order", [(297, "file"), (306, "file"), (264, "morton"), (296, "morton"), (354, "file"), (369, "morton"), (369, "file")])
@@ -142,29 +100,10 @@ def test_accumulation_is_exact_and_runs_are_identical(G, seed):
         assert torch.equal(one[k], again[k]) and torch.equal(out[k], 2 * one[k]), pr.FIELDS[k]
 
 
-def _masked(c, C, ref=None):
-    keep = ~sr.left_out(ref if ref is not None else c["ref"])
-    return c["F"][:, :C], (c["Gm"][..., :C] * keep[..., None]).astype(np.float32), (c["gT"] * keep).astype(np.float32)
-
-
-def _expected(theta_file, ocam, ref, F, Gz, gTz):
-    """(vjp64 of the closed form's rows, 1e-5's bound: bound64 of |g| + A + B_splat), file order."""
-    cf = sr.closed_form(ref, F, Gz, gTz)
-    return pr.vjp64(theta_file, ocam, cf["g"]), pr.bound64(theta_file, ocam, np.abs(cf["g"]) + cf["A"] + cf["B"])
-
-
 @pytest.mark.parametrize("seed", [264, 301, 354, 327, 252])
 def test_end_to_end(G, seed):
     """geometry_gradient at C = 3 and 17, with grad_T and without, against vjp64(closed form)."""
-    c = _case(G, seed, "morton")
-    R, cam = c["R"], c["cam"]
-    for Cw in (3, 17):
-        F, Gz, gTz = _masked(c, Cw)
-        for with_T in (True, False):
-            got = R.geometry_gradient(cam, _dev(F), _dev(Gz), _dev(gTz) if with_T else None)
-            want, B = _expected(c["theta_file"], c["ocam"], c["ref"], F, Gz, gTz if with_T else None)
-            pr.check_geometry(f"seed={seed} order=morton kind=end-to-end C={Cw} gT={int(with_T)}", pr.as_dict(got), want, B)
-            assert all(bool(t.any()) for t in got)
+    check_project_end_to_end(_case(G, seed, "morton"))
 
 
 @pytest.mark.parametrize("seed", [290, 324, 263])

@@ -12,59 +12,21 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_cases import _tool, fuzz_case, namespace
+from backward_cases import (DEGREES, FIVE, ORDERS, PINNED, check_colour_end_to_end, check_five as _check_five, check_sh_operator_parity,
+                            check_the_dense_and_the_per_lane_path_give_the_same_bits, dev as _dev, fm, pr, sh_case as _case,
+                            sh_e2e_case as _e2e_case, sh_expected as _expected, sh_filled as _filled, sh_into as _into,
+                            sh_masked as _masked, shr)
+from gpu_cases import namespace
 from order_scenes import camera_args
 
 pytestmark = pytest.mark.gpu
 
-fm = _tool("fuzz_maps")
-sr = _tool("splat_reference")
-pr = _tool("projection_reference")
-shr = _tool("sh_reference")
-PINNED = [s for s in fm.PINS if s not in fm.IDENTITIES_ONLY]
-ORDERS = ["file", "morton"]
-DEGREES = [0, 1, 2, 3]
 SIZES = {297: 1, 324: 63, 322: 64, 264: 65, 282: 257, 369: 4096}  # the wave edges of a per-wave LDS path; 282 and 369 hold all-clamped rows
 
 
 @pytest.fixture(scope="module")
 def G():
     return namespace()
-
-
-def _packed(G, seed):
-    if ("packed", seed) not in G.cases:
-        G.cases[("packed", seed)] = fuzz_case(seed, fm.MAX_N)
-    return G.cases[("packed", seed)]
-
-
-def _case(G, seed, order, degree=3, half=False):
-    """The pinned case as a scene in `order` at `degree` with its Rasterizer and cameras, theta in the scene's order and in the
-    file's, the upstream rows; built once and only read."""
-    key = (seed, order, degree, half)
-    if key not in G.cases:
-        c = _packed(G, seed)
-        scene = G.renderer.GaussianScene.from_packed(c["packed"], sh_degree=degree, sh_half=half, spatial_order=order == "morton")
-        assert (scene.order is None) == (order == "file")
-        assert ((c["W"] <= 160 and c["H"] <= 96) or (c["W"] <= 33 and c["H"] <= 360)) and c["n"] <= 4096  # small frames: quick cases
-        G.cases[key] = dict(seed=seed, c=c, scene=scene, R=G.renderer.Rasterizer(scene), cam=G.renderer.make_camera(*c["args"]),
-                            ocam=G.orc.camera(*c["args"]), n=c["n"], degree=degree,
-                            theta=shr.theta_of(c["packed"], scene.order, widen_f16=half), theta_file=shr.theta_of(c["packed"]),
-                            g=shr.unit_rows(seed, c["n"]))
-    return G.cases[key]
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _filled(n, seed=1):
-    gen = torch.Generator().manual_seed(seed)
-    return [torch.randn(s, generator=gen).cuda() for s in ((n, 16, 3), (n, 3))]
-
-
-def _into(G, c, g, bufs):
-    return G.renderer.sh_backward(c["scene"], c["cam"], g if isinstance(g, torch.Tensor) else _dev(g), out=G.renderer.ColourGradient(*bufs))
 
 
 def _zeros(n):
@@ -76,19 +38,7 @@ def _zeros(n):
 def test_operator_parity(G, seed, order):
     """sh_backward on unit-normal rows on EVERY gaussian against vjp64 at every degree: |err| <= 1e-5 B per element outside the
     band; the file-order result is the scene-order one through scene.order_t."""
-    for degree in DEGREES:
-        c = _case(G, seed, order, degree)
-        got = G.renderer.sh_backward(c["scene"], c["cam"], _dev(c["g"]), scene_order=True)
-        want, B = shr.vjp64(c["theta"], c["ocam"], degree, c["g"]), shr.bound64(c["theta"], c["ocam"], degree, c["g"])
-        keep_sh, keep_means, left_out = shr.keep_mask(c["theta"], c["ocam"], degree)
-        assert left_out <= shr.CAP_LEFT_OUT
-        shr.check_colour(f"seed={seed} order={order} degree={degree} kind=operator", shr.as_dict(got), want, B,
-                         dict(sh=keep_sh, means=keep_means))
-        assert bool(got.sh.any()) and bool(got.means.any()) == (degree > 0)
-        assert not got.sh[:, shr.coefficients(degree):].any()
-    filed = G.renderer.sh_backward(c["scene"], c["cam"], _dev(c["g"]))
-    for a, b in zip(filed, got):
-        assert torch.equal(a if c["scene"].order_t is None else a[c["scene"].order_t], b)
+    check_sh_operator_parity(G, seed, order)
 
 
 @pytest.mark.parametrize("degree", DEGREES)
@@ -169,18 +119,7 @@ def test_the_dense_and_the_per_lane_path_give_the_same_bits(G, seed, degree, hal
     """Every row touched: each full wave takes the LDS path.  The same rows in four calls, each keeping the lanes of one residue
     mod 4 and zeroing the rest: every wave then has 16 touched lanes, below the dense threshold, and takes the per-lane path.  Row
     for row the same bits, into a prefilled out."""
-    c = _case(G, seed, "morton", degree, half)
-    n = c["n"]
-    g = c["g"].copy()
-    g[~g.any(1)] = 1.0
-    fill = _filled(n, seed=2)
-    dense = [f.clone() for f in fill]
-    _into(G, c, g, dense)
-    sparse = [f.clone() for f in fill]
-    for part in range(4):
-        _into(G, c, np.where((np.arange(n) % 4 == part)[:, None], g, 0.0).astype(np.float32), sparse)
-    assert all(torch.equal(a, b) for a, b in zip(dense, sparse))
-    assert not torch.equal(dense[0], fill[0])
+    check_the_dense_and_the_per_lane_path_give_the_same_bits(G, _case(G, seed, "morton", degree, half))
 
 
 def test_the_clamp_decision_is_the_forwards(G):
@@ -217,67 +156,10 @@ def test_fp16_storage_is_the_fp32_path_on_the_widened_values(G):
 
 
 # ---- end to end: Rasterizer.colour_gradient ---------------------------------------------------------------------------------------------
-FIVE = ("means", "log_scales", "quats", "opacity_logit", "sh")
-
-
-def _e2e_case(G, seed, order="morton"):
-    key = ("e2e", seed, order)
-    if key not in G.cases:
-        c = _case(G, seed, order)
-        cc = c["c"]
-        ref = fm.build_reference(G.orc, cc["packed"], cc["args"], c["scene"].order)
-        G.cases[key] = dict(c, ref=ref, geo_file=pr.theta_of(cc["packed"]), geo=pr.theta_of(cc["packed"], c["scene"].order),
-                            Gm=fm.upstream_of(seed, cc["H"], cc["W"])[0][..., :3], gT=sr.gT_of(seed, cc["H"], cc["W"]))
-    return G.cases[key]
-
-
-def _masked(c, ref=None):
-    keep = ~sr.left_out(ref if ref is not None else c["ref"])
-    return (c["Gm"] * keep[..., None]).astype(np.float32), (c["gT"] * keep).astype(np.float32)
-
-
-def _expected(geo, theta, ocam, ref, Gz, gTz):
-    """(the float64 chain, 1e-5's bound, what to compare) in the order of `geo` / `theta` and ref["kept"]: the float64 colours as
-    features; the closed form's rows through the projection; sum_p w G through the SH transpose, summed into means."""
-    n = ref["n"]
-    fw = shr.sh64(theta, ocam, 3)
-    cf = sr.closed_form(ref, fw["rgb"], Gz, gTz)
-    want, B = pr.vjp64(geo, ocam, cf["g"]), pr.bound64(geo, ocam, np.abs(cf["g"]) + cf["A"] + cf["B"])
-    g_rgb = fm.gradient(ref, Gz, n)
-    own = fm.gradient(dict(ref, w=np.abs(ref["w"])), np.abs(Gz), n)  # sum_p w |G|: the feature gradient's own allowance
-    s_want, s_B = shr.vjp64(theta, ocam, 3, g_rgb), shr.bound64(theta, ocam, 3, np.abs(g_rgb) + own)
-    want, B = dict(want), dict(B)
-    want["means"], B["means"] = want["means"] + s_want["means"], B["means"] + s_B["means"]
-    want["sh"], B["sh"] = s_want["sh"], s_B["sh"]
-    keep_sh, keep_means, left_out = shr.keep_mask(theta, ocam, 3)
-    assert left_out <= shr.CAP_LEFT_OUT
-    keep = {k: np.ones(want[k].shape, bool) for k in FIVE}
-    keep["sh"], keep["means"] = keep_sh, keep_means
-    return want, B, keep
-
-
-def _check_five(tag, got, want, B, keep):
-    fig = {}
-    for k in FIVE:
-        err = np.abs(getattr(got, k).detach().cpu().numpy().astype(np.float64) - want[k])
-        with np.errstate(divide="ignore", invalid="ignore"):
-            r = np.where((err == 0) | ~keep[k], 0.0, err / (shr.REL * B[k]))
-        fig[k] = float(r.max(initial=0.0))
-    print(f"\nsh {tag}: worst |err| / (1e-05 B) " + " ".join(f"{k}={v:.3g}" for k, v in fig.items()), end="")
-    for k, v in fig.items():
-        assert v <= 1.0, f"{tag}: {k} exceeds 1e-5 B by a factor of {v:.3g}"
-
-
 @pytest.mark.parametrize("seed", [264, 301, 354, 327, 252])
 def test_end_to_end(G, seed):
     """colour_gradient, with grad_T and without, against the float64 chain in all five arrays."""
-    c = _e2e_case(G, seed)
-    Gz, gTz = _masked(c)
-    for with_T in (True, False):
-        got = c["R"].colour_gradient(c["cam"], _dev(Gz), _dev(gTz) if with_T else None)
-        want, B, keep = _expected(c["geo_file"], c["theta_file"], c["ocam"], c["ref"], Gz, gTz if with_T else None)
-        _check_five(f"seed={seed} order=morton kind=end-to-end gT={int(with_T)}", got, want, B, keep)
-        assert all(bool(t.any()) for t in got)
+    check_colour_end_to_end(_e2e_case(G, seed))
 
 
 @pytest.mark.parametrize("seed", [290, 324, 263])

@@ -11,31 +11,14 @@ import numpy as np
 import pytest
 import torch
 
-from gpu_cases import _tool, fuzz_case, modules
-
-fm = _tool("fuzz_maps")
-sr = _tool("splat_reference")
-shr = _tool("sh_reference")
-PINNED = [s for s in fm.PINS if s not in fm.IDENTITIES_ONLY]
-ORDERS = ["file", "morton"]
-DEGREES = [0, 1, 2, 3]
+from backward_cases import (DEGREES, ORDERS, PINNED, check_sh_fp32_emulation_within_the_bound, check_sh_vjp64_against_autograd, fm,
+                            sh_inputs as _inputs, shr, sr)
+from gpu_cases import modules
 
 
 @pytest.fixture(scope="module")
 def G():
     return modules()
-
-
-def _inputs(G, seed, order):
-    """The pin's arrays in the scene's order, the oracle's camera and the seeded unit-normal rows; built once and only read."""
-    key = (seed, order)
-    if key not in G.cases:
-        c = fuzz_case(seed, fm.MAX_N)
-        perm = G.renderer.morton_order(c["packed"]["means"]) if order == "morton" else None
-        packed = c["packed"] if perm is None else {k: np.ascontiguousarray(v[perm]) for k, v in c["packed"].items()}
-        G.cases[key] = dict(c=c, packed=packed, cam=G.orc.camera(*c["args"]), theta=shr.theta_of(c["packed"], perm),
-                            g=shr.unit_rows(seed, c["n"]), n=c["n"])
-    return G.cases[key]
 
 
 @pytest.mark.parametrize("order", ORDERS)
@@ -57,23 +40,7 @@ def test_sh64_against_the_oracle(G, seed, order):
 @pytest.mark.parametrize("seed", PINNED)
 def test_vjp64_against_autograd(G, seed, order):
     """Autograd of the monolithic statement: |diff| <= 1e-10 |value| per element; B covers |value|; nothing beyond the degree."""
-    c = _inputs(G, seed, order)
-    worst = 0.0
-    for degree in DEGREES:
-        v, B = shr.vjp64(c["theta"], c["cam"], degree, c["g"]), shr.bound64(c["theta"], c["cam"], degree, c["g"])
-        p = torch.tensor(c["theta"]["means"], dtype=torch.float64, requires_grad=True)
-        sh = torch.tensor(c["theta"]["sh"], dtype=torch.float64, requires_grad=True)
-        rgb = shr.sh_to_rgb_torch(p, sh, torch.tensor(shr.centre_of(c["cam"])), degree)
-        (rgb * torch.tensor(c["g"], dtype=torch.float64)).sum().backward()
-        auto = dict(sh=sh.grad.numpy(), means=p.grad.numpy() if degree > 0 else np.zeros((c["n"], 3)))
-        fa = shr.worst_ratios(auto, v, {k: np.abs(v[k]) for k in shr.FIELDS}, rel=shr.AUTOGRAD_REL)
-        worst = max(worst, max(fa.values()))
-        assert max(fa.values()) <= 1.0, (seed, order, degree, fa)
-        for k in shr.FIELDS:
-            assert (B[k] >= np.abs(v[k]) * (1 - 1e-12)).all()
-        assert np.any(v["sh"]) and bool(np.any(v["means"])) == (degree > 0)
-        assert not v["sh"][:, shr.coefficients(degree):].any()
-    print(f"\nsh autograd seed={seed} {order}: worst |diff| / (1e-10 scale) {worst:.2e}", end="")
+    check_sh_vjp64_against_autograd(_inputs(G, seed, order))
 
 
 @pytest.mark.parametrize("order", ORDERS)
@@ -116,20 +83,7 @@ def test_vjp64_against_finite_differences(G, seed, order):
 def test_fp32_emulation_within_the_bound(G, seed, order):
     """|emulation - vjp64| <= 1e-5 B per element outside the band, from the scene's float32 arrays; at most CAP_LEFT_OUT entries
     left out per pin and degree; on a pin with n >= 64 a clamped and an unclamped channel are both compared."""
-    c = _inputs(G, seed, order)
-    for degree in DEGREES:
-        v, B = shr.vjp64(c["theta"], c["cam"], degree, c["g"]), shr.bound64(c["theta"], c["cam"], degree, c["g"])
-        keep_sh, keep_means, left_out = shr.keep_mask(c["theta"], c["cam"], degree)
-        assert left_out <= shr.CAP_LEFT_OUT, (seed, order, degree, left_out)
-        emu = shr.emulate_fp32(c["theta"], c["cam"], degree, c["g"])
-        shr.check_colour(f"emulation seed={seed} {order} degree={degree}", emu, v, B, dict(sh=keep_sh, means=keep_means))
-        fw = shr.sh64(c["theta"], c["cam"], degree)
-        compared = keep_sh[:, 0, :]
-        if c["n"] >= 64:
-            assert (compared & fw["m"]).any() and (compared & ~fw["m"]).any(), (seed, order, degree)
-        # the float32 decision is the float64 one outside the band
-        m32 = (emu["v"] >= 0) & (emu["v"] <= 1)
-        assert np.array_equal(m32[compared], fw["m"][compared])
+    check_sh_fp32_emulation_within_the_bound(_inputs(G, seed, order))
 
 
 def test_the_clamp_is_covered(G):

@@ -1,5 +1,6 @@
 """CPU: where the tests' shared material lives.  Scenes, cases and references that more than one test file uses are in
-tests/gpu_cases.py, the scaffold of the test_*_abi.py files in tests/abi_checks.py; no test module is another's library, and
+tests/gpu_cases.py, the check bodies the backward tests share between cameras in tests/backward_cases.py, the scaffold of the
+test_*_abi.py files in tests/abi_checks.py; no test module is another's library, and
 nothing under tests/ but conftest.py arranges the import path."""
 import ast
 import glob

@@ -281,6 +281,37 @@ def case_views(orc, case, perm=None):
     return (views + spare)[:3]
 
 
+def _hamilton(a, b):
+    """The Hamilton product of two quaternions (w, x, y, z)."""
+    aw, ax, ay, az = a
+    bw, bx, by, bz = b
+    return np.array([aw * bw - ax * bx - ay * by - az * bz, aw * bx + ax * bw + ay * bz - az * by,
+                     aw * by - ax * bz + ay * bw + az * bx, aw * bz + ax * by - ay * bx + az * bw])
+
+
+def _axis_angle(axis, deg):
+    axis, half = np.asarray(axis, np.float64), 0.5 * np.deg2rad(deg)
+    return np.concatenate([[np.cos(half)], np.sin(half) * axis / np.linalg.norm(axis)])
+
+
+def camera_variant(args, roll_deg, fy_ratio, orbit_axis, orbit_deg):
+    """The camera `args` (make_camera's parameter list) rolled, orbited and made anamorphic: qvec' = q_z(roll) (x) qvec (x)
+    q(orbit_axis, orbit), tvec' = R_z(roll) tvec, fy_full' = fy_ratio fy_full.  The orbit turns the world about its origin — which
+    every pinned camera looks at — before the original pose; the roll turns the image about the optical axis.  With both, no entry
+    of w2c's rotation block is zero, and focal_y, lim_y and tan_fov_y differ from their x counterparts."""
+    qvec, tvec, fx_full, fy_full = args[:4]
+    q = _hamilton(_hamilton(_axis_angle((0, 0, 1), roll_deg), np.asarray(qvec, np.float64)), _axis_angle(orbit_axis, orbit_deg))
+    c, s = np.cos(np.deg2rad(roll_deg)), np.sin(np.deg2rad(roll_deg))
+    t = np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]) @ np.asarray(tvec, np.float64)
+    return (q, t, fx_full, fy_ratio * fy_full) + tuple(args[4:])
+
+
+# name -> (roll_deg, fy_ratio, orbit_axis, orbit_deg).  Measured on every pin but the identities-only one, under both
+# (tests/test_camera_variants.py asserts each): every entry of w2c's rotation block is nonzero; the caps, the clamp band and the SH
+# left-out cap hold on the reference alone as they do under the pin's own camera.
+CAMERAS = {"tilt_a": (33.0, 1.3, (1, 2, 3), 25.0), "tilt_b": (-117.0, 0.75, (3, -1, 2), -40.0)}
+
+
 def features_of(seed, n):
     return (np.random.default_rng(1000 + seed).standard_normal((n, N_CH)) * 50.0).astype(np.float32)
 

@@ -264,11 +264,19 @@ def bound64(theta, cam, rows, compat=True):
 
 
 # ---- (d) the kernel's arrangement of the chain ------------------------------------------------------------------------------------------
+MUTANTS = ("fx_for_fy", "w2c20_dropped", "limx_for_limy")
+
+
 @_one_thread
-def fused_vjp(theta, cam, rows, dtype=torch.float32, compat=True):
+def fused_vjp(theta, cam, rows, dtype=torch.float32, compat=True, mutant=None):
     """The chain as project_backward.hip forms it — P = g + g^T of the 2x2, S = T^T P T, S M, the closed quaternion sums, no stored
     Jacobian — in `dtype`.  float32: the emulation (torch's exp and its order inside a matrix product are not the device's);
-    float64: a second statement of vjp64."""
+    float64: a second statement of vjp64.
+
+    mutant (tests/test_camera_variants.py only; nothing that faces the kernel passes it): one of MUTANTS, a one-token slip of the
+    hand-indexed backward — d cm_y takes J00 (fx) for J11 (fy); the backward's copy of w2c has its [2][0] entry (V[8]) at zero; the
+    y clamp is decided against lim_x.  The forward it is taken at stays the true one."""
+    assert mutant is None or mutant in MUTANTS
     c = camera_of(cam)
     V, F = _t(c["V"], dtype), _t(c["F"], dtype)
     fw = _forward(theta, cam, dtype)
@@ -285,16 +293,20 @@ def fused_vjp(theta, cam, rows, dtype=torch.float32, compat=True):
     T, M, s = fw["T"], fw["M"], fw["s"]
     gT = P @ (T @ fw["vrk"])
     A = V[:3, :3]                              # T[r][k] = sum_m J[r][m] A[k][m]
+    if mutant == "w2c20_dropped":
+        A = A.clone()
+        A[2, 0] = 0.0
     gJ = gT @ A                                # gJ[r][m] = sum_k gT[r][k] A[k][m]
     cm = fw["cam_means"]
     tz = cm[:, 2]
     itz = 1.0 / tz
-    lim = _t([c["limx"], c["limy"]], dtype)
+    lim = _t([c["limx"], c["limx" if mutant == "limx_for_limy" else "limy"]], dtype)
     inside = (fw["ratio"] > -lim) & (fw["ratio"] < lim)
     J = fw["J"]
     zero = torch.zeros_like(tz)
     gcm0 = torch.where(inside[:, 0], -(gJ[:, 0, 2] * J[:, 0, 0]) * itz, zero)
-    gcm1 = torch.where(inside[:, 1], -(gJ[:, 1, 2] * J[:, 1, 1]) * itz, zero)
+    J11 = J[:, 0, 0] if mutant == "fx_for_fy" else J[:, 1, 1]
+    gcm1 = torch.where(inside[:, 1], -(gJ[:, 1, 2] * J11) * itz, zero)
     kx, ky = 1.0 + inside[:, 0].to(dtype), 1.0 + inside[:, 1].to(dtype)
     gcm2 = -(((gJ[:, 0, 0] * J[:, 0, 0] + gJ[:, 1, 1] * J[:, 1, 1]) + kx * (gJ[:, 0, 2] * J[:, 0, 2])) + ky * (gJ[:, 1, 2] * J[:, 1, 2])) * itz
     gcm = torch.stack([gcm0, gcm1, gcm2], 1)
