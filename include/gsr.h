@@ -6,12 +6,14 @@
  * binding for that path binds: every entry point names the reference lines it replaces.  Rules:
  *   - extern "C", POD structs, plain pointers and sizes; no C++/torch types; no exceptions cross.
  *   - every call returns int: GSR_OK or a negative GsrStatus; gsr_last_error() gives thread-local text.
+ *     (gsr_camera_backward_bytes returns a size: it cannot fail.)
  *   - the CALLER owns all device memory (inputs, outputs, one scratch workspace sized by
  *     gsr_workspace_bytes); the library never allocates on the hot path and holds no global state,
  *     so calls with distinct workspaces/streams may run concurrently.
  *   - all device work is enqueued on the caller's hipStream_t (passed as void*); nothing synchronises
  *     except gsr_read_stats.
  *   - fp32 throughout (the reference's arithmetic type); device pointers unless marked [host].
+ *     (gsr_camera_backward sums its fp32 per-gaussian terms over the scene in double and writes doubles.)
  *   - no environment variable is read anywhere: the A/B switches of rounds 1-3 are GsrOptions fields since 0.5.0
  *     (fine_binning, shard_preprocess, blend_pipe_tiles, sh_dense_min) — same frames whatever they say.
  */
@@ -38,7 +40,8 @@ extern "C" {
                             gsr_render_splat_backward — the gradient of a feature map and of the final T with respect to the 2-D splat: opacity, 2-D mean, inverse 2-D covariance, and the
                             per-pixel absolute mean gradients; gsr_project_backward — that gradient chained through the projection to the scene's means, log-scales,
                             quaternions and opacity logits; gsr_sh_backward — the transpose of gsr_sh_to_rgb: a view's colour gradient carried to the SH coefficients
-                            and, through the view direction, to the means): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
+                            and, through the view direction, to the means; gsr_camera_backward / gsr_camera_backward_bytes — the splat gradient of a view
+                            summed into the gradient with respect to the camera: w2c, full_proj, the focal lengths and cam_center, 32 doubles): several views per launch sequence — gsr_render_batch / gsr_render_batch_slots put as many views through ONE
                             preprocess / sort / blend launch sequence as the workspace holds slices of gsr_workspace_bytes() (GsrOptions.batch_views
                             caps it); gsr_blend takes the scene again (NULL = what gsr_preprocess left in the workspace); GsrScene.block_bounds + gsr_scene_bounds /
                             gsr_block_visibility (block-level culling); GsrOptions.tile_row_block (tile-row shards in pairs of rows).  0.5.0: GsrOptions.saturation_rule (the exact colour-saturation early-out), the four environment switches became GsrOptions
@@ -452,6 +455,50 @@ int gsr_sh_backward(const GsrScene *scene, const GsrCamera *cam,
                     const float *grad_rgb /* [n] rows, columns 0-2 read */, int64_t grad_rgb_stride /* floats, >= 3 */,
                     float *grad_sh /* [n,16,3] fp32, ADDS, may be NULL */, float *grad_means /* [n,3] ADDS, may be NULL */,
                     void *stream);
+
+/* The camera backward: the splat gradient of a view chained to the CAMERA.  grad_splat is the array gsr_project_backward reads
+ * ([n][8] float32, columns 0-5 read, columns 6 and 7 ignored); per gaussian the forward is recomputed and the upstream quantities
+ * are formed exactly as gsr_project_backward does it — the same rules, bit for bit, by the same functions: the same Skip rule (a
+ * row of six zeros is not touched, a wave of 64 such rows reads nothing else), the same exclusions (z_cam < GSR_CULL_Z, det is 0, a
+ * conic entry not finite or, with reference_compat, 0), the same Clamp rule (where the ray clamp is active the derivative in x / z is
+ * 0, and t_x = +-lim_x z still depends on z), the same quantities Held fixed (the tile rect, the footprint, the 1/255 threshold and
+ * the cull) and, new here, the depth order and lim_x / lim_y.  Where gsr_project_backward carries gcm, gT, gJ.. and gpt.. on to the
+ * gaussian's mean, this entry multiplies them by what the camera contributed and sums over the gaussians:
+ *   w2c through the camera-space mean   cm[j] = sum_k p[k] V[4 k + j] + V[12 + j]: dV[4 k + j] += p[k] gcm[j], dV[12 + j] += gcm[j];
+ *   w2c through T = J A^T               T[r][c] = sum_m V[4 c + m] J[r][m]: dV[4 c + m] += sum_{r = 0, 1} gT[r][c] J[r][m];
+ *   full_proj                           dF[4 k + j] += p[k] gpt_j, dF[12 + j] += gpt_j for j in {0, 1, 3};
+ *   focal lengths                       J00 = fx / z and J02 = -fx t_x / z^2 are linear in fx: dfx += gJ00 / z - gJ02 t_x / z^2
+ *                                       (no division by fx); fy likewise;
+ *   cam_center                          grad_view_means [n][3] is the view-direction term of d L / d mean — what gsr_sh_backward
+ *                                       leaves in a zeroed [n,3] array when called with grad_sh = NULL; the SH colours depend on
+ *                                       mean - cam_center, so dcc[k] -= grad_view_means[i][k], for EVERY row (no cull: gsr_sh_backward
+ *                                       has none).  No SH row is read here.
+ * Either input may be NULL (not both), and the entries the other feeds are bit for bit what they are in a call with both.
+ * Result layout: grad_camera is 32 doubles on the device, WRITTEN (not added into) — raw partials in the struct fields as the kernels
+ * read them, so a hand-filled GsrCamera has a gradient too:
+ *   [3 k + j]        k = 0..3, j = 0..2    d L / d w2c[4 k + j]       (column 3 of w2c is never read by the forward: derivative 0)
+ *   [12 + 3 k + jj]  k = 0..3, jj = 0..2   d L / d full_proj[4 k + (0, 1, 3)[jj]]   (column 2 of full_proj is never read)
+ *   [24], [25]       d L / d focal_x, focal_y
+ *   [26 .. 28]       d L / d cam_center
+ *   [29]             the number of gaussians that contributed a grad_splat term: touched and passing every exclusion.  Exact.
+ *   [30], [31]       0
+ * Reduction: the per-gaussian terms are float32, as in the chain they extend; every sum across gaussians is done in double — within
+ * a thread, across a wave, across a workgroup and across workgroups.  No atomics; which thread takes which gaussian and the order of
+ * every sum depend on n alone: two calls with the same input give the same bits, and doubling the inputs doubles the result exactly.
+ * Workspace: gsr_camera_backward_bytes(n) = 256 * max(1, ceil(B / ceil(B / 768))) bytes with B = ceil(n / 256) — one row of 32 doubles
+ * per workgroup, at most 768 of them (a 256-byte multiple); every row is written before it is read, so nothing has to be cleared.
+ * 8-byte aligned.  No lists; depends on the scene, the camera and opts->reference_compat only.  The scene's arrays are read, never written.
+ *   - grad_splat and grad_view_means must be finite.
+ * GSR_ERR_BAD_ARG, before any HIP call, for a null scene, camera, options, grad_camera or workspace, both inputs NULL, a workspace
+ * that is too small, a misaligned grad_splat (16 bytes), grad_camera or workspace (8 bytes), grad_camera or the workspace overlapping
+ * an input or each other, a scene gsr_preprocess refuses (sh_dtype), output_dtype = 1, accum_dtype = 1.  n = 0 writes 32 zeros and is
+ * GSR_OK.  Single views: sum over cameras on the caller's side. */
+size_t gsr_camera_backward_bytes(int64_t n);
+int gsr_camera_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts,
+                        const float *grad_splat /* [n][8], columns 0-5 read, may be NULL */,
+                        const float *grad_view_means /* [n][3], may be NULL (not both) */,
+                        double *grad_camera /* [32] device, WRITTEN */,
+                        void *workspace, size_t workspace_bytes, void *stream);
 
 /* Stage 3 for what no blended channel can hold — per pixel p, over the same depth-ordered lists and with the same weights
  * w_i = alpha_i T_i (and the same T, bit for bit) as gsr_blend_features (no reference counterpart):

@@ -267,19 +267,14 @@ def bound64(theta, cam, rows, compat=True):
 MUTANTS = ("fx_for_fy", "w2c20_dropped", "limx_for_limy")
 
 
-@_one_thread
-def fused_vjp(theta, cam, rows, dtype=torch.float32, compat=True, mutant=None):
-    """The chain as project_backward.hip forms it — P = g + g^T of the 2x2, S = T^T P T, S M, the closed quaternion sums, no stored
-    Jacobian — in `dtype`.  float32: the emulation (torch's exp and its order inside a matrix product are not the device's);
-    float64: a second statement of vjp64.
-
-    mutant (tests/test_camera_variants.py only; nothing that faces the kernel passes it): one of MUTANTS, a one-token slip of the
-    hand-indexed backward — d cm_y takes J00 (fx) for J11 (fy); the backward's copy of w2c has its [2][0] entry (V[8]) at zero; the
-    y clamp is decided against lim_x.  The forward it is taken at stays the true one."""
+def fused_upstream(fw, cam, rows, dtype=torch.float32, mutant=None):
+    """The upstream quantities of the kernels' fused chain at the forward `fw`, in `dtype` (project_backward.hip forms them on the
+    way to the mean, camera_backward.hip on the way to the camera; tools/camera_reference.py reads them here): P = g + g^T of the
+    2x2, gT [m, 2, 3] = P (T cov3d), gJ [m, 2, 3] = gT A, gcm [m, 3], gpt [m, 4] (column 2 zero), inside [m, 2] (the ray clamp is
+    not active), with V, F, A = w2c[:3, :3] (the mutant's, if any), g_op and a zero column."""
     assert mutant is None or mutant in MUTANTS
     c = camera_of(cam)
     V, F = _t(c["V"], dtype), _t(c["F"], dtype)
-    fw = _forward(theta, cam, dtype)
     g = _t(rows, dtype)[:, :6]
     g_op, g_mx, g_my, g0, g1, g2 = g.unbind(1)
     a, b01, b10, cc = fw["cov2d"].unbind(1)
@@ -290,8 +285,7 @@ def fused_vjp(theta, cam, rows, dtype=torch.float32, compat=True, mutant=None):
     gb01 = di2 * (((cc * b10) * g0 + (a * b10) * g1) - (a * cc) * g2)
     gb10 = di2 * (((cc * b01) * g0 + (a * b01) * g1) - (b01 * b01) * g2)
     P = torch.stack([2 * ga, gb01 + gb10, gb01 + gb10, 2 * gc], 1).reshape(-1, 2, 2)
-    T, M, s = fw["T"], fw["M"], fw["s"]
-    gT = P @ (T @ fw["vrk"])
+    gT = P @ (fw["T"] @ fw["vrk"])
     A = V[:3, :3]                              # T[r][k] = sum_m J[r][m] A[k][m]
     if mutant == "w2c20_dropped":
         A = A.clone()
@@ -313,6 +307,22 @@ def fused_vjp(theta, cam, rows, dtype=torch.float32, compat=True, mutant=None):
     clip, p_w = fw["clip"], fw["p_w"]
     gnx, gny = g_mx * (0.5 * c["W"]), g_my * (0.5 * c["H"])
     gpt = torch.stack([gnx * p_w, gny * p_w, zero, -((gnx * clip[:, 0] + gny * clip[:, 1]) * p_w) * p_w], 1)
+    return dict(V=V, F=F, A=A, P=P, gT=gT, gJ=gJ, gcm=gcm, gpt=gpt, inside=inside, g_op=g_op, zero=zero)
+
+
+@_one_thread
+def fused_vjp(theta, cam, rows, dtype=torch.float32, compat=True, mutant=None):
+    """The chain as project_backward.hip forms it — P = g + g^T of the 2x2, S = T^T P T, S M, the closed quaternion sums, no stored
+    Jacobian — in `dtype`.  float32: the emulation (torch's exp and its order inside a matrix product are not the device's);
+    float64: a second statement of vjp64.
+
+    mutant (tests/test_camera_variants.py only; nothing that faces the kernel passes it): one of MUTANTS, a one-token slip of the
+    hand-indexed backward — d cm_y takes J00 (fx) for J11 (fy); the backward's copy of w2c has its [2][0] entry (V[8]) at zero; the
+    y clamp is decided against lim_x.  The forward it is taken at stays the true one."""
+    fw = _forward(theta, cam, dtype)
+    up = fused_upstream(fw, cam, rows, dtype, mutant)
+    F, A, P, gcm, gpt, g_op, zero = up["F"], up["A"], up["P"], up["gcm"], up["gpt"], up["g_op"], up["zero"]
+    T, M, s = fw["T"], fw["M"], fw["s"]
     g_mean = gcm @ A.T + gpt @ F[:3].T
     S = T.transpose(1, 2) @ (P @ T)
     gM = S @ M

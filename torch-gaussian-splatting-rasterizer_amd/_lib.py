@@ -139,6 +139,7 @@ EXPORTS = [
     "gsr_render_channels_batch",
     "gsr_blend_splat_backward", "gsr_render_splat_backward",
     "gsr_project_backward", "gsr_sh_backward",
+    "gsr_camera_backward", "gsr_camera_backward_bytes",
 ]
 
 
@@ -180,6 +181,11 @@ def _load() -> C.CDLL:
     L.gsr_project_backward.argtypes = [scene_p, cam_p, opts_p, vp, vp, vp, vp, vp, vp]
     # scene, camera, grad_rgb rows, their stride in floats, grad_sh [n][16][3], grad_means [n][3] (either may be NULL), stream
     L.gsr_sh_backward.argtypes = [scene_p, cam_p, vp, i64, vp, vp, vp]
+    # scene, camera, options, grad_splat [n][8], grad_view_means [n][3] (either may be NULL), grad_camera [32] doubles, the partial sums'
+    # workspace and its bytes, stream.  The bytes are bound as a signed 64-bit integer (size_t's width here), not as c_size_t: that
+    # type marks the entries that take a FRAME workspace of gsr_workspace_bytes(), which this one is not
+    L.gsr_camera_backward.argtypes = [scene_p, cam_p, opts_p, vp, vp, vp, vp, i64, vp]
+    L.gsr_camera_backward_bytes.argtypes = [i64]
     L.gsr_render_batch.argtypes = [scene_p, cam_p, i32, opts_p, i64, vp, sz, vp, i64, vp]
     views = [cam_p, i32, opts_p, i64, vp, sz]        # gsr_*_views: cameras [host], how many, options, max_pairs, workspace, its bytes
     L.gsr_lists_views.argtypes = [scene_p] + views + [vp]
@@ -203,6 +209,7 @@ def _load() -> C.CDLL:
     for name in EXPORTS:
         if name not in ("gsr_last_error", "gsr_default_options"):
             getattr(L, name).restype = C.c_int
+    L.gsr_camera_backward_bytes.restype = sz  # a size, not a status
     return L
 
 

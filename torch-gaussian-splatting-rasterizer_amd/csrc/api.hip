@@ -874,6 +874,46 @@ int gsr_project_backward(const GsrScene *scene, const GsrCamera *cam, const GsrO
                                    static_cast<hipStream_t>(stream));
 }
 
+size_t gsr_camera_backward_bytes(int64_t n) { return camera_backward_bytes(n); }
+
+// The splat gradient of a view (and the view-direction term gsr_sh_backward left) chained to the camera: 32 doubles, no lists
+int gsr_camera_backward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, const float *grad_splat,
+                        const float *grad_view_means, double *grad_camera, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!scene) { set_error("null scene"); return GSR_ERR_BAD_ARG; }
+    int rc = check_camera_options(cam, opts);
+    if (rc) return rc;
+    if (!grad_camera) { set_error("null camera gradient"); return GSR_ERR_BAD_ARG; }
+    if (!workspace) { set_error("null workspace"); return GSR_ERR_BAD_ARG; }
+    if (!grad_splat && !grad_view_means) { set_error("null inputs: both grad_splat and grad_view_means"); return GSR_ERR_BAD_ARG; }
+    const size_t need = camera_backward_bytes(scene->n);
+    if (workspace_bytes < need) { set_error("camera workspace too small: %zu bytes given, %zu needed", workspace_bytes, need); return GSR_ERR_BAD_ARG; }
+    if (reinterpret_cast<uintptr_t>(grad_splat) % 16 != 0) { set_error("grad_splat must be 16-byte aligned"); return GSR_ERR_BAD_ARG; }
+    if (reinterpret_cast<uintptr_t>(grad_camera) % 8 != 0) { set_error("grad_camera must be 8-byte aligned"); return GSR_ERR_BAD_ARG; }
+    if (reinterpret_cast<uintptr_t>(workspace) % 8 != 0) { set_error("the camera workspace must be 8-byte aligned"); return GSR_ERR_BAD_ARG; }
+    const size_t rows = scene->n > 0 ? (size_t)scene->n : 0;
+    const struct { const void *p; size_t bytes; const char *name; } ins[2] = {{grad_splat, 32 * rows, "grad_splat"},
+                                                                               {grad_view_means, 12 * rows, "grad_view_means"}},
+                                                                     outs[2] = {{grad_camera, 32 * sizeof(double), "grad_camera"},
+                                                                                {workspace, need, "the workspace"}};
+    for (const auto &o : outs) {
+        const uintptr_t b = reinterpret_cast<uintptr_t>(o.p);
+        for (const auto &in : ins) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(in.p);
+            if (a && (a == b || (b < a + in.bytes && a < b + o.bytes))) { set_error("%s overlaps %s", o.name, in.name); return GSR_ERR_BAD_ARG; }
+        }
+    }
+    {
+        const uintptr_t g = reinterpret_cast<uintptr_t>(grad_camera), w = reinterpret_cast<uintptr_t>(workspace);
+        if (g < w + need && w < g + 32 * sizeof(double)) { set_error("grad_camera overlaps the workspace"); return GSR_ERR_BAD_ARG; }
+    }
+    rc = check_scene(scene);
+    if (rc) return rc;
+    if (opts->output_dtype == 1) { set_error("camera gradients are float64: output_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    if (opts->accum_dtype == 1) { set_error("camera gradients are summed in float64: accum_dtype = 1 (bfloat16) is not supported"); return GSR_ERR_BAD_ARG; }
+    return launch_camera_backward(*scene, *cam, *opts, grad_splat, grad_view_means, grad_camera, workspace, static_cast<hipStream_t>(stream));
+}
+
 // The colour gradient of a view chained to the scene's SH coefficients and means: no workspace, no lists, no options
 int gsr_sh_backward(const GsrScene *scene, const GsrCamera *cam, const float *grad_rgb, int64_t grad_rgb_stride, float *grad_sh,
                     float *grad_means, void *stream)

@@ -298,6 +298,11 @@ int launch_project_backward(const GsrScene &scene, const GsrCamera &cam, const G
 // i's SH coefficients and, through the view direction, to its mean; ADDED into the two arrays that are not null; no workspace
 int launch_sh_backward(const GsrScene &scene, const GsrCamera &cam, const float *grad_rgb, int64_t grad_stride, float *grad_sh,
                        float *grad_means, hipStream_t s);
+// The splat gradient of a view chained to the camera (camera_backward.hip): 32 doubles WRITTEN to grad_camera, the partial sums in
+// `workspace` (camera_backward_bytes(n), a function of n alone); either input may be null, not both; no atomics, fixed order
+size_t camera_backward_bytes(int64_t n);
+int launch_camera_backward(const GsrScene &scene, const GsrCamera &cam, const GsrOptions &opts, const float *grad_splat,
+                           const float *grad_view_means, double *grad_camera, void *workspace, hipStream_t s);
 int launch_blend_stats(FrameCtrl *ctrl, size_t workspace_bytes, hipStream_t s);
 
 // ---- small device helpers -----------------------------------------------------------------------

@@ -575,6 +575,95 @@ def sh_backward(scene: "GaussianScene", cam: GsrCamera, grad_rgb: torch.Tensor, 
     return out if out is not None else ColourGradient(*res.result())
 
 
+class CameraGradient(NamedTuple):
+    """camera_backward / Rasterizer.camera_gradient: the gradient with respect to the GsrCamera fields as the kernels read them —
+    w2c [4, 4], full_proj [4, 4], focal [2] = (focal_x, focal_y), cam_center [3] — and `contributing` (0-d), the exact number of
+    gaussians that contributed a splat term.  float64 tensors on the scene's device, all views of ONE buffer (nothing has
+    synchronised); the entries the forward never reads (column 3 of w2c, column 2 of full_proj) are 0.  pose_gradient chains them to
+    a twist and a log-focal step."""
+    w2c: torch.Tensor
+    full_proj: torch.Tensor
+    focal: torch.Tensor
+    cam_center: torch.Tensor
+    contributing: torch.Tensor
+
+
+def _camera_gradient_of(buf: torch.Tensor) -> CameraGradient:
+    """The [32] doubles gsr_camera_backward wrote, laid out as the struct's fields: slot 3 k + j is w2c[k][j] (j < 3), slot
+    12 + 3 k + jj is full_proj[k][(0, 1, 3)[jj]]; the columns the forward never reads are zeros.  Slice copies on the device into
+    ONE buffer, of which the five fields are views: no index tensor, no sync."""
+    out = torch.zeros(38, dtype=torch.float64, device=buf.device)
+    w2c, proj, src = out[0:16].view(4, 4), out[16:32].view(4, 4), buf[12:24].view(4, 3)
+    w2c[:, :3] = buf[0:12].view(4, 3)
+    proj[:, 0:2] = src[:, 0:2]
+    proj[:, 3] = src[:, 2]
+    out[32:38] = buf[24:30]
+    return CameraGradient(w2c, proj, out[32:34], out[34:37], out[37])
+
+
+def _camera_workspace(scene: "GaussianScene", keep: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The partial sums' workspace of gsr_camera_backward for this scene (`keep` itself when it already is one)."""
+    nbytes = int(lib.gsr_camera_backward_bytes(scene.n))
+    if keep is not None and keep.numel() == nbytes and keep.device == scene.device:
+        return keep
+    return torch.empty(nbytes, dtype=torch.uint8, device=scene.device)
+
+
+def _camera_backward_into(scene: "GaussianScene", cam: GsrCamera, opts: GsrOptions, splat_ptr, view_ptr, ws: torch.Tensor) -> CameraGradient:
+    """One gsr_camera_backward on the scene's stream into a new [32] float64 buffer."""
+    buf = torch.empty(32, dtype=torch.float64, device=scene.device)
+    sc = scene.c_struct()
+    with torch.cuda.device(scene.device):
+        check(lib.gsr_camera_backward(C.byref(sc), C.byref(cam), C.byref(opts), splat_ptr, view_ptr, buf.data_ptr(), ws.data_ptr(), ws.numel(),
+                                      _stream_ptr(scene.device)))
+    return _camera_gradient_of(buf)
+
+
+def camera_backward(scene: "GaussianScene", cam: GsrCamera, splat_rows: Optional[torch.Tensor] = None,
+                    view_mean_rows: Optional[torch.Tensor] = None, opts: Optional[GsrOptions] = None) -> CameraGradient:
+    """The splat gradient of a view summed into the gradient with respect to the CAMERA (gsr_camera_backward): the bare operator
+    on arrays in the SCENE's order.  splat_rows: [n, 8] float32 contiguous on the scene's device, columns (opacity, mean x, y, s0,
+    s1, s2, -, -) as splat_gradient(out=) fills them — the array project_backward reads, under its rules: a row of six zeros is
+    skipped, gaussians the view culls or whose 2-D covariance is singular contribute nothing, the derivative in x / z is 0 where the
+    ray clamp is active; held fixed are the tile rect, the footprint, the 1/255 threshold, the cull, the depth order and lim_x /
+    lim_y.  view_mean_rows: [n, 3] float32 contiguous, the view-direction term of d L / d mean that sh_backward leaves in `means`
+    when it is called alone; its negated column sum is d L / d cam_center.  Either may be None, not both.
+    Returns a CameraGradient of float64 tensors on the device.  The per-gaussian terms are float32, every sum across gaussians is a
+    double sum in a fixed order: no atomics, two calls give the same bits."""
+    if splat_rows is None and view_mean_rows is None:
+        raise ValueError("camera_backward needs splat_rows, view_mean_rows or both")
+    for name, t, cols in (("splat_rows", splat_rows, 8), ("view_mean_rows", view_mean_rows, 3)):
+        if t is not None:
+            _require_cuda(t, name)
+            _check_tensor(name, t, (scene.n, cols), torch.float32, scene.device)
+    if scene.n == 0:  # nothing to sum (an empty tensor has no address to hand to the library)
+        return _camera_gradient_of(torch.zeros(32, dtype=torch.float64, device=scene.device))
+    return _camera_backward_into(scene, cam, opts or make_options(), splat_rows.data_ptr() if splat_rows is not None else None,
+                                 view_mean_rows.data_ptr() if view_mean_rows is not None else None, _camera_workspace(scene))
+
+
+def pose_gradient(cam: GsrCamera, cg: CameraGradient):
+    """(twist [6], log_focal [2]), float64 CPU tensors: a CameraGradient's raw partials chained to the six parameters of a rigid
+    motion of the camera in its own frame and to the logs of the two focal lengths — what a pose or focal optimiser steps in.  The
+    twist xi = (omega, v) moves the camera by x_cam' = x_cam + omega x x_cam + v + O(|xi|^2): w2c' = w2c E(xi) in the row-vector
+    convention (E[:3, :3] = exp([omega]x)^T, E[3, :3] = v), full_proj' = w2c' (w2c^-1 full_proj) with the projection matrix
+    unchanged, cam_center' = inverse(w2c')[3, :3].  log_focal[0] = focal_x cg.focal[0] + sum_k full_proj[4 k] cg.full_proj[k][0]:
+    column 0 of full_proj is proportional to fx; lim_x is held fixed; y likewise with column 1.  Chained in float64 from the
+    struct's own values.  This is the one place that synchronises (it reads cg)."""
+    f64 = torch.float64
+    V = torch.tensor(list(cam.w2c), dtype=f64).view(4, 4)
+    F = torch.tensor(list(cam.full_proj), dtype=f64).view(4, 4)
+    dV, dF, dfoc, dcc = (t.detach().to("cpu", f64) for t in (cg.w2c, cg.full_proj, cg.focal, cg.cam_center))
+    Vinv = torch.linalg.inv(V)
+    GE = V.T @ dV + V.T @ dF @ (Vinv @ F).T  # d L / d E at E = I
+    A = GE[:3, :3]
+    # d E[:3, :3] / d omega_k = -[e_k]x: <A, -[e_k]x>
+    omega = torch.stack([A[1, 2] - A[2, 1], A[2, 0] - A[0, 2], A[0, 1] - A[1, 0]])
+    v = GE[3, :3] - Vinv[:3, :3] @ dcc  # d cam_center = -(dE V^-1)[3, :3]
+    log_focal = torch.stack([cam.focal_x * dfoc[0] + (F[:, 0] * dF[:, 0]).sum(), cam.focal_y * dfoc[1] + (F[:, 1] * dF[:, 1]).sum()])
+    return torch.cat([omega, v]), log_focal
+
+
 TOPK_SELECT = {"heaviest": _lib.GSR_TOPK_HEAVIEST, "nearest": _lib.GSR_TOPK_NEAREST}
 
 
@@ -680,6 +769,8 @@ class Rasterizer:
         self.last_slice_stats: list = []   # stats() per slice: the last view each slice rendered
         self._splat_rows: Optional[torch.Tensor] = None  # geometry_gradient's [n, 8] scratch, zeroed on every call
         self._colour_rows: Optional[torch.Tensor] = None  # colour_gradient's [n, 4] scratch (d L / d colour), zeroed on every call
+        self._view_mean_rows: Optional[torch.Tensor] = None  # camera_gradient's [n, 3] scratch (the view direction's d L / d mean)
+        self._camera_ws: Optional[torch.Tensor] = None  # camera_gradient's workspace of partial sums (gsr_camera_backward_bytes)
 
     # -- workspace ------------------------------------------------------------------------------
     def _workspace(self, width: int, height: int) -> torch.Tensor:
@@ -1124,6 +1215,57 @@ class Rasterizer:
             if res.ptrs[4] is not None or (res.ptrs[0] is not None and scene.sh_degree > 0):
                 _sh_backward_into(scene, cam, g_rgb, res.ptrs[4], res.ptrs[0])
         return out if out is not None else SceneGradient(*res.result())
+
+    # -- the gradient of a frame or of a feature map with respect to the camera -----------------------------------------------------------
+    def camera_gradient(self, cam: GsrCamera, grad_image: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
+                        opts: Optional[GsrOptions] = None, min_T: float = 0.0, features: Optional[torch.Tensor] = None,
+                        scene_order: bool = False) -> CameraGradient:
+        """The gradient of L = <grad_image, render(cam)> + <grad_T, final T> with respect to the CAMERA: w2c, full_proj, the focal
+        lengths and cam_center, as a CameraGradient (pose_gradient chains it to a twist and a log-focal step).  colour_gradient's
+        sequence: the view's colours as the features, ONE pair of stages 1-2, checked and re-run like any frame; over those lists
+        gsr_blend_channels_backward ([n, 4] scratch) and gsr_blend_splat_backward ([n, 8] scratch); above degree 0 gsr_sh_backward
+        with no grad_sh into a zeroed [n, 3] scratch — the view direction's term, whose negated sum is d L / d cam_center; then ONE
+        gsr_camera_backward.  With `features` ([n, C] as render_features takes them; scene_order applies to them) grad_image is the
+        [H, W, C] upstream of render_features(cam, features), as in geometry_gradient, and nothing flows through the SH evaluation:
+        cam_center gets 0.  grad_T: [H, W] in the layout of the final T, or None; min_T as splat_gradient's.  All finite.
+        Held fixed: what colour_gradient holds fixed, and the depth order and lim_x / lim_y.  The scratches and the partial sums'
+        workspace are kept on this Rasterizer.  The blends' float atomic sums may differ in the last bits between two calls; the
+        camera reduction adds nothing to that (double sums in a fixed order)."""
+        opts = opts or make_options()
+        scene, dev = self.scene, self.scene.device
+        _require_cuda(grad_image, "grad_image")
+        shape, tshape = self._out_shape(cam, opts)
+        if features is not None:
+            self._check_features(features, _lib.GSR_MAX_FEATURE_CHANNELS)
+            shape = tuple(shape[:2]) + (int(features.shape[1]),)
+        _check_tensor("grad_image", grad_image, tuple(shape), None, dev, "any")
+        if grad_T is not None:
+            _check_tensor("grad_T", grad_T, tshape, None, dev, "any", " (the layout of the final T)")
+        if not (float(min_T) >= 0.0 and float(min_T) < float("inf")):
+            raise ValueError(f"min_T must be finite and >= 0, got {min_T}")
+        self._camera_ws = _camera_workspace(scene, getattr(self, "_camera_ws", None))
+        rows = self._zeroed_scratch("_splat_rows", 8)
+        if not (scene.n and grad_image.numel()):  # nothing to draw, or a shard that owns no tile row: the gradient is zero
+            return _camera_gradient_of(torch.zeros(32, dtype=torch.float64, device=dev))
+        gm = grad_image.detach().to(torch.float32).contiguous()
+        gt = grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None
+        view_rows = None
+        o = None
+        if features is None:
+            rgb, n_ch, stride = self._view_colours(cam), 3, 3
+            g_rgb = self._zeroed_scratch("_colour_rows", 4)
+            o = self._checked_lists(cam, opts, "camera gradient")
+            self._blend_lists(cam, o, lib.gsr_blend_channels_backward, gm.data_ptr(), 3, g_rgb.data_ptr(), 4)
+        else:
+            rgb = self._feature_rows(features.detach(), scene_order)
+            n_ch, stride = int(rgb.shape[1]), int(rgb.stride(0))
+            o = self._checked_lists(cam, opts, "camera gradient")
+        self._blend_lists(cam, o, lib.gsr_blend_splat_backward, rgb.data_ptr(), stride, n_ch, gm.data_ptr(),
+                          gt.data_ptr() if gt is not None else None, float(min_T), 0, rows.data_ptr())
+        if features is None and scene.sh_degree > 0:
+            view_rows = self._zeroed_scratch("_view_mean_rows", 3)
+            _sh_backward_into(scene, cam, g_rgb, None, view_rows.data_ptr())
+        return _camera_backward_into(scene, cam, opts, rows.data_ptr(), view_rows.data_ptr() if view_rows is not None else None, self._camera_ws)
 
     def blend_weights(self, cam: GsrCamera, opts: Optional[GsrOptions] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """[n]: every gaussian's blend weight summed over the drawn pixels of this view, sum_p w_i(p) — feature_gradient of a
