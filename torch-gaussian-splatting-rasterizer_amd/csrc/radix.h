@@ -68,7 +68,7 @@ __device__ __forceinline__ bool radix_tile_of(uint32_t n, uint32_t tile_size, ui
 // 32 B per array, measured +35 % per pass); doubling the tile keeps the runs at 16 records and the table reads per record equal.
 // LDS budget: the arrays of a record (key, payload) pass through ONE tile-sized buffer one after the other instead of
 // each having its own (barriers more per tile; the depth sort's 8-byte {id, rect8} payload in two halves): 52 KB instead of 116 KB
-// for the depth sort's 512-thread tiles, so that LDS leaves room for three workgroups on a CU instead of one.  Two are resident: the scatter kernel's 117-128 VGPRs allow four waves
+// for the depth sort's 512-thread tiles, so that LDS leaves room for three workgroups on a CU instead of one.  Two are resident: the scatter kernel's 103-120 VGPRs allow four waves
 // per SIMD, which is two 512-thread workgroups (sort.hip; the compiler's occupancy figure, tools/kernel_resources.sh) — the passes
 // are bound by the latency of a tile's dependent phases (load, rank, layout, reorder, store), not by any pipe, and with one
 // workgroup per CU a 410-tile pass ran as two rounds of 256 + 154.

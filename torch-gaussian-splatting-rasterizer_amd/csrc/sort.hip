@@ -15,7 +15,8 @@
 //   rowscan  one workgroup per digit: exclusive scan of its row in place, row total -> digit_tot[digit]
 //   scatter  one workgroup per tile: per-wave ranking through LDS peer masks -> tile reordered by digit in LDS -> digit
 //            runs written out contiguously (coalesced), position = digit base + scanned hist + rank in run   (radix.h);
-//            the keys go through the tile buffer first, then the payload
+//            the keys go through the tile buffer first, then the payload.  The keys and the two table words are requested
+//            before anything else; the digit bases are scanned while the keys are in flight
 // The element count lives in device memory (n_dev): grids are sized by the host-side bound and surplus workgroups fall
 // through.  Which tile a hist / scatter workgroup takes is a matter of speed only (radix_tile_of, radix.h: consecutive tiles per XCD).  16 keys per thread (2048-key tiles measured slower, the fixed per-workgroup costs dominate); the depth sort's
 // 9-bit passes run 512 threads on 8192 keys, the pair sort's <= 8-bit passes 256 threads on 4096 (radix.h says why).
@@ -61,33 +62,29 @@ __global__ __launch_bounds__(THREADS) void radix_hist_kernel(const KeyT *__restr
     uint32_t tile;
     if (!radix_tile_of(n, (uint32_t)TILE, &tile)) return;  // rowscan and scatter stop at the live tiles too
     const uint32_t base = tile * (uint32_t)TILE;
-    h[threadIdx.x] = 0;
-    if (threadIdx.x == 0) s_max = 0;
-    __syncthreads();
-    uint32_t kmax = 0;
-    if (n - base >= (uint32_t)TILE) {  // full tile: unguarded loads, all in flight together
-        uint32_t k[ITEMS];
+    // the keys are requested ahead of the LDS clear and the barrier that publishes it: the loads fly across both
+    const bool full = n - base >= (uint32_t)TILE;  // unguarded loads, all in flight together
+    uint32_t k[ITEMS];
+    if (full) {
 #pragma unroll
         for (int r = 0; r < ITEMS; ++r) k[r] = keys[base + r * THREADS + threadIdx.x];
-#pragma unroll
-        for (int r = 0; r < ITEMS; ++r)
-            if (!DROP || k[r] < ps.drop_from) {
-                atomicAdd(&h[((k[r] - ps.key_base) >> shift) & mask], 1u);
-                kmax = max(kmax, k[r]);
-            }
     } else {
 #pragma unroll
         for (int r = 0; r < ITEMS; ++r) {
             const uint32_t idx = base + r * THREADS + threadIdx.x;
-            if (idx < n) {
-                const uint32_t k = keys[idx];
-                if (!DROP || k < ps.drop_from) {
-                    atomicAdd(&h[((k - ps.key_base) >> shift) & mask], 1u);
-                    kmax = max(kmax, k);
-                }
-            }
+            k[r] = idx < n ? (uint32_t)keys[idx] : 0u;
         }
     }
+    h[threadIdx.x] = 0;
+    if (threadIdx.x == 0) s_max = 0;
+    __syncthreads();
+    uint32_t kmax = 0;
+#pragma unroll
+    for (int r = 0; r < ITEMS; ++r)
+        if ((full || base + r * THREADS + threadIdx.x < n) && (!DROP || k[r] < ps.drop_from)) {
+            atomicAdd(&h[((k[r] - ps.key_base) >> shift) & mask], 1u);
+            kmax = max(kmax, k[r]);
+        }
     if (ps.dyn_pass == 0) {  // key range of the frame: wave max -> workgroup max -> at most one device atomic, usually none
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) kmax = max(kmax, (uint32_t)__shfl_xor((int)kmax, d, 64));
@@ -194,11 +191,10 @@ __global__ __launch_bounds__(THREADS, 4) void radix_scatter_kernel(
     const uint32_t base = tile * (uint32_t)TILE;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
-    radix_clear(sm);
-    __syncthreads();
-
-    // keys first; the payloads are loaded when their turn at the tile buffer comes (their loads fly while the previous array
-    // goes out), so that at most four 16-register arrays are live at once
+    // Everything the tile reads that depends on nothing but its index is requested here, ahead of the LDS clear and its barrier: this
+    // digit's total and this tile's entry of the scanned histogram, the plan's pass count, the keys (behind the
+    // ranking and the layout the table words cost the tile a round trip of their own).  The payloads are loaded when their turn at
+    // the tile buffer comes (their loads fly while the previous array goes out), so that at most four 16-register arrays are live at once
     uint32_t key[ITEMS], rank[ITEMS];
     const bool full = n - base >= (uint32_t)TILE;  // all but the last workgroup: unguarded loads, all in flight together
     auto load = [&](const auto *__restrict__ src, uint32_t (&v)[ITEMS], uint32_t fill) {
@@ -213,25 +209,42 @@ __global__ __launch_bounds__(THREADS, 4) void radix_scatter_kernel(
             }
         }
     };
-    load(keys_in, key, KEY_INVALID);
+    // (the two table words are requested ahead of the keys: loads return in request order, and the scan below waits for them alone)
+    const bool has = (uint32_t)tid <= mask;  // digit values beyond the pass's width do not occur
+    const uint32_t tot = has ? ctrl->digit_tot[tid] : 0u;
+    const uint32_t scanned = has ? hist[(size_t)tid * hist_blocks + tile] : 0u;
+    // the depth sort's LAST pass (which one that is the frame's plan says) leaves sorted ids and rects: nobody reads the sorted keys
+    const bool write_keys = !(ps.dyn_pass >= 0 && (uint32_t)ps.dyn_pass + 1u == ctrl->sort_passes);
+    // (the partial tile's loads are unguarded too, from indices clamped to the last key — n >= 1 here, and dig() never looks at a key
+    // past n: ITEMS loads in straight-line code either way, after which the compiler's wait for the table words leaves them in flight)
+    if (full) {
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r) key[r] = (uint32_t)keys_in[base + wave * (64 * ITEMS) + r * 64 + lane];
+    } else {
+#pragma unroll
+        for (int r = 0; r < ITEMS; ++r) key[r] = (uint32_t)keys_in[min(base + wave * (64 * ITEMS) + r * 64 + lane, n - 1u)];
+    }
     auto dig = [&](int r) -> uint32_t {
         const uint32_t idx = base + wave * (64 * ITEMS) + r * 64 + lane;
         const bool valid = (idx < n) && (!DROP || key[r] < ps.drop_from);
         return valid ? ((key[r] - ps.key_base) >> shift) & mask : RADIX_NO_DIGIT;
     };
+
+    radix_clear(sm);
+    {  // global digit bases, while the keys are in flight: exclusive scan of the digit totals + this tile's entry of the scanned
+       // histogram.  The scan's first barrier also publishes the cleared counters and peer masks; its second one ends its use of
+       // sm.scratch, which radix_tile_layout takes next
+        uint32_t all_total;
+        const uint32_t gs = block_excl_scan<THREADS>(tot, sm.scratch, &all_total);
+        digit_base[tid] = gs + scanned;
+        if (n_out != nullptr && tile == 0 && tid == 0) *n_out = all_total;
+    }
+
     radix_rank(sm, dig, rank);
     __syncthreads();
 
     radix_tile_layout(sm);
-    {  // global digit bases: exclusive scan of the digit totals + this tile's entry of the scanned histogram
-        const bool has = (uint32_t)tid <= mask;  // digit values beyond the pass's width do not occur
-        const uint32_t tot = has ? ctrl->digit_tot[tid] : 0u;
-        uint32_t all_total;
-        const uint32_t gs = block_excl_scan<THREADS>(tot, sm.scratch, &all_total);
-        digit_base[tid] = gs + (has ? hist[(size_t)tid * hist_blocks + tile] : 0u);
-        if (n_out != nullptr && tile == 0 && tid == 0) *n_out = all_total;
-    }
-    __syncthreads();
+    __syncthreads();  // publishes the tile's tables (and, long since, digit_base)
 
     radix_positions(sm, dig, rank);  // rank[] is now the position inside the reordered tile
     // the payload's loads fly while the keys go out
@@ -266,8 +279,6 @@ __global__ __launch_bounds__(THREADS, 4) void radix_scatter_kernel(
     radix_stage(sm, rank, key);
     __syncthreads();
     const uint32_t nvalid = sm.n_valid;
-    // the depth sort's LAST pass (which one that is the frame's plan says) leaves sorted ids and rects: nobody reads the sorted keys
-    const bool write_keys = !(ps.dyn_pass >= 0 && (uint32_t)ps.dyn_pass + 1u == ctrl->sort_passes);
     uint32_t gpos[ITEMS];
 #pragma unroll
     for (int k = 0; k < ITEMS; ++k) {
