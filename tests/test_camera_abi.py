@@ -115,12 +115,19 @@ def test_the_kernel_has_a_translation_unit_of_its_own_with_the_preprocess_flags(
     rule, pre = abi.makefile_recipe("camera_backward.o"), abi.makefile_recipe("preprocess.o")
     assert "-ffp-contract=off" in rule and rule.split() == pre.split()
     deps = abi.makefile_rule("camera_backward.o")[0]
-    assert "gauss_math.h" in deps and "gsr_internal.h" in deps and "camera_backward.hip" in deps
+    assert "gauss_math.h" in deps and "gsr_internal.h" in deps and "camera_backward.hip" in deps and "splat_chain.h" in deps
     src = open(os.path.join(abi.CSRC, "camera_backward.hip")).read()
-    assert "camera_backward_kernel" in src and "camera_reduce_kernel" in src and "__launch_bounds__(CB_THREADS" in src
+    assert "camera_backward_kernel" in src and "camera_reduce_kernel" in src and "__launch_bounds__(CB_THREADS)" in src
     assert "atomic" not in src.lower().replace("no atomics", "")
+    # the chain is the header's, the one project_backward.hip walks: included, its four functions called, nothing of it restated
+    chain, other = (open(os.path.join(abi.CSRC, f)).read() for f in ("splat_chain.h", "project_backward.hip"))
+    assert '#include "splat_chain.h"' in src and '#include "gauss_math.h"' in chain
+    for call in ("splat_row(", "splat_forward(", "cov2d_grad(", "mean_grad("):
+        assert call in src and call in other and re.search(rf"__device__ __forceinline__ [\w ]+\b{re.escape(call)}", chain), call
     for shared in ("cam_mean(", "cov3d_of(", "ewa_cov2d(", "cov2d_det(", "conic_of(", "clip_point(", "pixel_mean("):  # the forward's own functions
-        assert shared in src, shared
+        assert shared in chain and shared not in src, shared
+    for upstream in ("di2", "V[10]", "in_x", "gnx"):  # sigmas <- cov2d, d / d J = gT A, the clamp decision, d / d clip point: stated once
+        assert upstream in chain and upstream not in src and upstream not in other, upstream
     assert "sh_eval" not in src and "sc.sh" not in src  # no SH row is read
     assert "double acc[29]" in src and "float acc" not in src
     assert "camera_backward.hip" in open(os.path.join(abi.REPO, "tools", "kernel_resources.sh")).read()
@@ -137,6 +144,9 @@ def test_the_translation_unit_cross_compiles_for_gfx950(tmp_path):
     assert os.path.getsize(tmp_path / "camera_backward.o") > 0
     scratch = re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)
     assert len(scratch) == 2 and all(int(s) == 0 for s in scratch), out.stderr
+    # 3 waves per SIMD is what CB_MAX_GROUPS counts on; the reduction's few registers leave it all eight
+    occ = dict(re.findall(r"Function Name: _ZN3gsr\d+(\w+?_kernel)E.*?Occupancy \[waves/SIMD\]: (\d+)", out.stderr, flags=re.S))
+    assert occ == {"camera_backward_kernel": "3", "camera_reduce_kernel": "8"}, out.stderr
 
 
 def test_the_host_side_names():

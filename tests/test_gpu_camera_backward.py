@@ -183,7 +183,8 @@ def test_end_to_end(G, seed, camera):
 
 
 def test_the_translation_rows_are_the_column_sums_of_grad_means(G):
-    """camera_backward.hip restates the upstream steps of project_backward.hip: the two statements are held together here.
+    """Both kernels take gcm and gpt from ONE statement of the upstream chain (splat_chain.h); what each does with them — the
+    mean's combination in project_backward.hip, the camera's rows in camera_backward.hip — is checked here against the other.
     d cm / d mean = A^T and d cm / d w2c[3] = I, d clip / d mean = F[:3] and d clip / d F[3] = I, so the column sums of
     gsr_project_backward's grad_means are (w2c translation row) A^T + (full_proj translation row) F[:3]^T: to 1e-5 B, B the same
     combination of the camera bound's rows in absolute values plus the means' own bound summed."""

@@ -94,16 +94,24 @@ def test_the_kernel_has_a_translation_unit_of_its_own_with_the_preprocess_flags(
     rule, pre = abi.makefile_recipe("project_backward.o"), abi.makefile_recipe("preprocess.o")
     assert "-ffp-contract=off" in rule and rule.split() == pre.split()
     deps = abi.makefile_rule("project_backward.o")[0]
-    assert "gauss_math.h" in deps and "gsr_internal.h" in deps and "project_backward.hip" in deps
+    assert "gauss_math.h" in deps and "gsr_internal.h" in deps and "project_backward.hip" in deps and "splat_chain.h" in deps
     src = open(os.path.join(abi.CSRC, "project_backward.hip")).read()
-    assert "project_backward_kernel" in src and "__launch_bounds__(PB_THREADS" in src and "PB_THREADS = 256" in src
+    assert "project_backward_kernel" in src and "__launch_bounds__(PB_THREADS, 5)" in src and "PB_THREADS = 256" in src
     assert "atomic" not in src.replace("no atomics", "") and "__shared__" not in src
-    for shared in ("cov3d_of(", "ewa_cov2d(", "quat_to_rot("):  # the forward's own functions, not copies
-        assert shared in src, shared
+    # the chain is the header's: this file includes it, calls its four functions and restates none of the forward
+    chain = open(os.path.join(abi.CSRC, "splat_chain.h")).read()
+    assert '#include "splat_chain.h"' in src and '#include "gauss_math.h"' in chain
+    for call in ("splat_row(", "splat_forward(", "cov2d_grad(", "mean_grad("):
+        assert call in src and re.search(rf"__device__ __forceinline__ [\w ]+\b{re.escape(call)}", chain), call
+    for shared in ("cam_mean(", "cov3d_of(", "ewa_cov2d(", "conic_of(", "cov2d_det(", "clip_point(", "pixel_mean("):  # the forward's own functions
+        assert shared in chain and shared not in src, shared
+    assert "quat_to_rot(" in src  # (named where its transpose is written out; cov3d_of calls it)
+    holders = [f for f in sorted(os.listdir(abi.CSRC)) if f.endswith((".hip", ".h", ".inc")) and re.search(r"\bdi2\b", open(os.path.join(abi.CSRC, f)).read())]
+    assert holders == ["splat_chain.h"]  # sigmas <- cov2d opens the chain: stated in one file
 
 
 def test_the_translation_unit_cross_compiles_for_gfx950(tmp_path):
-    """With preprocess.o's flags, as csrc/Makefile spells them; the resource remarks show no scratch."""
+    """With preprocess.o's flags, as csrc/Makefile spells them; the resource remarks show no scratch and 5 waves per SIMD."""
     mk = open(os.path.join(abi.CSRC, "Makefile")).read()
     hipcc = re.search(r"^HIPCC\s*\?=\s*(\S+)", mk, flags=re.M).group(1)
     common = re.search(r"^COMMON\s*=\s*(.*)$", mk, flags=re.M).group(1).replace("$(ARCH)", "gfx950").split()
@@ -113,6 +121,7 @@ def test_the_translation_unit_cross_compiles_for_gfx950(tmp_path):
     assert os.path.getsize(tmp_path / "project_backward.o") > 0
     scratch = re.findall(r"ScratchSize \[bytes/lane\]: (\d+)", out.stderr)
     assert scratch and all(int(s) == 0 for s in scratch), out.stderr
+    assert re.findall(r"Occupancy \[waves/SIMD\]: (\d+)", out.stderr) == ["5"], out.stderr  # what its launch bounds ask for
 
 
 def test_the_host_side_names():

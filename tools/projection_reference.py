@@ -268,8 +268,9 @@ MUTANTS = ("fx_for_fy", "w2c20_dropped", "limx_for_limy")
 
 
 def fused_upstream(fw, cam, rows, dtype=torch.float32, mutant=None):
-    """The upstream quantities of the kernels' fused chain at the forward `fw`, in `dtype` (project_backward.hip forms them on the
-    way to the mean, camera_backward.hip on the way to the camera; tools/camera_reference.py reads them here): P = g + g^T of the
+    """The upstream quantities of the kernels' fused chain at the forward `fw`, in `dtype` (csrc/splat_chain.h forms them, for
+    project_backward.hip on the way to the mean and camera_backward.hip on the way to the camera, as tools/camera_reference.py reads
+    them here): P = g + g^T of the
     2x2, gT [m, 2, 3] = P (T cov3d), gJ [m, 2, 3] = gT A, gcm [m, 3], gpt [m, 4] (column 2 zero), inside [m, 2] (the ray clamp is
     not active), with V, F, A = w2c[:3, :3] (the mutant's, if any), g_op and a zero column."""
     assert mutant is None or mutant in MUTANTS

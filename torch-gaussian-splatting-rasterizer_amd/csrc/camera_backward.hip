@@ -1,9 +1,7 @@
 // camera_backward.hip — the splat gradient of a view chained to the CAMERA: d L / d w2c, full_proj, focal_x, focal_y and cam_center,
 // the raw partials in the GsrCamera fields as the kernels read them, 32 doubles (layout: include/gsr.h, gsr_camera_backward).
-// camera_backward_kernel recomputes the forward per gaussian exactly as project_backward_kernel does — the same gauss_math.h calls,
-// the same skip rule, cull, det == 0, non-finite and reference_compat exclusions, the same ray-clamp rule — builds the same upstream
-// quantities (sigmas <- cov2d, P, gT, gJ.., gcm, gpt..: restated here, project_backward.hip is left as it is) and,
-// where that kernel carries them on to the gaussian's mean, multiplies them by what the camera contributed instead.  The view
+// camera_backward_kernel walks the chain of splat_chain.h by the very functions project_backward_kernel calls and,
+// where that kernel carries gT, gJ.., gcm and gpt on to the gaussian's mean, multiplies them by what the camera contributed.  The view
 // direction's term (cam_center) is the negated column sum of grad_view_means, which gsr_sh_backward computed: no SH row is read here.
 //
 // A reduction of n gaussians into 30 numbers, deterministic and in double: the per-gaussian terms are fp32, as in the chain they
@@ -19,14 +17,12 @@
 //   - camera_reduce_kernel, one workgroup: eight contiguous runs of rows summed in row order, the eight sums in run order.
 //
 // Built with -ffp-contract=off, like preprocess.hip and project_backward.hip.  Roofline: HBM, the reads of project_backward_kernel.
-#include <cmath>
-#include "gsr_internal.h"
-#include "gauss_math.h"
+#include "splat_chain.h"
 
 namespace gsr {
 
 constexpr int CB_THREADS = 256;
-constexpr int CB_MAX_GROUPS = 768;   // 3 per CU x 256 CUs: what 136 VGPRs (3 waves per SIMD) keep resident at once, so no second round
+constexpr int CB_MAX_GROUPS = 768;   // 3 per CU x 256 CUs: what 150 VGPRs (3 waves per SIMD) keep resident at once, so no second round
 constexpr int CB_SLOTS = 32;         // doubles per row: 29 sums, the count, two zeros
 constexpr int CB_PARTS = 8;          // camera_reduce_kernel: contiguous runs of rows summed side by side
 
@@ -56,7 +52,6 @@ __global__ __launch_bounds__(CB_THREADS) void camera_backward_kernel(GsrScene sc
                                                                    const float *__restrict__ grad_view_means, double *__restrict__ rows)
 {
     __shared__ double part[CB_THREADS / 64][CB_SLOTS];
-    const float *V = cam.V, *F = cam.F;
     double acc[29];
 #pragma unroll
     for (int k = 0; k < 29; ++k) acc[k] = 0.0;
@@ -83,62 +78,19 @@ __global__ __launch_bounds__(CB_THREADS) void camera_backward_kernel(GsrScene sc
             // cam_center: d = mean - cam_center, so the row enters negated; no cull and no skip (gsr_sh_backward has none)
             acc[26] -= (double)grad_view_means[3 * i]; acc[27] -= (double)grad_view_means[3 * i + 1]; acc[28] -= (double)grad_view_means[3 * i + 2];
         }
-        const float g_mx = r0.y, g_my = r0.z, g_s0 = r0.w, g_s1 = r1.x, g_s2 = r1.y;  // columns 6 and 7 are not looked at
-        const bool touched = r0.x != 0.0f || g_mx != 0.0f || g_my != 0.0f || g_s0 != 0.0f || g_s1 != 0.0f || g_s2 != 0.0f;
+        SplatRow g;
+        const bool touched = splat_row(r0, r1, g);
         if (__ballot(touched) == 0ull) continue;  // wave-uniform: the rows and nothing else
         if (!touched) continue;
 
-        // ---- the forward, by the functions geometry_one / geometry_view call (gauss_math.h), as project_backward_kernel ------------------
-        const float p[3] = {sc.means[3 * i], sc.means[3 * i + 1], sc.means[3 * i + 2]};
-        float cm[3];
-        cam_mean(V, p, cm);
-        if (cm[2] < GSR_CULL_Z) continue;  // culled: contributes nothing
-
-        const float ls[3] = {sc.log_scales[3 * i], sc.log_scales[3 * i + 1], sc.log_scales[3 * i + 2]};
-        const float4 q = reinterpret_cast<const float4 *>(sc.quats)[i];
-        float C3[3][3], c2[4];
-        EwaKeep k2;
-        cov3d_of(ls, q, C3);
-        ewa_cov2d(V, C3, cm, cam.fx, cam.fy, cam.limx, cam.limy, c2, &k2);
-        const float a = c2[0], b01 = c2[1], b10 = c2[2], c = c2[3];
-        const float det = cov2d_det(a, b01, b10, c);
-        if (det == 0.0f) continue;
-        float sx, sy, sxy;
-        const float det_inv = conic_of(det, a, b01, c, &sx, &sy, &sxy);
-        if (!(fabsf(sx) < INFINITY) || !(fabsf(sy) < INFINITY) || !(fabsf(sxy) < INFINITY)) continue;
-        if (compat && (sx == 0.0f || sy == 0.0f || sxy == 0.0f)) continue;  // Q2: the reference's loop never draws it
-        const float (&TV)[3][3] = k2.TV;
-        const float tz = cm[2], J00 = k2.J[0][0], J02 = k2.J[0][2], J11 = k2.J[1][1], J12 = k2.J[1][2];
+        SplatForward f;
+        if (!splat_forward(sc, cam, compat, i, f)) continue;
         ++count;
-
-        // ---- the chain down to gcm and gpt.., as project_backward_kernel forms it -----------------------------------------------------------
-        const float di2 = det_inv * det_inv, bb = b10 * b01;
-        const float ga = di2 * ((-(c * c) * g_s0 - bb * g_s1) + (b01 * c) * g_s2);
-        const float gc = di2 * ((-bb * g_s0 - (a * a) * g_s1) + (b01 * a) * g_s2);
-        const float gb01 = di2 * (((c * b10) * g_s0 + (a * b10) * g_s1) - (a * c) * g_s2);
-        const float gb10 = di2 * (((c * b01) * g_s0 + (a * b01) * g_s1) - (b01 * b01) * g_s2);
-        const float P00 = 2.0f * ga, P01 = gb01 + gb10, P11 = 2.0f * gc;
-        float gT[2][3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            gT[0][k] = P00 * TV[0][k] + P01 * TV[1][k];
-            gT[1][k] = P01 * TV[0][k] + P11 * TV[1][k];
-        }
-        const float gJ00 = (gT[0][0] * V[0] + gT[0][1] * V[4]) + gT[0][2] * V[8];
-        const float gJ02 = (gT[0][0] * V[2] + gT[0][1] * V[6]) + gT[0][2] * V[10];
-        const float gJ11 = (gT[1][0] * V[1] + gT[1][1] * V[5]) + gT[1][2] * V[9];
-        const float gJ12 = (gT[1][0] * V[2] + gT[1][1] * V[6]) + gT[1][2] * V[10];
-        const bool in_x = k2.txtz > -cam.limx && k2.txtz < cam.limx, in_y = k2.tytz > -cam.limy && k2.tytz < cam.limy;
-        const float itz = 1.0f / tz;
-        float gcm[3];
-        gcm[0] = in_x ? -(gJ02 * J00) * itz : 0.0f;
-        gcm[1] = in_y ? -(gJ12 * J11) * itz : 0.0f;
-        gcm[2] = -(((gJ00 * J00 + gJ11 * J11) + (in_x ? 2.0f : 1.0f) * (gJ02 * J02)) + (in_y ? 2.0f : 1.0f) * (gJ12 * J12)) * itz;
-        float pt[4], mx, my;
-        clip_point(F, p, pt);
-        const float p_w = pixel_mean(pt, (float)cam.W, (float)cam.H, &mx, &my), pt0 = pt[0], pt1 = pt[1];
-        const float gnx = g_mx * (0.5f * (float)cam.W), gny = g_my * (0.5f * (float)cam.H);
-        const float gpt[3] = {gnx * p_w, gny * p_w, -((gnx * pt0 + gny * pt1) * p_w) * p_w};  // columns 0, 1, 3 of the clip point
+        MeanGrad m;
+        mean_grad(cam, g, f, cov2d_grad(g, f), m);
+        const float (&p)[3] = f.p, (&gT)[2][3] = m.gT, (&gcm)[3] = m.gcm, (&gpt)[3] = m.gpt;
+        const float tz = f.cm[2], J00 = f.k2.J[0][0], J02 = f.k2.J[0][2], J11 = f.k2.J[1][1], J12 = f.k2.J[1][2];
+        const float txtz = f.k2.txtz, tytz = f.k2.tytz, itz = m.itz, gJ00 = m.gJ00, gJ02 = m.gJ02, gJ11 = m.gJ11, gJ12 = m.gJ12;
 
         // ---- what the camera contributed: one fp32 term per entry, added in double ----------------------------------------------------------
         // w2c rows 0..2: cm[j] = sum_k p[k] V[4 k + j] + V[12 + j], and T[r][c] = sum_m V[4 c + m] J[r][m] with J's four entries
@@ -157,7 +109,7 @@ __global__ __launch_bounds__(CB_THREADS) void camera_backward_kernel(GsrScene sc
             acc[21 + j] += (double)gpt[j];
         }
         // focal: J00 = fx / z and J02 = -fx t_x / z^2 are linear in fx (t_x = clamp(x / z) z, the forward's: lim_x is held fixed)
-        const float tx = fminf(cam.limx, fmaxf(-cam.limx, k2.txtz)) * tz, ty = fminf(cam.limy, fmaxf(-cam.limy, k2.tytz)) * tz;
+        const float tx = fminf(cam.limx, fmaxf(-cam.limx, txtz)) * tz, ty = fminf(cam.limy, fmaxf(-cam.limy, tytz)) * tz;
         const float itz2 = 1.0f / (tz * tz);
         acc[24] += (double)(gJ00 * itz + gJ02 * (-tx * itz2));
         acc[25] += (double)(gJ11 * itz + gJ12 * (-ty * itz2));

@@ -489,6 +489,13 @@ def _geometry_out(scene: "GaussianScene", out: Optional[GeometryGradient], scene
     return _PerGaussianOut(scene, fields, out, scene_order, zeroed=True)
 
 
+def _project_backward_into(scene: "GaussianScene", cam: GsrCamera, opts: GsrOptions, splat_rows: torch.Tensor, ptrs) -> None:
+    """One gsr_project_backward on the scene's stream: added into the four outputs that are not None."""
+    sc = scene.c_struct()
+    with torch.cuda.device(scene.device):
+        check(lib.gsr_project_backward(C.byref(sc), C.byref(cam), C.byref(opts), splat_rows.data_ptr(), *ptrs, _stream_ptr(scene.device)))
+
+
 def project_backward(scene: "GaussianScene", cam: GsrCamera, splat_rows: torch.Tensor, opts: Optional[GsrOptions] = None,
                      out: Optional[GeometryGradient] = None, scene_order: bool = False) -> GeometryGradient:
     """The splat gradient of a view chained through the preprocess' projection to the scene's own parameters
@@ -509,9 +516,7 @@ def project_backward(scene: "GaussianScene", cam: GsrCamera, splat_rows: torch.T
     _check_tensor("splat_rows", splat_rows, (scene.n, 8), torch.float32, scene.device)
     res = _geometry_out(scene, out, scene_order)
     if scene.n:
-        opts, sc = opts or make_options(), scene.c_struct()
-        with torch.cuda.device(scene.device):
-            check(lib.gsr_project_backward(C.byref(sc), C.byref(cam), C.byref(opts), splat_rows.data_ptr(), *res.ptrs, _stream_ptr(scene.device)))
+        _project_backward_into(scene, cam, opts or make_options(), splat_rows, res.ptrs)
     return out if out is not None else GeometryGradient(*res.result())
 
 
@@ -1096,6 +1101,21 @@ class Rasterizer:
         return res.result()[0]
 
     # -- the gradient of a feature map with respect to opacity and the 2-D splat ----------------------------------------------------
+    def _upstream(self, cam: GsrCamera, opts: GsrOptions, name: str, grad_map: torch.Tensor, channels: int, grad_T, min_T: float):
+        """The upstream arguments of splat_gradient, colour_gradient and camera_gradient (each has looked at where the map lives),
+        checked in this order — the map against the frame's shape with `channels`, grad_T, min_T — and handed back detached, float32
+        and contiguous: (gm, gt or None); (None, None) when there is nothing to draw or the shard owns no tile row: no copy is made."""
+        shape, tshape = self._out_shape(cam, opts)
+        _check_tensor(name, grad_map, tuple(shape[:2]) + (channels,), None, self.scene.device, "any")
+        if grad_T is not None:
+            _check_tensor("grad_T", grad_T, tshape, None, self.scene.device, "any", " (the layout of the final T)")
+        if not (float(min_T) >= 0.0 and float(min_T) < float("inf")):
+            raise ValueError(f"min_T must be finite and >= 0, got {min_T}")
+        if not (self.scene.n and grad_map.numel()):
+            return None, None
+        return (grad_map.detach().to(torch.float32).contiguous(),
+                grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None)
+
     def splat_gradient(self, cam: GsrCamera, features: torch.Tensor, grad_map: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
                        opts: Optional[GsrOptions] = None, min_T: float = 0.0, abs_mean: bool = False,
                        out: Optional[torch.Tensor] = None, scene_order: bool = False) -> SplatGradient:
@@ -1117,23 +1137,15 @@ class Rasterizer:
         SplatGradient returned holds views of it, in the scene's order: stages 1-2 are checked and re-run first and only then does
         the blend add.  Float atomic sums may differ in the last bits between two calls."""
         opts = opts or make_options()
-        dev = self.scene.device
         self._check_features(features, _lib.GSR_MAX_FEATURE_CHANNELS)
         n_ch = int(features.shape[1])
         _require_cuda(grad_map, "grad_map")
-        shape, tshape = self._out_shape(cam, opts)
-        _check_tensor("grad_map", grad_map, tuple(shape[:2]) + (n_ch,), None, dev, "any")
-        if grad_T is not None:
-            _check_tensor("grad_T", grad_T, tshape, None, dev, "any", " (the layout of the final T)")
-        if not (float(min_T) >= 0.0 and float(min_T) < float("inf")):
-            raise ValueError(f"min_T must be finite and >= 0, got {min_T}")
+        gm, gt = self._upstream(cam, opts, "grad_map", grad_map, n_ch, grad_T, min_T)
         if abs_mean and n_ch > 16:
             raise ValueError(f"abs_mean takes at most 16 channels (the absolute sums are not linear in them), got {n_ch}")
-        drawn = self.scene.n != 0 and grad_map.numel() != 0  # else nothing to draw, or a shard that owns no tile row
+        drawn = gm is not None  # else nothing to draw, or a shard that owns no tile row
         res = _PerGaussianOut(self.scene, [("out", (8,), torch.float32, True)], out, scene_order, zeroed=not drawn)
         if drawn:
-            gm = grad_map.detach().to(torch.float32).contiguous()
-            gt = grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None
             rows = self._feature_rows(features.detach(), scene_order)
             self._accumulate_view(cam, opts, "splat gradient", res.own, lib.gsr_render_splat_backward, lib.gsr_blend_splat_backward,
                                   rows.data_ptr(), int(rows.stride(0)), n_ch, gm.data_ptr(), gt.data_ptr() if gt is not None else None,
@@ -1154,12 +1166,9 @@ class Rasterizer:
         `out` (project_backward's: tensors in the SCENE's order, None = not computed) the view's gradient is ACCUMULATED into it, as
         feature_gradient(out=) does: a camera set is one call per view.  The splat gradient's float atomic sums may differ in the
         last bits between two calls; the projection adds nothing to that."""
-        n, dev = self.scene.n, self.scene.device
         if out is not None:
             _geometry_out(self.scene, out, scene_order)  # refused before the splat gradient runs, not after
-        if self._splat_rows is None or tuple(self._splat_rows.shape) != (n, 8):
-            self._splat_rows = torch.empty((n, 8), dtype=torch.float32, device=dev)
-        rows = self._splat_rows.zero_()
+        rows = self._zeroed_scratch("_splat_rows", 8)
         self.splat_gradient(cam, features, grad_map, grad_T, opts, min_T, abs_mean=False, out=rows, scene_order=scene_order)
         return project_backward(self.scene, cam, rows, opts, out, scene_order)
 
@@ -1171,6 +1180,20 @@ class Rasterizer:
             buf = torch.empty((self.scene.n, cols), dtype=torch.float32, device=self.scene.device)
             setattr(self, name, buf)
         return buf.zero_()
+
+    def _gradient_rows(self, cam: GsrCamera, opts: GsrOptions, what: str, feats: torch.Tensor, gm: torch.Tensor, gt, min_T: float, colour: bool):
+        """A view's gradient rows over ONE pair of stages 1-2, checked and re-run like any frame: with `colour` the feature gradient of
+        the three-channel map (gsr_blend_channels_backward) into the zeroed [n, 4] scratch `_colour_rows`, then the splat gradient
+        under the features `feats` (gsr_blend_splat_backward) into the zeroed [n, 8] scratch `_splat_rows`.  (colour rows or None,
+        splat rows)."""
+        g_rgb = self._zeroed_scratch("_colour_rows", 4) if colour else None
+        rows = self._zeroed_scratch("_splat_rows", 8)
+        o = self._checked_lists(cam, opts, what)
+        if colour:
+            self._blend_lists(cam, o, lib.gsr_blend_channels_backward, gm.data_ptr(), 3, g_rgb.data_ptr(), 4)
+        self._blend_lists(cam, o, lib.gsr_blend_splat_backward, feats.data_ptr(), int(feats.stride(0)), int(feats.shape[1]), gm.data_ptr(),
+                          gt.data_ptr() if gt is not None else None, float(min_T), 0, rows.data_ptr())
+        return g_rgb, rows
 
     def colour_gradient(self, cam: GsrCamera, grad_image: torch.Tensor, grad_T: Optional[torch.Tensor] = None,
                         opts: Optional[GsrOptions] = None, min_T: float = 0.0, out: Optional[SceneGradient] = None,
@@ -1190,28 +1213,14 @@ class Rasterizer:
         is ACCUMULATED into it, as geometry_gradient(out=) does: a camera set is one call per view.  The blends' float atomic sums
         may differ in the last bits between two calls; the projection and the SH transpose add nothing to that."""
         opts = opts or make_options()
-        scene, dev = self.scene, self.scene.device
+        scene = self.scene
         _require_cuda(grad_image, "grad_image")
-        shape, tshape = self._out_shape(cam, opts)
-        _check_tensor("grad_image", grad_image, tuple(shape), None, dev, "any")
-        if grad_T is not None:
-            _check_tensor("grad_T", grad_T, tshape, None, dev, "any", " (the layout of the final T)")
-        if not (float(min_T) >= 0.0 and float(min_T) < float("inf")):
-            raise ValueError(f"min_T must be finite and >= 0, got {min_T}")
+        gm, gt = self._upstream(cam, opts, "grad_image", grad_image, 3, grad_T, min_T)
         res = _gradient_out(scene, SceneGradient, out, scene_order)  # refused before anything runs, not after
-        if scene.n and grad_image.numel():  # else nothing to draw, or a shard that owns no tile row: the gradient is zero
-            gm = grad_image.detach().to(torch.float32).contiguous()
-            gt = grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None
-            rgb = self._view_colours(cam)
-            g_rgb, rows = self._zeroed_scratch("_colour_rows", 4), self._zeroed_scratch("_splat_rows", 8)
-            o = self._checked_lists(cam, opts, "colour gradient")
-            self._blend_lists(cam, o, lib.gsr_blend_channels_backward, gm.data_ptr(), 3, g_rgb.data_ptr(), 4)
-            self._blend_lists(cam, o, lib.gsr_blend_splat_backward, rgb.data_ptr(), 3, 3, gm.data_ptr(),
-                              gt.data_ptr() if gt is not None else None, float(min_T), 0, rows.data_ptr())
-            sc = scene.c_struct()
+        if gm is not None:  # else nothing to draw, or a shard that owns no tile row: the gradient is zero
+            g_rgb, rows = self._gradient_rows(cam, opts, "colour gradient", self._view_colours(cam), gm, gt, min_T, colour=True)
             if any(p is not None for p in res.ptrs[:4]):
-                with torch.cuda.device(dev):
-                    check(lib.gsr_project_backward(C.byref(sc), C.byref(cam), C.byref(opts), rows.data_ptr(), *res.ptrs[:4], _stream_ptr(dev)))
+                _project_backward_into(scene, cam, opts, rows, res.ptrs[:4])
             if res.ptrs[4] is not None or (res.ptrs[0] is not None and scene.sh_degree > 0):
                 _sh_backward_into(scene, cam, g_rgb, res.ptrs[4], res.ptrs[0])
         return out if out is not None else SceneGradient(*res.result())
@@ -1232,36 +1241,17 @@ class Rasterizer:
         workspace are kept on this Rasterizer.  The blends' float atomic sums may differ in the last bits between two calls; the
         camera reduction adds nothing to that (double sums in a fixed order)."""
         opts = opts or make_options()
-        scene, dev = self.scene, self.scene.device
+        scene = self.scene
         _require_cuda(grad_image, "grad_image")
-        shape, tshape = self._out_shape(cam, opts)
         if features is not None:
             self._check_features(features, _lib.GSR_MAX_FEATURE_CHANNELS)
-            shape = tuple(shape[:2]) + (int(features.shape[1]),)
-        _check_tensor("grad_image", grad_image, tuple(shape), None, dev, "any")
-        if grad_T is not None:
-            _check_tensor("grad_T", grad_T, tshape, None, dev, "any", " (the layout of the final T)")
-        if not (float(min_T) >= 0.0 and float(min_T) < float("inf")):
-            raise ValueError(f"min_T must be finite and >= 0, got {min_T}")
+        gm, gt = self._upstream(cam, opts, "grad_image", grad_image, 3 if features is None else int(features.shape[1]), grad_T, min_T)
         self._camera_ws = _camera_workspace(scene, getattr(self, "_camera_ws", None))
-        rows = self._zeroed_scratch("_splat_rows", 8)
-        if not (scene.n and grad_image.numel()):  # nothing to draw, or a shard that owns no tile row: the gradient is zero
-            return _camera_gradient_of(torch.zeros(32, dtype=torch.float64, device=dev))
-        gm = grad_image.detach().to(torch.float32).contiguous()
-        gt = grad_T.detach().to(torch.float32).contiguous() if grad_T is not None else None
+        if gm is None:  # nothing to draw, or a shard that owns no tile row: the gradient is zero
+            return _camera_gradient_of(torch.zeros(32, dtype=torch.float64, device=scene.device))
+        feats = self._view_colours(cam) if features is None else self._feature_rows(features.detach(), scene_order)
+        g_rgb, rows = self._gradient_rows(cam, opts, "camera gradient", feats, gm, gt, min_T, colour=features is None)
         view_rows = None
-        o = None
-        if features is None:
-            rgb, n_ch, stride = self._view_colours(cam), 3, 3
-            g_rgb = self._zeroed_scratch("_colour_rows", 4)
-            o = self._checked_lists(cam, opts, "camera gradient")
-            self._blend_lists(cam, o, lib.gsr_blend_channels_backward, gm.data_ptr(), 3, g_rgb.data_ptr(), 4)
-        else:
-            rgb = self._feature_rows(features.detach(), scene_order)
-            n_ch, stride = int(rgb.shape[1]), int(rgb.stride(0))
-            o = self._checked_lists(cam, opts, "camera gradient")
-        self._blend_lists(cam, o, lib.gsr_blend_splat_backward, rgb.data_ptr(), stride, n_ch, gm.data_ptr(),
-                          gt.data_ptr() if gt is not None else None, float(min_T), 0, rows.data_ptr())
         if features is None and scene.sh_degree > 0:
             view_rows = self._zeroed_scratch("_view_mean_rows", 3)
             _sh_backward_into(scene, cam, g_rgb, None, view_rows.data_ptr())
