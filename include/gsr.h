@@ -157,7 +157,21 @@ typedef struct GsrOptions {
                                  shrinks).  Pixels the reference never draws (Q1) count as finished.  Frames are bit-identical to rule 1;
                                  ~4x fewer evaluated entries on the bench frame.  When out_final_T is requested rule 1 applies (T itself
                                  is then an output and keeps shrinking).
-                                 1: once T has underflowed to 0.0f for all 64 pixels (rounds 1-3) — the A/B reference of rule 0. */
+                                 1: once T has underflowed to 0.0f for all 64 pixels (rounds 1-3) — the A/B reference of rule 0.
+                                 3, 4: rule 0 with the FRONT SLICE forced on / switched off (tests, A/B timing; 2 is refused).  The front
+                                 slice is how gsr_render_forward / gsr_render_batch / gsr_render_batch_slots build a whole colour frame
+                                 of a large scene under rule 0 (coarse binning, no shard, draw_limit = 0, early_out_T = 0, fp32
+                                 accumulators, blend_impl = 0, no out_final_T; by plan: from 3000 tiles, 6 000 000 gaussians and SIX views per launch
+                                 sequence on — one view alone is faster in one pass, so gsr_render_forward slices only when forced): the
+                                 nearest eighth of the draw order is binned and blended first, the rest is binned and sorted only
+                                 where a tile is still open after it, and blended on from the stored fp32 T and colour sums.  Same
+                                 bits as the single pass (csrc/binning.hip has the argument).  Its planes (16 B per pixel) lie over the
+                                 workspace's depth keys and unpacked rects, which need ~257 gaussians per tile: rule 0 builds a scene
+                                 below that in one pass, rule 3 refuses it (GSR_ERR_BAD_ARG).  After such a frame the depth keys are
+                                 gone and the lists in the workspace are the second slice's remainder, not the frame's: a gsr_bin_sort
+                                 there needs a gsr_preprocess first, and a stage-3 entry over the workspace's lists needs both (see
+                                 gsr_render_forward).
+                                 1 never slices; the staged calls and every list consumer never do either: their lists are complete. */
     int32_t fine_binning;     /* 0 (default): (gaussian, 32x32 cell) pairs whenever the frame allows (<= 4096 px, n <= 2^28), the blend filters
                                  the cell lists by tile.  1: (gaussian, 16x16 tile) pairs — the path wider frames always take; A/B timing and
                                  the test that both build the same frame (csrc/binning.hip).  Was GSR_FINE_BINNING. */
@@ -196,10 +210,13 @@ typedef struct GsrStats {
     uint32_t n_visible;     /* V: gaussians that survive cull and have a non-empty footprint */
     uint32_t n_pairs_bbox;  /* D: pair slots this frame needs, i.e. what max_pairs must cover: (gaussian, 32x32 cell) pairs of the
                                visible gaussians' rects (frames wider than 4096 px: (gaussian, 16x16 tile) pairs of this shard) */
-    uint32_t n_pairs;       /* E: entries of the per-tile lists the blend consumes (this shard; after footprint culling) */
+    uint32_t n_pairs;       /* E: entries of the per-tile lists the blend consumes (this shard; after footprint culling).  A front-slice
+                               frame (GsrOptions.saturation_rule): the entries actually EMITTED — those of tiles already finished when
+                               the second slice is binned are not; D above stays what the whole draw order needs */
     uint32_t overflow;      /* bit 0: D exceeded max_pairs (frame incomplete); bit 1: the depth sort needed more passes than
                                depth_sort_passes allowed (frame wrong) */
-    uint32_t max_list_len;  /* longest list a blend workgroup walks: per 32x32 cell (frames wider than 4096 px: per 16x16 tile) */
+    uint32_t max_list_len;  /* longest list a blend workgroup walks: per 32x32 cell (frames wider than 4096 px: per 16x16 tile; a
+                               front-slice frame: per cell and slice) */
     uint32_t sort_passes;   /* radix passes the depth sort of this frame needs (1..4): the bound to pass as depth_sort_passes.  When
                                overflow bit 1 is set: the most any frame since the last cleared one (keep_flags, batches) needed */
     uint64_t wave_entries;  /* (8x8 quadrant, entry) pairs the blend actually evaluated: 64 pixel evaluations each */
@@ -269,7 +286,15 @@ int gsr_blend(const GsrScene *scene /* may be NULL */, int64_t n, const GsrCamer
               void *workspace, size_t workspace_bytes, void *out_image /* float32 or bfloat16, opts->output_dtype */,
               float *out_final_T, void *stream);
 
-/* Stages 1-3 back to back: the whole render call of rasterize.py:354-446. */
+/* Stages 1-3 back to back: the whole render call of rasterize.py:354-446.
+ * WHAT IT LEAVES IN THE WORKSPACE.  This entry, gsr_render_batch and gsr_render_batch_slots owe the caller the frame and the counters,
+ * NOT the frame's lists: when the plan takes the front slice (GsrOptions.saturation_rule; by default gsr_render_batch of six or more
+ * views of a whole 1080p-class frame of a scene of 6 000 000 gaussians or more) the lists left behind are the second slice's remainder — the far seven eighths of the draw order,
+ * without the gaussians and tile bits of tiles that had finished — and the depth keys are overwritten.  A stage-3 entry that walks the
+ * workspace's lists (a second gsr_blend, gsr_blend_features / _channels / _pick / _topk / _slab / _gaussian_stats, the backward
+ * blends) must therefore follow gsr_preprocess + gsr_bin_sort (or a gsr_render_X / gsr_lists_views of its own kind), never one of the
+ * three fused colour-frame entries: nothing on the host can see the difference, and the maps would be built from partial lists without
+ * an error.  saturation_rule = 4 restores the old behaviour (complete lists after the fused entries) at the single pass's speed. */
 int gsr_render_forward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs,
                        void *workspace, size_t workspace_bytes, void *out_image, float *out_final_T, void *stream);
 

@@ -70,6 +70,26 @@ size_t carve_workspace(void *base, int64_t n, int width, int height, int64_t max
     ws->tile_order = static_cast<int *>(take(sizeof(int) * order_slots));
     ws->blend_stats = static_cast<uint32_t *>(take(sizeof(uint32_t) * BLEND_STAT_WORDS * order_slots));
     ws->tile_work = static_cast<uint32_t *>(take(sizeof(uint32_t) * (size_t)ws->tiles_x * ws->tiles_y));
+    // The front slice (plan_frame) takes no bytes of its own: its planes and tables lie over per-gaussian arrays that nobody reads
+    // between the depth sort and the next preprocess on the coarse path — rect[] (the rect travels packed, in rect8[]) and the
+    // depth keys key[0], key[1] (the sort has consumed them).  16 B per pixel of the frame, in two halves: a scene of fewer than
+    // ~257 gaussians per tile has no room for them, and front_fits says so.
+    {
+        const size_t tiles = (size_t)ws->tiles_x * ws->tiles_y, cells = (size_t)ws->ctiles_x * ws->ctiles_y;
+        const size_t half = align_up(sizeof(float4) * 128 * tiles, 256);
+        char *r1 = reinterpret_cast<char *>(ws->rect), *r2 = reinterpret_cast<char *>(ws->key[0]);
+        const size_t r1_bytes = sizeof(ushort4) * nn, r2_bytes = align_up(4 * nn, 256) + 4 * nn;  // (key[1] follows key[0])
+        const bool adjacent = !p || reinterpret_cast<char *>(ws->key[1]) == r2 + align_up(4 * nn, 256);  // gsr_internal.h, the contract at key[]
+        size_t o1 = 0, o2 = 0;
+        auto over = [](char *r, size_t &o, size_t bytes) { char *q = r ? r + o : nullptr; o = (o + bytes + 255) / 256 * 256; return q; };
+        ws->front_acc[0] = reinterpret_cast<float4 *>(over(r1, o1, half));
+        ws->front_acc[1] = reinterpret_cast<float4 *>(over(r2, o2, half));
+        ws->tile_open = reinterpret_cast<unsigned char *>(over(r1, o1, tiles));
+        ws->cell_open = reinterpret_cast<unsigned char *>(over(r1, o1, cells));
+        ws->open_sum = reinterpret_cast<uint32_t *>(over(r1, o1, 4 * (size_t)(ws->ctiles_x + 1) * (ws->ctiles_y + 1)));
+        ws->blk_full = reinterpret_cast<uint32_t *>(over(r2, o2, 4 * ((nn + EMIT_THREADS - 1) / EMIT_THREADS + 4)));
+        ws->front_fits = adjacent && ws->tiles_x <= 256 && ws->tiles_y <= 256 && o1 <= r1_bytes && o2 <= r2_bytes;
+    }
 
     ws->pair_off = nullptr;
     ws->bytes = off;
@@ -107,7 +127,7 @@ static int check_frame(int64_t n, const GsrCamera *cam, const GsrOptions *opts, 
     if (opts->depth_sort_passes < 0 || opts->depth_sort_passes > 4) { set_error("bad depth_sort_passes %d", opts->depth_sort_passes); return GSR_ERR_BAD_ARG; }
     if (opts->accum_dtype != 0 && opts->accum_dtype != 1) { set_error("bad accum_dtype %d", opts->accum_dtype); return GSR_ERR_BAD_ARG; }
     if (opts->keep_flags != 0 && opts->keep_flags != 1) { set_error("bad keep_flags %d", opts->keep_flags); return GSR_ERR_BAD_ARG; }
-    if (opts->saturation_rule != 0 && opts->saturation_rule != 1) { set_error("bad saturation_rule %d", opts->saturation_rule); return GSR_ERR_BAD_ARG; }
+    if (opts->saturation_rule != 0 && opts->saturation_rule != 1 && opts->saturation_rule != 3 && opts->saturation_rule != 4) { set_error("bad saturation_rule %d", opts->saturation_rule); return GSR_ERR_BAD_ARG; }
     if (opts->fine_binning != 0 && opts->fine_binning != 1) { set_error("bad fine_binning %d", opts->fine_binning); return GSR_ERR_BAD_ARG; }
     if (opts->shard_preprocess < 0 || opts->shard_preprocess > 2) { set_error("bad shard_preprocess %d", opts->shard_preprocess); return GSR_ERR_BAD_ARG; }
     if (opts->blend_pipe_tiles < -1) { set_error("bad blend_pipe_tiles %d", opts->blend_pipe_tiles); return GSR_ERR_BAD_ARG; }
@@ -139,8 +159,15 @@ constexpr int BLEND_HALF_MIN_TILES = GSR_BLEND_HALF_MIN_TILES;  // (the macro: t
 // the pipelined one-quadrant walk (96 VGPRs: 5 waves per SIMD = 1280 four-wave workgroups resident) up to this many tiles per launch;
 // GsrOptions.blend_pipe_tiles overrides it (experiments and tests: -1 switches the variant off)
 constexpr int BLEND_PIPE_MAX_TILES = 1280;
+// The front slice (FramePlan.front_slice) by plan: from this many gaussians and this many views per launch sequence on.  Both from the
+// sweep of profiles/front_slice_sweeps.txt (1080p, forced on against off, one stream): the second round of 13 dispatches is paid
+// per launch sequence and the spared pair work per view and per gaussian the first slice hides — at 6 views 2^21 gaussians are 22 %
+// slower sliced, 5.0 M 2.5 % slower, 6.13 M 0.8 % faster (+3.9 % in bench.py's three batches in flight); at 4 views and at 1 every size
+// up to 6.13 M is slower.  So: only what was measured to win
+constexpr int FRONT_SLICE_MIN_VIEWS = 6;
+constexpr int64_t FRONT_SLICE_MIN_N = 6000000;
 
-FramePlan plan_frame(const Workspace &ws, const GsrOptions &opts)
+FramePlan plan_frame(const Workspace &ws, const GsrOptions &opts, bool colour_frame)
 {
     FramePlan p;
     // ---- stage 1.  The tile rect packs into 32 bits when the tile grid fits 8 bits per coordinate (frames up to 4096 px): the
@@ -195,6 +222,18 @@ FramePlan plan_frame(const Workspace &ws, const GsrOptions &opts)
             : opts.blend_impl == 1 ? BlendKernel::Tile
             : launch_tiles >= BLEND_HALF_MIN_TILES ? BlendKernel::Walk2
             : launch_tiles <= pipe_max_tiles ? BlendKernel::Walk1Pipe : BlendKernel::Walk1;
+    // ---- the front slice.  A whole colour frame under the exact colour-saturation rule, binned by cells and blended by the product
+    // walk: the nearest eighth of the draw order finishes most tiles (bench frame: 61 % of the cells), and the rest of the order is
+    // then binned and sorted only where a tile is still open.  It pays where binning the whole order costs more than a second round
+    // of launches: frames of Walk2 size over scenes of FRONT_SLICE_MIN_N gaussians.  saturation_rule 3 forces it on whatever the two
+    // sizes say, 4 switches it off (tests, A/B).  A sliced frame is blended by the two-quadrant walk, the one kernel that knows how.
+    const bool sliceable = colour_frame && p.coarse && opts.tile_row_step <= 1 && opts.draw_limit == 0 && opts.early_out_T == 0.0f &&
+                           opts.accum_dtype == 0 && opts.blend_impl == 0 && (opts.saturation_rule == 0 || opts.saturation_rule == 3);
+    // (forced where its planes have no room — carve_workspace, front_fits — the frame is refused by render_views, not quietly built whole)
+    // (the two measured thresholds: above, at their definitions)
+    p.front_slice = sliceable && (opts.saturation_rule == 3 || (ws.front_fits && ws.views >= FRONT_SLICE_MIN_VIEWS &&
+                                                                p.rows * ws.tiles_x >= BLEND_HALF_MIN_TILES && ws.n >= FRONT_SLICE_MIN_N));
+    if (p.front_slice) p.blend = BlendKernel::Walk2;
     return p;
 }
 
@@ -459,14 +498,29 @@ static int render_views(const GsrScene *scene, const GsrCamera *cams, int views,
     Workspace ws;
     rc = check_view_slices(scene->n, cams, views, opts, max_pairs, workspace, workspace_bytes, &ws);
     if (rc) return rc;
-    const FramePlan plan = plan_frame(ws, *opts);
+    const FramePlan plan = plan_frame(ws, *opts, out_final_T == nullptr);
+    if (plan.front_slice && !ws.front_fits) {
+        set_error("saturation_rule 3: no room for the front slice's planes (%lld gaussians, %d tiles: 257 gaussians per tile hold them)",
+                  (long long)ws.n, ws.tiles_x * ws.tiles_y);
+        return GSR_ERR_BAD_ARG;
+    }
     hipStream_t s = static_cast<hipStream_t>(stream);
     rc = launch_preprocess(*scene, cams, *opts, ws, plan, nullptr, reset_words_of(opts, keep_batch_words), s);
     if (rc) return rc;
-    rc = bin_sort_impl(opts, ws, plan, s);
-    if (rc) return rc;
     // (the blend finds the scene through what the preprocess above left in each view's control block: same call, same arrays)
-    return launch_blend(cams[0], *opts, ws, plan, out_images, out_view_stride, out_final_T, nullptr, s);
+    if (!plan.front_slice) {
+        rc = bin_sort_impl(opts, ws, plan, s);
+        if (rc) return rc;
+        return launch_blend(cams[0], *opts, ws, plan, out_images, out_view_stride, out_final_T, nullptr, s);
+    }
+    // the front slice (binning.hip): one depth sort; bin and blend the nearest ranks; bin the rest where a tile is still open, blend on
+    rc = launch_depth_sort(ws, plan, s);
+    for (int slice = 1; slice <= 2 && !rc; ++slice) {
+        if (slice == 2) rc = launch_open_cells(ws, s);
+        if (!rc) rc = launch_binning(*opts, ws, plan, s, slice);
+        if (!rc) rc = launch_blend(cams[0], *opts, ws, plan, out_images, out_view_stride, nullptr, nullptr, s, slice);
+    }
+    return rc;
 }
 
 int gsr_render_forward(const GsrScene *scene, const GsrCamera *cam, const GsrOptions *opts, int64_t max_pairs,

@@ -100,23 +100,66 @@ __device__ __forceinline__ ushort4 sorted_of(uint32_t r, const uint32_t *sorted_
     return COARSE ? coarse_rect(rc) : rc;
 }
 
+// ---- the front slice (FramePlan.front_slice) -------------------------------------------------------------------------------------
+// A whole colour frame under the exact colour-saturation rule is built in two rounds of the kernels below and of the blend:
+//   slice A   count, scan, emit, cell sort, ranges, order and blend for the ranks [0, L) of the draw order, L = ceil(V / 8).  The
+//             blend stores every tile's colour as ever; a tile whose list ends with a quadrant still live (blend.hip) also leaves its
+//             pixels' T and colour sums, the fp32 values its registers held, in front_acc[] and sets tile_open[tile];
+//   between   open_cells_kernel: a 32x32 cell is open when a tile of it is; cell_open[] holds the tiles' bits, open_sum[] the 2-D prefix
+//             sums of the open cells;
+//   slice B   the same kernels for the ranks [L, V): a gaussian whose cell rect holds no open cell counts no pair (four loads of
+//             open_sum[] say so); the others emit their rect with the bits of closed tiles cleared from every pair's mask, and a pair
+//             left without a bit takes the culled key, which the cell sort's first pass drops.  Closed tiles get an empty launch slot; an open
+//             tile's blend starts from the stored T and sums and stores the final colour.
+// Why the frame is the single pass's bit for bit: per pixel, the entries of slice A followed by those of slice B are the pixel's full
+// list in the same order, and T and the sums cross the boundary as the fp32 values the registers held.  A pixel finished by the
+// colour-saturation rule is changed by no later entry (blend_args.h, pixel_finished), so a tile whose pixels are all finished loses
+// nothing when its later pairs are never emitted; a mask bit is cleared only for such a tile, and a gaussian is skipped only when
+// every tile it reaches is one.  Counters of the blend may differ by whole 64-entry chunks: saturation is tested per chunk, and
+// slice B's chunks start at the boundary.
+// SLICE (template parameter of the kernels): 0 = the whole draw order, as every other path runs them; 1 = slice A; 2 = slice B.
+template <int SLICE>
+__device__ __forceinline__ void slice_ranks(uint32_t n, uint32_t draw_limit, uint32_t *lo, uint32_t *hi)
+{
+    const uint32_t lim = n < draw_limit ? n : draw_limit;
+    const uint32_t L = min(lim, (n + FRONT_SLICE_FRACTION - 1u) / FRONT_SLICE_FRACTION);
+    *lo = SLICE == 2 ? L : 0u;
+    *hi = SLICE == 1 ? L : lim;
+}
+// slice B's first emit block, rounded down to four: the scan reads the blocks' sums 16 B at a time (slice A's ranks in them count 0)
+template <int SLICE>
+__device__ __forceinline__ uint32_t slice_first_block(uint32_t lo)
+{
+    return SLICE == 2 ? (lo / EMIT_THREADS) & ~3u : 0u;
+}
+// does the cell rect hold an open cell?  (os_x = ctiles_x + 1: the row stride of open_sum[]; the rect lies inside the cell grid)
+__device__ __forceinline__ bool any_open_cell(ushort4 rc, const uint32_t *__restrict__ open_sum, int os_x)
+{
+    if (rc.z <= rc.x || rc.w <= rc.y) return false;
+    const uint32_t a = open_sum[rc.w * os_x + rc.z], b = open_sum[rc.y * os_x + rc.z], c = open_sum[rc.w * os_x + rc.x], d = open_sum[rc.y * os_x + rc.x];
+    return a + d != b + c;
+}
+
 // One WAVE per emit block (EMIT_THREADS = 256 consecutive gaussians of the draw order): a lane takes four consecutive gaussians
 // (PACKED: one 16-B load of four packed rects), the wave sums its 256 counts with shuffles — no LDS, no barrier — and a workgroup
 // covers four emit blocks.  (Round 1-3: one workgroup per emit block with a block scan, 13 K workgroups of almost no work each:
 // 15 us for 13 MB; this form: 4x fewer workgroups, nothing to wait for.)
 constexpr int COUNT_BLOCKS_PER_WG = EMIT_THREADS / 64;  // emit blocks per count workgroup
 static_assert(EMIT_THREADS == 256, "a lane of the count kernel takes EMIT_THREADS / 64 = 4 gaussians: one uint4 of packed rects");
-template <bool PACKED, bool COARSE>
+template <bool PACKED, bool COARSE, int SLICE>
 __global__ __launch_bounds__(EMIT_THREADS) void pair_count_kernel(const uint32_t *__restrict__ id_a, const uint32_t *__restrict__ id_b,
                                                                   const uint2 *__restrict__ pay_a, const uint2 *__restrict__ pay_b,
                                                                   const FrameCtrl *ctrl, const ushort4 *__restrict__ rect, RowShard sh,
                                                                   uint32_t *__restrict__ blk_sum, uint2 *__restrict__ ranges,
                                                                   int n_tiles, uint32_t draw_limit, uint2 *__restrict__ cranges, int n_ctiles,
-                                                                  FrameCtrl *ctrl_w, uint32_t ent_off, int nblk_n, int grid_wgs, size_t vstride)
+                                                                  FrameCtrl *ctrl_w, uint32_t ent_off, int nblk_n, int grid_wgs, size_t vstride,
+                                                                  const uint32_t *__restrict__ open_sum, int os_x, uint32_t *__restrict__ blk_full)
 {
+    static_assert(SLICE == 0 || (PACKED && COARSE), "the front slice bins by cells");
     id_a = view_slice(id_a, vstride); id_b = view_slice(id_b, vstride); pay_a = view_slice(pay_a, vstride); pay_b = view_slice(pay_b, vstride);
     ctrl = view_slice(ctrl, vstride); rect = view_slice(rect, vstride); blk_sum = view_slice(blk_sum, vstride); ranges = view_slice(ranges, vstride);
     cranges = view_slice(cranges, vstride); ctrl_w = view_slice(ctrl_w, vstride);
+    if (SLICE == 2) { open_sum = view_slice(open_sum, vstride); blk_full = view_slice(blk_full, vstride); }
     const uint32_t n = ctrl->n_visible;
     const uint32_t t = blockIdx.x * EMIT_THREADS + threadIdx.x;
     // threads in the grid (not gridDim.x: that would pull in the hidden kernarg block)
@@ -130,40 +173,60 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_count_kernel(const uint32_t
     const uint32_t *sorted_ids = odd ? id_b : id_a;  // PACKED: not read
     const uint2 *sorted_pay = odd ? pay_b : pay_a;   // else: not read
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t lim = n < draw_limit ? n : draw_limit;
+    uint32_t lo, lim;  // the ranks counted: [lo, lim)
+    slice_ranks<SLICE>(n, draw_limit, &lo, &lim);
+    const uint32_t blk0 = slice_first_block<SLICE>(lo);
     // this wave's emit blocks: the grid is capped (launch_binning) and strides over the blocks the frame HAS — n_visible is only known
     // here; a grid sized by the bound n >= V spent most of the kernel launching waves that had nothing to count (a rank of 8 shards:
     // 24 K workgroups for 2.4 K blocks)
-    for (uint32_t blk = blockIdx.x * COUNT_BLOCKS_PER_WG + (uint32_t)wave; blk < (uint32_t)nblk_n && blk * EMIT_THREADS < n;  // wave-uniform
+    for (uint32_t blk = blk0 + blockIdx.x * COUNT_BLOCKS_PER_WG + (uint32_t)wave; blk < (uint32_t)nblk_n && blk * EMIT_THREADS < (SLICE == 0 ? n : lim);  // wave-uniform
          blk += (uint32_t)grid_wgs * COUNT_BLOCKS_PER_WG) {
     const uint32_t r0 = blk * EMIT_THREADS + (uint32_t)lane * 4u;            // r = rank in the draw order
-    uint32_t cnt = 0;
+    uint32_t cnt = 0, full = 0;  // full (slice B): before the open-cell test
     if (r0 < lim) {
         int first;
-        if (PACKED && r0 + 4 <= lim) {  // the packed rects ride through the depth sort beside the ids: four {id, rect8} in two 16-B loads (r0 is a multiple of 4)
+        if (PACKED && r0 + 4 <= lim && (SLICE != 2 || r0 >= lo)) {  // the packed rects ride through the depth sort beside the ids: four {id, rect8} in two 16-B loads (r0 is a multiple of 4)
             const uint4 pa = *reinterpret_cast<const uint4 *>(sorted_pay + r0), pb = *reinterpret_cast<const uint4 *>(sorted_pay + r0 + 2);
             const uint32_t p[4] = {pa.y, pa.w, pb.y, pb.w};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const ushort4 rc = unpack_rect8(p[j]);
-                cnt += tiles_of(COARSE ? coarse_rect(rc) : rc, sh, &first);
+                const ushort4 rc = COARSE ? coarse_rect(unpack_rect8(p[j])) : unpack_rect8(p[j]);
+                const uint32_t c = tiles_of(rc, sh, &first);
+                if (SLICE == 2) { full += c; cnt += any_open_cell(rc, open_sum, os_x) ? c : 0u; }
+                else cnt += c;
             }
         } else {
             uint32_t g, packed;
-            for (uint32_t r = r0; r < r0 + 4 && r < lim; ++r) cnt += tiles_of(sorted_of<PACKED, COARSE>(r, sorted_ids, sorted_pay, rect, &g, &packed), sh, &first);
+            for (uint32_t r = r0; r < r0 + 4 && r < lim; ++r) {
+                if (SLICE == 2 && r < lo) continue;
+                const ushort4 rc = sorted_of<PACKED, COARSE>(r, sorted_ids, sorted_pay, rect, &g, &packed);
+                const uint32_t c = tiles_of(rc, sh, &first);
+                if (SLICE == 2) { full += c; cnt += any_open_cell(rc, open_sum, os_x) ? c : 0u; }
+                else cnt += c;
+            }
         }
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) cnt += (uint32_t)__shfl_xor((int)cnt, d, 64);
     if (lane == 0) blk_sum[blk] = cnt;
+    if (SLICE == 2) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) full += (uint32_t)__shfl_xor((int)full, d, 64);
+        if (lane == 0) blk_full[blk] = full;
+    }
     }
 }
 
 // Single workgroup (1024 threads): exclusive scan of blk_sum[0..nblk) in place; totals into ctrl.  Sixteen
 // consecutive sums per thread (four 16-B loads), so a 6 M-gaussian frame is one trip: serial scan in registers,
 // wave scan, 16 wave totals through LDS.  64-bit partials so that a D beyond 2^32 is still caught as overflow.
+// SLICE (the front slice, above): the emit blocks of the slice's ranks alone, offsets from 0; slice A leaves its D in the control block,
+// slice B adds to it the pair slots of its rects BEFORE the open-cell test (blk_full[]): D stays what max_pairs must cover without the
+// slice, while the overflow test is each slice's own (its pairs are what the buffers hold at one time).
+template <int SLICE>
 __global__ __launch_bounds__(1024) void pair_scan_kernel(uint32_t *__restrict__ blk_sum, int nblk_bound, FrameCtrl *ctrl,
-                                                         uint32_t max_pairs, size_t vstride)
+                                                         uint32_t max_pairs, size_t vstride, uint32_t draw_limit,
+                                                         const uint32_t *__restrict__ blk_full)
 {
     constexpr int PER = 16;
     __shared__ unsigned long long wsum[16];
@@ -171,7 +234,19 @@ __global__ __launch_bounds__(1024) void pair_scan_kernel(uint32_t *__restrict__ 
     blk_sum = view_slice(blk_sum, vstride); ctrl = view_slice(ctrl, vstride);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t n = ctrl->n_visible;
-    const int nblk = min(nblk_bound, (int)((n + EMIT_THREADS - 1) / EMIT_THREADS));
+    int nblk = min(nblk_bound, (int)((n + EMIT_THREADS - 1) / EMIT_THREADS));
+    unsigned long long full = 0;  // slice B: this thread's share of the blocks' unfiltered sums
+    if (SLICE != 0) {
+        uint32_t lo, hi;
+        slice_ranks<SLICE>(n, draw_limit, &lo, &hi);
+        const int blk0 = (int)slice_first_block<SLICE>(lo);
+        nblk = max(0, min(nblk, (int)((hi + EMIT_THREADS - 1) / EMIT_THREADS)) - blk0);
+        blk_sum += blk0;
+        if (SLICE == 2) {
+            blk_full = view_slice(blk_full, vstride) + blk0;
+            for (int i = tid; i < nblk; i += 1024) full += blk_full[i];
+        }
+    }
     if (tid == 0) s_carry = 0;
     __syncthreads();
     unsigned long long grand = 0;
@@ -219,9 +294,24 @@ __global__ __launch_bounds__(1024) void pair_scan_kernel(uint32_t *__restrict__ 
         if (tid == 0) s_carry = carry + tot;
         __syncthreads();
     }
+    if (SLICE == 2) {  // (uniform) the total of `full`, through the scan's LDS words
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) full += __shfl_xor(full, d, 64);
+        __syncthreads();
+        if (lane == 0) wsum[wave] = full;
+        __syncthreads();
+    }
     if (tid == 0) {
         const unsigned long long D = grand;
-        const uint32_t Dc = D > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)D;
+        unsigned long long Dall = D;  // what the whole draw order needs
+        if (SLICE == 2) {
+            Dall = ctrl->front_bbox;
+            for (int w = 0; w < 16; ++w) Dall += wsum[w];
+        }
+        const uint32_t Dc = Dall > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)Dall;
+        if (SLICE == 1) ctrl->front_bbox = Dc;
+        // (the cell sort leaves its survivor count only when it has a pair to sort: a slice B without one must not find slice A's)
+        if (SLICE == 2) ctrl->n_cpairs = 0u;
         if (D > (unsigned long long)max_pairs) { ctrl->batch_overflow |= 1u; ctrl->batch_need = max(ctrl->batch_need, Dc); }
         ctrl->overflow = ctrl->batch_overflow;  // bit 0: pairs; bit 1: the depth sort was short of passes (sort.hip)
         ctrl->n_pairs_bbox = (ctrl->batch_overflow & 1u) ? max(ctrl->batch_need, Dc) : Dc;
@@ -235,7 +325,7 @@ __global__ __launch_bounds__(1024) void pair_scan_kernel(uint32_t *__restrict__ 
 // (Round 4 measured the obvious refinement — gaussians of up to four cells, most of them, write their own pairs without search or
 // division, only the larger rects are load-balanced: 46.6 us either way.  The kernel is 13 K workgroups of a ~7-us dependent
 // chain each — counters, ids and rects, scan, stores — eight to a CU: six rounds of latency, not search or store throughput.)
-template <bool PACKED, bool COARSE, typename KeyT>  // KeyT: uint16_t when the keys fit (FramePlan.key16), else uint32_t
+template <bool PACKED, bool COARSE, typename KeyT, int SLICE>  // KeyT: uint16_t when the keys fit (FramePlan.key16), else uint32_t
 __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t *__restrict__ id_a, const uint32_t *__restrict__ id_b,
                                                                  const uint2 *__restrict__ pay_a, const uint2 *__restrict__ pay_b,
                                                                  const FrameCtrl *ctrl, const ushort4 *__restrict__ rect, RowShard sh,
@@ -243,11 +333,14 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
                                                                  const uint32_t *blk_off, uint32_t max_pairs,
                                                                  KeyT *__restrict__ pkey, uint32_t *__restrict__ pval,
                                                                  uint32_t draw_limit, RowShard tsh, uint32_t *blk_entries /* = blk_off: no __restrict__ on either */,
-                                                                 int grid_wgs, size_t vstride)
+                                                                 int grid_wgs, size_t vstride, const uint32_t *__restrict__ open_sum, int os_x,
+                                                                 const unsigned char *__restrict__ cell_open)
 {
+    static_assert(SLICE == 0 || (PACKED && COARSE), "the front slice bins by cells");
     id_a = view_slice(id_a, vstride); id_b = view_slice(id_b, vstride); pay_a = view_slice(pay_a, vstride); pay_b = view_slice(pay_b, vstride);
     ctrl = view_slice(ctrl, vstride); rect = view_slice(rect, vstride); rec = view_slice(rec, vstride); blk_off = view_slice(blk_off, vstride);
     pkey = view_slice(pkey, vstride); pval = view_slice(pval, vstride); blk_entries = view_slice(blk_entries, vstride);
+    if (SLICE == 2) { open_sum = view_slice(open_sum, vstride); cell_open = view_slice(cell_open, vstride); }
     __shared__ uint32_t scratch[8];
     __shared__ uint32_t s_off[EMIT_THREADS];   // exclusive pair offset of each gaussian inside the workgroup
     __shared__ uint32_t s_id[EMIT_THREADS];
@@ -261,10 +354,12 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
     const uint32_t *sorted_ids = odd ? id_b : id_a;  // PACKED: not read
     const uint2 *sorted_pay = odd ? pay_b : pay_a;   // else: not read
     const int tid = threadIdx.x;
+    uint32_t rank_lo = 0, rank_hi = n;  // the front slice's ranks
+    if (SLICE != 0) slice_ranks<SLICE>(n, draw_limit, &rank_lo, &rank_hi);
     // the grid is capped (launch_binning) and strides over the emit blocks the frame has: sized by the bound n >= V it launched more
     // workgroups that found nothing to do than ones that did (n_visible is only known here)
 #pragma unroll 1
-    for (uint32_t blk = blockIdx.x; blk * EMIT_THREADS < n; blk += (uint32_t)grid_wgs) {  // uniform
+    for (uint32_t blk = slice_first_block<SLICE>(rank_lo) + blockIdx.x; blk * EMIT_THREADS < rank_hi; blk += (uint32_t)grid_wgs) {  // uniform
     // the block's slot base first: its load is independent of everything below and would otherwise wait behind two barriers
     // (saturated at 2^32 - 1 by the scan: then nothing below is written)
     const unsigned long long base = blk_off[blk];
@@ -272,10 +367,11 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
     uint32_t cnt = 0, g = 0;
     int first = 0;
     ushort4 rc = make_ushort4(0, 0, 0, 0);
-    if (r < n && r < draw_limit) {
+    if (SLICE == 0 ? (r < n && r < draw_limit) : (r >= rank_lo && r < rank_hi)) {
         uint32_t packed;
         rc = sorted_of<PACKED, COARSE>(r, sorted_ids, sorted_pay, rect, &g, &packed);
         cnt = tiles_of(rc, sh, &first);
+        if (SLICE == 2 && !any_open_cell(rc, open_sum, os_x)) cnt = 0;  // (the count kernel's test: the offsets are its sums)
         if (COARSE) s_fine[tid] = packed;
     }
     const bool test = cnt > CULL_MIN_TILES;
@@ -321,6 +417,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void pair_emit_kernel(const uint32_t 
                     const bool mine = tsh.owns(fy);
                     mask |= (fx >= x0 && fx <= x1 && fy >= y0 && fy <= y1 && mine) ? 1u << q : 0u;
                 }
+                if (SLICE == 2) mask &= (uint32_t)cell_open[ty * (os_x - 1) + tx];  // a closed tile never blends again
                 const bool hit = mask != 0u && (!tested || footprint_hits_rect(s_q0[lo], s_q1[lo], (float)(tx * 32), (float)(tx * 32 + 31),
                                                                                (float)(ty * 32), (float)(ty * 32 + 31)));
                 pkey[o] = (KeyT)((hit ? (uint32_t)ty << bits_x : culled_row) | (uint32_t)tx);
@@ -383,8 +480,71 @@ __global__ __launch_bounds__(256) void tile_ranges_kernel(const KeyT *__restrict
     }
 }
 
-int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, hipStream_t s)
+// Between the two slices of a front-slice frame, one workgroup per view: cell_open[cell] = the open bits of the cell's tiles
+// (tile_open[], written by every workgroup of slice A's blend), open_sum[y][x] = open cells in rows < y and columns < x (a row and a
+// column of zeros ahead of the cells: any rect's count is four loads), and what slice A's emit left of E — its workgroups' partial
+// counts, which slice B's kernels overwrite from block ent_first on — into the control block for gsr_read_stats.
+__global__ __launch_bounds__(1024) void open_cells_kernel(const unsigned char *__restrict__ tile_open, unsigned char *__restrict__ cell_open,
+                                                          uint32_t *open_sum, FrameCtrl *ctrl, const uint32_t *__restrict__ blk_entries,
+                                                          int tiles_x, int tiles_y, int ctiles_x, int ctiles_y, int nblk_bound, size_t vstride)
 {
+    tile_open = view_slice(tile_open, vstride); cell_open = view_slice(cell_open, vstride); open_sum = view_slice(open_sum, vstride);
+    ctrl = view_slice(ctrl, vstride); blk_entries = view_slice(blk_entries, vstride);
+    __shared__ unsigned long long part[16];
+    const int tid = threadIdx.x, os_x = ctiles_x + 1;
+    for (int c = tid; c < ctiles_x * ctiles_y; c += 1024) {
+        const int cy = c / ctiles_x, cx = c - cy * ctiles_x;
+        uint32_t m = 0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int tx = 2 * cx + (q & 1), ty = 2 * cy + (q >> 1);
+            if (tx < tiles_x && ty < tiles_y && tile_open[ty * tiles_x + tx] != 0) m |= 1u << q;
+        }
+        cell_open[c] = (unsigned char)m;
+        open_sum[(cy + 1) * os_x + cx + 1] = m != 0u ? 1u : 0u;
+    }
+    for (int x = tid; x <= ctiles_x; x += 1024) open_sum[x] = 0u;
+    for (int y = tid; y <= ctiles_y; y += 1024) open_sum[y * os_x] = 0u;
+    __syncthreads();
+    for (int y = 1 + tid; y <= ctiles_y; y += 1024) {  // along the rows
+        uint32_t run = 0;
+        for (int x = 1; x <= ctiles_x; ++x) { run += open_sum[y * os_x + x]; open_sum[y * os_x + x] = run; }
+    }
+    __syncthreads();
+    for (int x = 1 + tid; x <= ctiles_x; x += 1024) {  // down the columns
+        uint32_t run = 0;
+        for (int y = 1; y <= ctiles_y; ++y) { run += open_sum[y * os_x + x]; open_sum[y * os_x + x] = run; }
+    }
+    // slice A's entries: the partial counts of its emit blocks
+    uint32_t lo, hi;
+    slice_ranks<1>(ctrl->n_visible, 0xFFFFFFFFu, &lo, &hi);
+    const int nblk = min(nblk_bound, (int)((hi + EMIT_THREADS - 1) / EMIT_THREADS));
+    unsigned long long e = 0;
+    for (int i = tid; i < nblk; i += 1024) e += blk_entries[i];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) e += __shfl_xor(e, d, 64);
+    if ((tid & 63) == 0) part[tid >> 6] = e;
+    __syncthreads();
+    if (tid == 0) {
+        e = 0;
+        for (int w = 0; w < 16; ++w) e += part[w];
+        ctrl->front_entries = e > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)e;
+        ctrl->ent_first = slice_first_block<2>(hi);
+    }
+}
+
+int launch_open_cells(const Workspace &ws, hipStream_t s)
+{
+    const int nblk_n = (int)((ws.n + EMIT_THREADS - 1) / EMIT_THREADS);
+    hipLaunchKernelGGL(open_cells_kernel, dim3(1, (unsigned)ws.views), dim3(1024), 0, s, ws.tile_open, ws.cell_open, ws.open_sum, ws.ctrl, ws.blk_sum,
+                       ws.tiles_x, ws.tiles_y, ws.ctiles_x, ws.ctiles_y, ws.n > 0 ? nblk_n : 0, ws.view_stride);
+    GSR_HIP(hipGetLastError());
+    return GSR_OK;
+}
+
+int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, hipStream_t s, int slice)
+{
+    if (slice != 0 && !(plan.front_slice && plan.coarse)) { set_error("a slice of a frame that has none"); return GSR_ERR_BAD_ARG; }
     const int n_tiles = ws.tiles_x * ws.tiles_y;
     if (ws.n <= 0) {  // no count kernel to clear the ranges (per tile, and per cell for a blend that reads the cell lists)
         for (int v = 0; v < ws.views; ++v) {
@@ -399,20 +559,30 @@ int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan 
     const uint32_t cap = (uint32_t)ws.max_pairs;
     const uint32_t limit = opts.draw_limit > 0 ? (uint32_t)opts.draw_limit : 0xFFFFFFFFu;
     const int nblk_n = (int)((ws.n + EMIT_THREADS - 1) / EMIT_THREADS);                       // emit blocks (the bound: n >= V)
+    // (slice A: those of its ranks, L <= ceil(n / FRONT_SLICE_FRACTION))
+    const int nblk_s = slice == 1 ? (int)(((ws.n + FRONT_SLICE_FRACTION - 1) / FRONT_SLICE_FRACTION + EMIT_THREADS - 1) / EMIT_THREADS) : nblk_n;
+    const int os_x = ws.ctiles_x + 1;
     // the count kernel: one wave per emit block (it also zeroes ranges[] / cranges[], grid-stride); both grids are capped and stride
     // over the blocks the frame has — V is known on the device only
-    const int nblk_count = std::min((nblk_n + COUNT_BLOCKS_PER_WG - 1) / COUNT_BLOCKS_PER_WG, EMIT_GRID_CAP / COUNT_BLOCKS_PER_WG);
-    const int nblk_emit = std::min(nblk_n, EMIT_GRID_CAP);
-#define GSR_COUNT(P, C) hipLaunchKernelGGL((pair_count_kernel<P, C>), dim3(nblk_count, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.pay[0], ws.pay[1], \
+    const int nblk_count = std::min((nblk_s + COUNT_BLOCKS_PER_WG - 1) / COUNT_BLOCKS_PER_WG, EMIT_GRID_CAP / COUNT_BLOCKS_PER_WG);
+    const int nblk_emit = std::min(nblk_s, EMIT_GRID_CAP);
+#define GSR_COUNT(P, C, S) hipLaunchKernelGGL((pair_count_kernel<P, C, S>), dim3(nblk_count, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.pay[0], ws.pay[1], \
                                            ws.ctrl, ws.rect, C ? plan.csh : plan.rs, ws.blk_sum, ws.ranges, n_tiles, limit, ws.cranges, n_ctiles, ws.ctrl, \
-                                           C ? (uint32_t)(reinterpret_cast<const char *>(ws.blk_sum) - reinterpret_cast<const char *>(ws.ctrl)) : 0u, nblk_n, nblk_count, vs)
-#define GSR_EMIT_T(P, C, T) hipLaunchKernelGGL((pair_emit_kernel<P, C, T>), dim3(nblk_emit, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.pay[0], ws.pay[1], \
+                                           C ? (uint32_t)(reinterpret_cast<const char *>(ws.blk_sum) - reinterpret_cast<const char *>(ws.ctrl)) : 0u, nblk_n, nblk_count, vs, \
+                                           ws.open_sum, os_x, ws.blk_full)
+#define GSR_EMIT_T(P, C, T, S) hipLaunchKernelGGL((pair_emit_kernel<P, C, T, S>), dim3(nblk_emit, nv), dim3(EMIT_THREADS), 0, s, ws.val[0], ws.val[1], ws.pay[0], ws.pay[1], \
                                           ws.ctrl, ws.rect, C ? plan.csh : plan.rs, plan.bits_x, plan.grid_y, ws.rec, ws.blk_sum, cap, reinterpret_cast<T *>(ws.pkey[0]), ws.pval[0], limit, \
-                                          plan.rs, ws.blk_sum, nblk_emit, vs)
-#define GSR_EMIT(P, C) do { if (plan.key16) GSR_EMIT_T(P, C, uint16_t); else GSR_EMIT_T(P, C, uint32_t); } while (0)
-    if (plan.coarse) GSR_COUNT(true, true); else if (plan.packed_rect) GSR_COUNT(true, false); else GSR_COUNT(false, false);
-    hipLaunchKernelGGL(pair_scan_kernel, dim3(1, nv), dim3(1024), 0, s, ws.blk_sum, nblk_n, ws.ctrl, cap, vs);
-    if (plan.coarse) GSR_EMIT(true, true); else if (plan.packed_rect) GSR_EMIT(true, false); else GSR_EMIT(false, false);
+                                          plan.rs, ws.blk_sum, nblk_emit, vs, ws.open_sum, os_x, ws.cell_open)
+#define GSR_EMIT(P, C, S) do { if (plan.key16) GSR_EMIT_T(P, C, uint16_t, S); else GSR_EMIT_T(P, C, uint32_t, S); } while (0)
+#define GSR_SCAN(S) hipLaunchKernelGGL(pair_scan_kernel<S>, dim3(1, nv), dim3(1024), 0, s, ws.blk_sum, nblk_n, ws.ctrl, cap, vs, limit, ws.blk_full)
+    if (slice == 1) { GSR_COUNT(true, true, 1); GSR_SCAN(1); GSR_EMIT(true, true, 1); }
+    else if (slice == 2) { GSR_COUNT(true, true, 2); GSR_SCAN(2); GSR_EMIT(true, true, 2); }
+    else {
+    if (plan.coarse) GSR_COUNT(true, true, 0); else if (plan.packed_rect) GSR_COUNT(true, false, 0); else GSR_COUNT(false, false, 0);
+    GSR_SCAN(0);
+    if (plan.coarse) GSR_EMIT(true, true, 0); else if (plan.packed_rect) GSR_EMIT(true, false, 0); else GSR_EMIT(false, false, 0);
+    }
+#undef GSR_SCAN
 #undef GSR_COUNT
 #undef GSR_EMIT
 #undef GSR_EMIT_T

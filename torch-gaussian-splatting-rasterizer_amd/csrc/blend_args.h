@@ -34,6 +34,9 @@ struct BlendArgs {
     int col_degree, col_sh16;
     size_t view_stride;     // several views per launch (gridDim.y): bytes between the views' workspace slices ...
     size_t out_view_stride; // ... and between their frames
+    // the front slice (binning.hip): where slice A's blend leaves an open tile's accumulators and slice B's finds them
+    float4 *front_acc[2];      // [tiles][128] each, {T, Cr, Cg, Cb}: the first / second pixel of a thread of the two-quadrant walk
+    unsigned char *tile_open;  // [tiles]
 };
 
 // The arguments of view blockIdx.y (the host fills in view 0's): a new value, built field by field — mutating the kernel's argument
@@ -62,6 +65,7 @@ __device__ __forceinline__ BlendArgs blend_args_of_view(const BlendArgs &a)
     b.col_cc[0] = a.col_cc[0]; b.col_cc[1] = a.col_cc[1]; b.col_cc[2] = a.col_cc[2];
     b.col_degree = a.col_degree; b.col_sh16 = a.col_sh16;
     b.view_stride = a.view_stride; b.out_view_stride = a.out_view_stride;
+    b.front_acc[0] = at(a.front_acc[0], o); b.front_acc[1] = at(a.front_acc[1], o); b.tile_open = at(a.tile_open, o);
     return b;
 }
 

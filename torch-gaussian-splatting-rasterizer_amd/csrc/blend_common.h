@@ -273,21 +273,23 @@ __device__ __forceinline__ void quadrants_finished(const BlendClassLds &cl, int 
 // Epilogue, every thread: the counters gsr_read_stats totals.  COLOUR, the colour frame's kernels: stat[5] = the workgroup's
 // deferred-colour evaluations (wave totals into LDS, one store), and tile_work = next frame's launch-order hint.  The feature
 // blend evaluates no colour and leaves tile_work what the last colour blend left.
-template <int THREADS, bool COLOUR>
+// ADD (slice B of a front-slice frame, blend.hip): the counters and the hint are added to what slice A's blend left — in the slot,
+// which was another tile's there: only the totals over all slots are ever read.
+template <int THREADS, bool COLOUR, bool ADD = false>
 __device__ __forceinline__ void blend_stats_out(const BlendArgs &a, const TilePixel &t, int tid, int lane, int wave, const BlendLds &lds,
                                                 uint32_t evaluated, uint32_t fetched, uint32_t col_evals)
 {
     if (lane == 0) {
-        t.stat[wave] = evaluated;
-        if (THREADS == 128) t.stat[2 + wave] = 0;
+        t.stat[wave] = (ADD ? t.stat[wave] : 0u) + evaluated;
+        if (THREADS == 128 && !ADD) t.stat[2 + wave] = 0;
     }
     if (COLOUR) {
-        if (tid == 0) { t.stat[4] = fetched; a.tile_work[t.tile] = fetched + 1u; }
+        if (tid == 0) { t.stat[4] = (ADD ? t.stat[4] : 0u) + fetched; a.tile_work[t.tile] = (ADD ? a.tile_work[t.tile] : 1u) + fetched; }
 #pragma unroll
         for (int d = 32; d >= 1; d >>= 1) col_evals += (uint32_t)__shfl_xor((int)col_evals, d, 64);
         if (lane == 0 && col_evals) atomicAdd(lds.col, col_evals);
         __syncthreads();
-        if (tid == 0) t.stat[5] = *lds.col;
+        if (tid == 0) t.stat[5] = (ADD ? t.stat[5] : 0u) + *lds.col;
     } else if (tid == 0) {
         t.stat[4] = fetched; t.stat[5] = 0;
     }

@@ -45,6 +45,12 @@ struct FrameCtrl {
                              // A frame short of passes (flagged, to be re-rendered) still hands binning a buffer this frame's sort filled
     uint32_t depth_key_max;  // maximum of the frame's valid depth keys (pass-0 histogram).  Cleared with the frame AND by the pass-0
                              // rowscan once consumed (gsr_bin_sort may be repeated on one gsr_preprocess).
+    // the front slice (FramePlan.front_slice; binning.hip has the sequence): what slice A leaves for the frame's totals.  0 on every
+    // other path (cleared with the frame)
+    uint32_t front_bbox;     // pair slots of slice A's rects (the first part of D)
+    uint32_t front_entries;  // tile-list entries slice A emitted (the first part of E): open_cells_kernel totals A's partial counts
+    uint32_t ent_first;      // first emit block whose partial count at ent_off is slice B's (those before it are totalled in front_entries)
+    uint32_t _pad0;
     // ---- everything below survives the per-frame clear of a frame rendered with GsrOptions.keep_flags (and of the later views
     // ---- of a batch): the record of what went wrong in ANY frame since the last full clear
     uint32_t batch_overflow;     // bit 0 pair overflow, bit 1 depth sort short of passes
@@ -76,11 +82,17 @@ constexpr uint32_t KEY_INVALID = 0xFFFFFFFFu;
 struct Workspace {
     FrameCtrl *ctrl;
     GaussRec *rec;        // [n]
-    ushort4 *rect;        // [n]   tile rect {tx0, ty0, tx1, ty1} (exclusive upper), after footprint refinement
+    ushort4 *rect;        // [n]   tile rect {tx0, ty0, tx1, ty1} (exclusive upper), after footprint refinement.  Written and read only when
+                          //       the rect does not travel packed (FramePlan.packed_rect false); on the packed path nobody touches it, and a
+                          //       front-slice frame keeps its planes there (front_acc[0], tile_open, cell_open, open_sum)
     uint32_t *rect8[2];   // [n]   the same rect packed x0 | y0<<8 | (x1-1)<<16 | (y1-1)<<24, written per gaussian into rect8[0] when the
                           //       tile grid fits 8 bits (frames up to 4096 px); depth-sort pass 0 moves it into the payload (pay[])
                           //       ([1]: a shard rank's run scratch)
-    uint32_t *key[2];     // [n]   depth keys (ping-pong)
+    uint32_t *key[2];     // [n]   depth keys (ping-pong); key[1] also: a shard rank's run scratch (preprocess.hip).  CONTRACT: dead between
+                          //       the last pass of launch_depth_sort and the next preprocess — nothing after the sort reads a key — and key[1]
+                          //       follows key[0] at align_up(4 n, 256) (carve_workspace checks it): a front-slice frame, which is never
+                          //       a shard's, keeps front_acc[1] and blk_full over the two.  A new reader of keys behind the sort, or a
+                          //       new array carved between them, must take the overlay out of carve_workspace first
     uint32_t *val[2];     // [n]   gaussian ids (ping-pong) — the depth sort's payload when the rect does not ride along; val[0] also: a
                           //       shard rank's compacted ids entering pass 0
     uint2 *pay[2];        // [n]   {gaussian id, rect8}: the depth sort's payload from pass 0's output on when the rect rides along
@@ -98,6 +110,14 @@ struct Workspace {
                           // the launch-order hint of the next frame (blend.hip, tile_order_kernel); never cleared, never trusted
     uint32_t *blend_stats; // [tile_order slots][BLEND_STAT_WORDS] per-workgroup counters: plain stores, no atomics (40 k
                           // same-address atomics per frame put a 0.45 ms floor under the blend kernel)
+    // the front slice (FramePlan.front_slice): no bytes of their own — they lie over rect[] and key[] (carve_workspace), dead on the
+    // coarse path once the depth sort has run.  front_fits: there is room for them
+    bool front_fits;
+    float4 *front_acc[2]; // [tiles][128] each: {T, Cr, Cg, Cb} of the first / second pixel of every thread of a tile slice A left open, as its blend's registers held them
+    unsigned char *tile_open;  // [tiles] 1: slice A's list ended with a quadrant of the tile still live
+    unsigned char *cell_open;  // [ctiles] bit q: tile q of the 32x32 cell is open
+    uint32_t *open_sum;   // [(ctiles_y + 1) * (ctiles_x + 1)] open_sum[y][x] = open cells in rows < y and columns < x
+    uint32_t *blk_full;   // [like blk_sum] slice B: pair slots of each emit block's rects before the open-cell test (for D)
     int64_t n;
     int64_t max_pairs;
     int tiles_x, tiles_y;
@@ -203,8 +223,17 @@ struct FramePlan {
     bool cell_lists;       // the blend filters the 32x32-cell lists by tile bit itself
     int rows;              // tile rows the rank blends
     BlendKernel blend;
+    // the front slice: the nearest 1 / FRONT_SLICE_FRACTION of the draw order is binned and blended first, the rest is binned only where a
+    // tile is still open after it (binning.hip has the sequence and why the frame is the single pass's bit for bit)
+    bool front_slice;
 };
-FramePlan plan_frame(const Workspace &ws, const GsrOptions &opts);  // ws: after check_frame, with ws.views set
+#ifndef GSR_FRONT_SLICE_FRACTION
+#define GSR_FRONT_SLICE_FRACTION 8
+#endif
+constexpr uint32_t FRONT_SLICE_FRACTION = GSR_FRONT_SLICE_FRACTION;  // (the macro: the sweep builds of csrc/Makefile, libgsr_fsfrac%.so)
+// ws: after check_frame, with ws.views set.  colour_frame: the fused colour-frame entries without a final-T output (render_views) — the
+// only callers that may be handed a front slice
+FramePlan plan_frame(const Workspace &ws, const GsrOptions &opts, bool colour_frame = false);
 
 // A view's camera as the per-gaussian kernels hold it (preprocess.hip, project_backward.hip): a kernel argument
 struct Cam {
@@ -242,13 +271,16 @@ int launch_scene_order(int64_t n, const float *means, uint32_t *perm_out, void *
 int launch_pair_sort(const Workspace &ws, const FramePlan &plan, const uint32_t *n_dev, uint32_t *n_out, int *result_buf, hipStream_t s);
 // Stage 2b: pairs of the depth-sorted gaussians -> per-tile depth-ordered lists + ranges[] (count, scan, emit, sort, ranges,
 // and with coarse binning the expansion).
-int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, hipStream_t s);
+// slice (plan.front_slice only): 0 = the whole draw order; 1 = slice A, its first 1 / FRONT_SLICE_FRACTION; 2 = slice B, the rest, where open
+int launch_binning(const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, hipStream_t s, int slice = 0);
+// Between the slices: cell_open[], open_sum[] from slice A's tile_open[], and A's share of E into the control block
+int launch_open_cells(const Workspace &ws, hipStream_t s);
 // out_image: view 0's frame, view v's lies v * out_view_stride BYTES further (out_T: single views only).  scene: where deferred
 // colours are evaluated from (single views only); nullptr = what the preprocess left in the workspace's control block
 int launch_blend(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, void *out_image,
-                 size_t out_view_stride, float *out_T, const GsrScene *scene, hipStream_t s);
+                 size_t out_view_stride, float *out_T, const GsrScene *scene, hipStream_t s, int slice = 0);
 // The blend's launch order (blend.hip, tile_order_kernel): returns the launch slots per view; use_hint: by what each tile staged last frame
-int launch_tile_order(const Workspace &ws, const FramePlan &plan, bool use_hint, hipStream_t s);
+int launch_tile_order(const Workspace &ws, const FramePlan &plan, bool use_hint, hipStream_t s, int slice = 0);
 // Stage 3 for caller-supplied channels (blend_features.hip): out_map[p] = sum_i w_i(p) features[i], single views only
 int launch_blend_features(const GsrCamera &cam, const GsrOptions &opts, const Workspace &ws, const FramePlan &plan, const float *features,
                           float *out_map, float *out_T, hipStream_t s);
